@@ -4,6 +4,14 @@ metric; workload c3 = configs[2]: per slot 16384 attestation sets + 1024 aggrega
 x 3 sets = 17408 jobs / 19456 sets, signing roots shared per committee as on mainnet).
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3] [--slots B] [--inflight F]
+                  [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up (W steps on one engine), times K steps and prints the headline line:
+K batch verifications in all, dealt round-robin to the F batches in flight; ms_per_step = the timed
+region / K, value = sets per batch x K / the timed region.  --dump-outputs DIR then writes the last
+timed step's per-job verdicts (what lb_batch_verify's caller receives) to DIR/codes.npy; the inputs
+are seeded, so two builds can be compared output for output.  --full adds every secondary
+measurement listed below (each on at most 20 steps, however many K).
 
 One process per GPU.  Under torchrun (WORLD_SIZE set) every rank runs main(); `--gpus N` with
 N > 1 and no WORLD_SIZE relaunches itself under torch.distributed.run (127.0.0.1) before any GPU
@@ -16,7 +24,7 @@ independent engines; 5 / 6 / 7 in flight measured 9.7 / 10.4 / 10.9 M sets/s in 
 lb_batch_verify over one resident batch: all kernels + CSPRNG scalars + per-job result readback.
 Inputs are in HBM before the timed region.  Rank 0 prints one JSON line.
 
-Secondary measurements on the same line (rank 0; N = 1 unless noted):
+Secondary measurements on the same line under --full (rank 0; N = 1 unless noted):
   value_one_batch_in_flight     one engine, the same batch
   value_distinct_roots          every signing root distinct (the no-sharing bound)
   value_one_invalid_per_batch   one wrong-message attestation per slot (the invalid-set search)
@@ -103,6 +111,12 @@ def parse():
                     help="secondary legs to run (comma list; A/B runs pick one)")
     ap.add_argument("--dropin-engines", type=int, default=4)
     ap.add_argument("--dropin-rounds", type=int, default=10, help="drop-in leg: timed rounds (median reported)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary measurements (one batch in flight + roofline, range-sync "
+                         "segments, distinct roots, the --legs, CPU baselines); without it only the headline runs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (the per-job verdicts) "
+                         "to DIR/codes.npy (float32)")
     return ap.parse_args()
 
 
@@ -213,19 +227,28 @@ def roofline(counts, packed, stage_ms):
             "device_ms": round(wall, 3), "stages": per}
 
 
-def run_inflight(batches, steps, expected, barrier, step_fns=None, mark=None):
+def split_steps(steps, n):
+    """`steps` batch verifications dealt round-robin to n engines (the same split on every rank, so
+    the per-engine collectives of --exchange pair up): step s runs on engine s mod n"""
+    return [steps // n + (1 if k < steps % n else 0) for k in range(n)]
+
+
+def run_inflight(batches, steps, expected, barrier, step_fns=None, mark=None, results=None):
     """len(batches) batches in flight: independent engines (own streams + workspaces), one host
-    thread each, every engine verifying its own resident copy of the slot `steps` times
+    thread each, every engine verifying its own resident copy of the slot `steps` times, or
+    steps[k] times for a list (the headline: split_steps)
     (step_fns[k]() instead of batches[k].verify() when given: the --exchange steps).
-    mark(): called right before and right after the timed region (profiling markers)."""
+    mark(): called right before and right after the timed region (profiling markers).
+    results: a list that receives every engine's last result (None where it ran no step)."""
     import threading
     fns = step_fns or [b.verify for b in batches]
     for f in fns[1:]:
         f()
     res = [None] * len(batches)
+    per = steps if isinstance(steps, list) else [steps] * len(batches)
 
     def run(k):
-        for _ in range(steps):
+        for _ in range(per[k]):
             res[k] = fns[k]()
 
     barrier()
@@ -242,8 +265,18 @@ def run_inflight(batches, steps, expected, barrier, step_fns=None, mark=None):
     if mark:
         mark()
     for r in res:
-        assert np.array_equal(np.asarray(r), expected), "verification results differ"
+        assert r is None or np.array_equal(np.asarray(r), expected), "verification results differ"
+    if results is not None:
+        results[:] = res
     return el
+
+
+def dump_outputs(path, rank, codes):
+    """--dump-outputs: what the last timed step returned to its caller, the per-job verdicts
+    (1 valid / 0 invalid / -code rejected, the C ABI's out_job convention; exact in float32)"""
+    os.makedirs(path, exist_ok=True)
+    name = "codes.npy" if rank == 0 else "codes_rank%d.npy" % rank
+    np.save(os.path.join(path, name), np.asarray(codes, dtype=np.float32))
 
 
 def median_ms(fn, reps):
@@ -637,55 +670,74 @@ def main():
 
     for _ in range(a.warmup):
         codes = step()
-    assert np.array_equal(np.asarray(codes), wl.expected), "verification results differ from expected"
+        assert np.array_equal(np.asarray(codes), wl.expected), "verification results differ from expected"
 
-    # (1) one batch in flight: K profiled steps (per-stage HIP-event times feed the roofline)
-    stage_ms = {}
-    eng.set_profiling(True)
-    barrier()
-    t1 = time.perf_counter()
-    for _ in range(a.steps):
-        codes = step()
-        for k, v in eng.last_profile().items():
-            stage_ms[k] = stage_ms.get(k, 0.0) + v
-    barrier()
-    el_single = time.perf_counter() - t1
-    eng.set_profiling(False)
-    stage_ms = {k: v / a.steps for k, v in stage_ms.items()}
-    el = el_single
+    # the secondary measurements (--full) take at most 20 steps each, however many the headline times
+    sec = argparse.Namespace(**vars(a))
+    sec.steps = min(a.steps, 20)
     inflight = a.inflight
+    # (1) one batch in flight: K profiled steps (per-stage HIP-event times feed the roofline).  With
+    # --inflight 1 this loop is the headline itself (profiled only under --full); with more batches in
+    # flight it is a run of its own and belongs to --full
+    stage_ms = {}
+    el = el_single = None
+    if a.full or inflight == 1:
+        n_single = a.steps if inflight == 1 else sec.steps
+        if a.full:
+            eng.set_profiling(True)
+        barrier()
+        t1 = time.perf_counter()
+        for _ in range(n_single):
+            codes = step()
+            if a.full:
+                for k, v in eng.last_profile().items():
+                    stage_ms[k] = stage_ms.get(k, 0.0) + v
+        barrier()
+        el_single = (time.perf_counter() - t1) * a.steps / n_single
+        eng.set_profiling(False)
+        stage_ms = {k: v / n_single for k, v in stage_ms.items()}
+        assert np.array_equal(np.asarray(codes), wl.expected), "verification results differ from expected"
+        el = el_single
+    last = [codes] if inflight == 1 else []
     # LB_PROF_MARK=1: an empty lb_fp12_product_is_one (one k_partials_check dispatch) right before
     # and after the headline's timed region, so a counter pass (tools/valu_util.py) can keep
     # exactly the timed region's dispatches (not the workload generator's k_sign, nor the one
     # batch in flight above)
     mark = (lambda: engs[0].product_is_one([])) if os.environ.get("LB_PROF_MARK") == "1" else None
+    # (2) the headline: --steps batch verifications in all, dealt to the engines in flight (a step =
+    # one lb_batch_verify; ms_per_step = the timed region over its steps)
     if inflight > 1:
-        el = run_inflight(batches, a.steps, wl.expected, barrier, [make_step(k) for k in range(inflight)], mark)
+        el = run_inflight(batches, split_steps(a.steps, inflight), wl.expected, barrier,
+                          [make_step(k) for k in range(inflight)], mark, results=last)
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, rank, last[(a.steps - 1) % inflight])
     el_t = torch.tensor([el], dtype=torch.float64, device=coll_dev)
     if world > 1:
         dist.all_reduce(el_t, op=dist.ReduceOp.MAX)
     el = float(el_t.item())
-    es_t = torch.tensor([el_single], dtype=torch.float64, device=coll_dev)
-    if world > 1:
-        dist.all_reduce(es_t, op=dist.ReduceOp.MAX)
-    value_single = n_sets * world * a.steps / float(es_t.item())
-    ms_per_step = el / (a.steps * inflight) * 1e3
-    value = n_sets * world * a.steps * inflight / el
+    value_single = None
+    if el_single is not None:
+        es_t = torch.tensor([el_single], dtype=torch.float64, device=coll_dev)
+        if world > 1:
+            dist.all_reduce(es_t, op=dist.ReduceOp.MAX)
+        value_single = n_sets * world * a.steps / float(es_t.item())
+    ms_per_step = el / a.steps * 1e3
+    value = n_sets * world * a.steps / el
 
     # N > 1: the same batches in flight with the north-star single-verdict exchange (576-byte Fp12
     # partials all-gathered over RCCL, one final exponentiation of their product per step)
     exchange_leg = None
-    if world > 1 and not a.exchange and "exchange" in a.legs.split(","):
-        elx = run_inflight(batches, a.steps, wl.expected, barrier,
+    if a.full and world > 1 and not a.exchange and "exchange" in a.legs.split(","):
+        elx = run_inflight(batches, sec.steps, wl.expected, barrier,
                            [make_step(k, exchange=True) for k in range(inflight)])
         elx_t = torch.tensor([elx], dtype=torch.float64, device=coll_dev)
         dist.all_reduce(elx_t, op=dist.ReduceOp.MAX)
         elx = float(elx_t.item())
-        exchange_leg = {"value": round(n_sets * world * a.steps * inflight / elx, 1),
-                        "ms_per_step": round(elx / (a.steps * inflight) * 1e3, 3),
+        exchange_leg = {"value": round(n_sets * world * sec.steps * inflight / elx, 1),
+                        "ms_per_step": round(elx / (sec.steps * inflight) * 1e3, 3),
                         "collective": "all_gather of 576-byte Fp12 partials per batch (backend %s)" % backend,
                         "world_size_seen": world_seen}
-    roof = roofline(load_counts(), wl.packed, stage_ms)
+    roof = roofline(load_counts(), wl.packed, stage_ms) if a.full else None
     if roof is not None:
         # the headline's own fraction: all stages' algorithmic MACs per batch over the measured
         # time per batch at this configuration (ms_per_step, batches in flight), against the peak
@@ -697,44 +749,44 @@ def main():
         roof["stage_ms_source"] = ("HIP events on each stage's own stream, one batch in flight, %d profiled steps; "
                                    "profiles/r6_rocprof_kernel_stats_inflight1.csv holds rocprof's per-kernel "
                                    "averages for the same configuration (the round-6 final tree); "
-                                   "tools/trace_stage_avg.py -> profiles/r6_inflight1_decode_check.json compares them" % a.steps)
+                                   "tools/trace_stage_avg.py -> profiles/r6_inflight1_decode_check.json compares them" % n_single)
         roof["valu_util_source"] = ("profiles/r6_valu_util.json: per-kernel VALU instructions per batch and VALU-busy "
                                     "fraction from rocprofv3 counters at this configuration (tools/valu_util.py)")
         roof["resource_table"] = "profiles/r6_resource_usage.txt (VGPR / AGPR / scratch / LDS per kernel, hipcc remarks)"
     segments = None
-    if a.workload == "c3" and "segment" in a.legs.split(","):
-        segments = segment_legs(a, eng, W, rank, world, barrier, coll_dev, backend)
+    if a.full and a.workload == "c3" and "segment" in a.legs.split(","):
+        segments = segment_legs(sec, eng, W, rank, world, barrier, coll_dev, backend)
     # secondary: the same slot shape with every signing root distinct (no sharing to exploit)
     value_distinct = None
-    if a.workload == "c3" and not a.no_distinct and not a.exchange:
+    if a.full and a.workload == "c3" and not a.no_distinct and not a.exchange:
         wd = W.make(eng, "c3_distinct", seed=W.SEED + rank, **wkw)
         for b in batches:
             b.free()
         batches = [e.upload(W.indexed_for(e, wd)) for e in engs]
         batches[0].verify()
-        eld = run_inflight(batches, a.steps, wd.expected, barrier) if a.inflight > 1 else None
+        eld = run_inflight(batches, sec.steps, wd.expected, barrier) if a.inflight > 1 else None
         if eld is None:
             barrier()
             t1 = time.perf_counter()
-            for _ in range(a.steps):
+            for _ in range(sec.steps):
                 batches[0].verify()
             barrier()
             eld = time.perf_counter() - t1
         eld_t = torch.tensor([eld], dtype=torch.float64, device=coll_dev)
         if world > 1:
             dist.all_reduce(eld_t, op=dist.ReduceOp.MAX)
-        value_distinct = wd.packed.n_sets * world * a.steps * a.inflight / float(eld_t.item())
+        value_distinct = wd.packed.n_sets * world * sec.steps * a.inflight / float(eld_t.item())
     for b in batches:
         b.free()
-    solo = rank == 0 and world == 1 and not a.no_extra and a.workload == "c3" and not a.exchange
+    solo = a.full and rank == 0 and world == 1 and not a.no_extra and a.workload == "c3" and not a.exchange
     extra, dropin, wc1 = {}, None, None
     if solo:
-        extra, wc1 = extra_legs(a, engs, barrier, W, wl)
+        extra, wc1 = extra_legs(sec, engs, barrier, W, wl)
     for e in engs:
         e.close()
     if solo and "dropin" in a.legs.split(","):
         try:
-            dropin = dropin_leg(a, W, lambda: Engine(local))
+            dropin = dropin_leg(sec, W, lambda: Engine(local))
         except Exception as e:  # reported, never fatal
             dropin = {"error": repr(e)}
     if solo and "roots" in a.legs.split(","):
@@ -743,7 +795,7 @@ def main():
         except Exception as e:  # reported, never fatal
             extra["signing_roots"] = {"error": repr(e)}
     cpu = cpu_c1 = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         try:
             from oracle.cpu_pool import time_c1, time_cpu_pool
             cpu = time_cpu_pool(wl.packed, seconds=a.cpu_seconds, threads=a.cpu_threads,
@@ -768,10 +820,11 @@ def main():
                        "exchange": bool(a.exchange), "inflight": inflight, "world_size_seen": world_seen,
                        "pubkeys": "96-byte keys per set" if a.pubkey_bytes else "indices into the GPU-resident table",
                        "signing_roots_per_gpu": n_roots(wl.packed)},
-            "value_one_batch_in_flight": round(value_single, 1),
-            "batch_latency_ms": round(el / a.steps * 1e3, 1),
-            "value_distinct_roots": None if value_distinct is None else round(value_distinct, 1),
+            "batch_latency_ms": round(ms_per_step * inflight, 1),
         }
+        if a.full:
+            line["value_one_batch_in_flight"] = round(value_single, 1)
+            line["value_distinct_roots"] = None if value_distinct is None else round(value_distinct, 1)
         if exchange_leg is not None:
             line["value_exchange"] = exchange_leg["value"]
             line["exchange"] = exchange_leg
@@ -781,7 +834,9 @@ def main():
         if dropin is not None:
             line["value_dropin"] = dropin.get("value_dropin")
             line["dropin"] = dropin
-        line.update({"roofline": roof, "cpu_baseline": cpu, "cpu_c1": cpu_c1, "gen_s": round(gen_s, 2)})
+        if a.full:
+            line.update({"roofline": roof, "cpu_baseline": cpu, "cpu_c1": cpu_c1})
+        line["gen_s"] = round(gen_s, 2)
         print(json.dumps(line), flush=True)
     if world > 1:
         dist.destroy_process_group()

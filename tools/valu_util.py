@@ -7,8 +7,8 @@ Input: the counter_collection CSV of
         SQ_WAVES SQ_INSTS_SALU SQ_INSTS_VALU_INT64 SQ_INSTS_VALU_INT32 GRBM_GUI_ACTIVE -- python3 bench.py ...
 bench.py brackets the headline's timed region with one k_partials_check dispatch each side
 (LB_PROF_MARK=1); only the dispatches between the two markers count, so "per batch" means one
-batch of the F-in-flight headline (K x F batches), without the workload generator (k_sign), the
-table fill or the one-batch-in-flight profiled steps before the region.
+batch of the F-in-flight headline (--steps K = K batches in all), without the workload generator
+(k_sign), the table fill or, under --full, the one-batch-in-flight profiled steps before the region.
 
 Per kernel:
   valu_G_per_batch   SQ_INSTS_VALU (wave-instructions) / batches
@@ -23,10 +23,10 @@ Chip:
                      SIMD-32, MI355X_MICROARCH.md "v_fma_f32 (wave64) 2 cyc") / (1 024 SIMDs x
                      clock x the un-profiled region time), with clock 2.4 GHz (the loaded shader
                      clock read by the wave microbench) unless --clock-ghz; the
-                     un-profiled time comes from a bench line (--line, ms_per_step x K x F)
+                     un-profiled time comes from a bench line (--line, ms_per_step x K)
 Counter passes serialise dispatches, so no time-based figure here is taken from the profiled run.
 
-  python3 tools/valu_util.py COUNTERS.csv --batches K*F [--line bench_line.json] [--out json]
+  python3 tools/valu_util.py COUNTERS.csv --batches K [--line bench_line.json] [--out json]
 """
 import argparse
 import collections
@@ -51,7 +51,7 @@ def load(path):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("csv")
-    ap.add_argument("--batches", type=int, required=True, help="batches in the timed region (steps x inflight)")
+    ap.add_argument("--batches", type=int, required=True, help="batches in the timed region (bench.py --steps)")
     ap.add_argument("--line", help="an un-profiled bench.py JSON line of the same configuration")
     ap.add_argument("--clock-ghz", type=float, default=2.4)
     ap.add_argument("--out")
