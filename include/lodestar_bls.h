@@ -247,6 +247,16 @@ int32_t lb_sign(lb_engine* e, uint32_t n, const uint8_t* sks32, const uint8_t* m
 int32_t lb_pubkey_table_append(lb_engine* e, uint32_t n, const uint8_t* keys, uint32_t key_size, int32_t validate,
                                int32_t* out_status, uint32_t* out_first_index);
 uint32_t lb_pubkey_table_size(const lb_engine* e);
+/*
+ * Keys of the table (its first lb_pubkey_comb_size) that also carry fixed-base window entries: 72
+ * affine points, 6.75 KiB per key and engine, filled inside lb_pubkey_table_append.  A set over
+ * exactly one such key takes r * PK from them without doublings; every other set takes the GLV
+ * ladder.  Environment, read at engine creation: LB_PK_COMB_MB = the entries' budget per engine in
+ * MiB (default 8192, a 2^20-key table in full; keys past it use the ladder), LB_PK_COMB=0 = none.
+ */
+uint32_t lb_pubkey_comb_size(const lb_engine* e);
+/* Sets whose r * PK the engine has taken from those entries so far, over all its batches. */
+uint64_t lb_pubkey_comb_sets(const lb_engine* e);
 
 /*
  * Like lb_batch_create, but set i aggregates table entries pk_indices[set_pk_offsets[i] ..

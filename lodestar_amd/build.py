@@ -114,6 +114,23 @@ def build_harness(force=False, verbose=True):
     return HARNESS
 
 
+COMB_HARNESS = os.path.join(ROOT, "build", "lb_comb_harness.so")
+
+
+def build_comb_harness(force=False, verbose=True):
+    """the fixed-base comb of the resident pubkey table on the CPU (tests/test_pk_comb_cpu.py)"""
+    src = os.path.join(ROOT, "tests", "harness", "lb_comb_harness.cpp")
+    os.makedirs(os.path.dirname(COMB_HARNESS), exist_ok=True)
+    if not force and not _stale(COMB_HARNESS, _deps() + [src]):
+        return COMB_HARNESS
+    cmd = ["g++", "-O2", "-shared", "-fPIC", "-I" + INC, "-I" + CSRC, src, "-o", COMB_HARNESS + ".tmp"]
+    if verbose:
+        print("[build]", " ".join(cmd), flush=True)
+    subprocess.run(cmd, check=True)
+    os.replace(COMB_HARNESS + ".tmp", COMB_HARNESS)
+    return COMB_HARNESS
+
+
 def build_cpu_pool(force=False, verbose=True):
     src = os.path.join(ROOT, "oracle", "cpu_pool.cpp")
     if not os.path.exists(src):
@@ -172,6 +189,7 @@ def build_all(force=False):
     build_lib(force)
     build_napi(force)
     build_harness(force)
+    build_comb_harness(force)
     build_cpu_pool(force)
     build_ubench(force)
 

@@ -228,6 +228,62 @@ LB_NI jac<F> jac_mul_glv(aff<F> t1, aff<F> t2, aff<F> t3, uint64_t w) {
   return jac_mul_glv_i(t1, t2, t3, w);
 }
 
+// Fixed-base comb for a key that stays resident (the pubkey table): the same [r]P, r = lo + hi
+// lambda, without doublings.  Each 32-bit half is recoded into LB_COMB_J signed radix-16 digits,
+//   h = sum_j d_j 16^j,  d_j = nibble_j(h + 0x88888888) - 8 in [-8, 7] (j < 8),  d_8 = the carry,
+// and the key's table holds the affine points E[j][d] = [d 16^j]P, d = 1..8 (entry 8 j + d - 1),
+// so  [r]P = sum_j sgn(lo_j) E[j][|lo_j|] + sum_j sgn(hi_j) phi(E[j][|hi_j|]),  phi(x, y) = (beta x, y):
+// 18 mixed additions and 9 products by beta.  An entry at infinity (a registered point of small
+// order, possible only for unvalidated keys) is stored as (0, 0) -- no curve point has y = 0,
+// the group order being odd -- and skipped like a zero digit.
+#define LB_COMB_J 9
+#define LB_COMB_D 8
+#define LB_COMB_ENTRIES (LB_COMB_J * LB_COMB_D)
+// digit k of the word: k < 9 digit k of lo, else digit k - 9 of hi
+LB_HD int comb_digit(uint64_t w, int k) {
+  const uint64_t h = (k < LB_COMB_J ? (w & 0xffffffffu) : (w >> 32)) + 0x88888888ull;
+  const int j = k < LB_COMB_J ? k : k - LB_COMB_J;
+  return j < 8 ? (int)((h >> (4 * j)) & 15u) - 8 : (int)(h >> 32);
+}
+// the table entry digit k reads (a zero digit reads its position's first entry and discards it)
+LB_HD uint32_t comb_entry(uint64_t w, int k) {
+  const int d = comb_digit(w, k), a = d < 0 ? -d : d;
+  return (uint32_t)(LB_COMB_D * (k < LB_COMB_J ? k : k - LB_COMB_J) + (a ? a - 1 : 0));
+}
+// E[j][d] = [d 16^j]P (Jacobian), d in [1, 8]
+template <class F>
+LB_HD jac<F> jac_comb_entry_i(const aff<F>& p, int j, int d) {
+  jac<F> acc = jac_infinity<F>();
+  for (int b = 3; b >= 0; b--) {
+    acc = jac_dbl_i(acc);
+    jac<F> s = jac_add_aff_i<F, true>(acc, p);
+    if ((d >> b) & 1) acc = s;
+  }
+  for (int k = 0; k < 4 * j; k++) acc = jac_dbl_i(acc);
+  return acc;
+}
+// ld(e): entry e of the key's table.  The loads of step k + 1 are issued before the addition of
+// step k.  The loop stays rolled: one inline addition in the kernel.
+template <class F, class Ld>
+LB_HD jac<F> jac_mul_comb_i(Ld&& ld, const F& beta, uint64_t w) {
+  jac<F> acc = jac_infinity<F>();
+  aff<F> nx = ld(comb_entry(w, 0));
+#if defined(__clang__)
+#pragma clang loop unroll(disable)
+#endif
+  for (int k = 0; k < 2 * LB_COMB_J; k++) {
+    aff<F> t = nx;
+    if (k + 1 < 2 * LB_COMB_J) nx = ld(comb_entry(w, k + 1));
+    const int d = comb_digit(w, k);
+    const bool skip = d == 0 || f_is_zero(t.y);
+    if (k >= LB_COMB_J) t.x = f_mul(t.x, beta);
+    t.y = f_select(d < 0, f_neg(t.y), t.y);
+    jac<F> s = jac_add_aff_i<F, true>(acc, t);
+    if (!skip) acc = s;
+  }
+  return acc;
+}
+
 // [k]P for a 64-bit scalar, P Jacobian (used after aggregation, before the one inversion)
 template <class F>
 LB_NI jac<F> jac_mul_u64_jac(jac<F> p, uint64_t k) {

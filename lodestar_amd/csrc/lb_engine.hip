@@ -102,7 +102,14 @@ struct lb_batch {
   std::vector<uint32_t> h_set_chunk_off, h_chunk_lo;  // host staging of the chunk decomposition
   uint32_t n_chunks = 0;           // pubkey aggregation chunks (k_pk_chunks)
   bool indexed = false;            // pubkeys are indices into the engine's resident table
-  dbuf d_job_off, d_pk_off, d_pks, d_msgs, d_sigs, d_sig_sizes, d_set_chunk_off, d_chunk_lo;
+  // r PK routing of an indexed batch (batch_fill): d_route = the set ids of the single-key sets
+  // whose key had comb entries at upload, [0, n_comb), then every other set (the ladder's),
+  // [n_comb, n_sets).  Valid on route_eng only (the comb table is per engine; its coverage never
+  // shrinks, so keys covered at upload stay covered).
+  std::vector<uint32_t> h_route;
+  uint32_t n_comb = 0;
+  const void* route_eng = nullptr;
+  dbuf d_job_off, d_pk_off, d_pks, d_msgs, d_sigs, d_sig_sizes, d_set_chunk_off, d_chunk_lo, d_route;
   dbuf d_arena;  // small uploads: the arrays above as views into one buffer, filled by one copy
   bool has_sizes = false;
   int device = 0;
@@ -116,6 +123,7 @@ struct lb_batch {
     d_sig_sizes.release();
     d_set_chunk_off.release();
     d_chunk_lo.release();
+    d_route.release();
   }
 };
 
@@ -248,6 +256,14 @@ struct lb_engine {
   // resident pubkey table: one 128-byte record per key (g1a + flag, LB_TABLE_REC words)
   dbuf table;
   uint32_t table_n = 0, table_cap = 0;
+  // fixed-base comb entries of the table's first comb_n keys (k_comb_fill: LB_COMB_ENTRIES points
+  // of 96 B per key, 6.75 KiB), so that r PK of a single-key set is 18 mixed additions
+  // (k_pk_blind_comb) instead of the GLV ladder.  comb_max = keys the engine's budget allows:
+  // LB_PK_COMB_MB (MiB per engine, default 8192: a 2^20-key table in full), LB_PK_COMB=0 turns
+  // the comb off (every set takes the ladder, the A/B).  Keys past the budget take the ladder.
+  dbuf comb;
+  uint32_t comb_n = 0, comb_cap = 0, comb_max = 0;
+  uint64_t comb_sets = 0;  // sets k_pk_blind_comb was launched over, all batches (lb_pubkey_comb_sets)
   // KZG trusted setup (lb_kzg_load_setup): [tau^i] G1 as g1a SoA (kzg_n entries), [tau^0,1] G2
   dbuf kzg_g1, kzg_g2;
   uint32_t kzg_n = 0;
@@ -484,6 +500,13 @@ int32_t lb_engine_create_ex(int32_t device, uint32_t flags, lb_engine** out) {
   if (const char* sm = getenv("LB_MSM_G8")) e->msm_g8 = std::atoi(sm) != 0;
   if (const char* sm = getenv("LB_SPEC_GSUM")) e->spec_gsum = std::atoi(sm) != 0;
   if (const char* al = getenv("LB_ALONE")) e->alone_force = std::atoi(al) != 0 ? 1 : 0;
+  {
+    const char* on = getenv("LB_PK_COMB");
+    const char* mb = getenv("LB_PK_COMB_MB");
+    const double mib = mb ? std::max(0.0, strtod(mb, nullptr)) : 8192.0;  // fractions allowed (tests)
+    const uint64_t keys = (uint64_t)(mib * 1048576.0 / (double)(LB_COMB_ENTRIES * sizeof(g1a)));
+    e->comb_max = (on && std::atoi(on) == 0) ? 0u : (uint32_t)std::min<uint64_t>(keys, 0x7fffffffu);
+  }
   // CU partition: a latency engine's streams on the reserved CUs [0, R), every engine created
   // while a partition exists on [R, ncu)
   bool masked = false;
@@ -605,7 +628,7 @@ void lb_engine_destroy(lb_engine* e) {
   hipStreamSynchronize(e->stream);
   dbuf* bufs[] = {&e->scalars, &e->sig_aff, &e->sig_inf, &e->sig_status, &e->q, &e->h_aff, &e->rpk, &e->rsig,
                   &e->pk_status, &e->ml, &e->treeP, &e->treeS, &e->job_status, &e->nodes, &e->verdict, &e->parts,
-                  &e->ok, &e->chunk_acc, &e->chunk_status, &e->fS, &e->table, &e->msg_tab,
+                  &e->ok, &e->chunk_acc, &e->chunk_status, &e->fS, &e->table, &e->comb, &e->msg_tab,
                   &e->rep_of, &e->uid_of, &e->uniq_set, &e->n_u, &e->set_uid, &e->gcnt, &e->gpos, &e->goff,
                   &e->gch, &e->chunk_beg, &e->chunk_end, &e->members, &e->set_live, &e->gacc, &e->gp_aff,
                   &e->gp_inf, &e->chunk_root, &e->sig_aos, &e->bcnt, &e->bcursor, &e->boff, &e->bch, &e->bchunk_beg,
@@ -718,6 +741,23 @@ static int32_t batch_fill(lb_engine* e, lb_batch* b, uint32_t n_jobs, const uint
   chunk_lo.push_back(n_pks | LB_CHUNK_FIRST);  // chunk c ends where chunk c+1 starts (chunks never
   // span sets: a set's last chunk ends at the next set's first key, which is its own first chunk start)
   b->indexed = indexed;
+  // r PK routing (run_pipeline): single-key sets over a key with comb entries first, the rest after
+  std::vector<uint32_t>& route = b->h_route;
+  route.clear();
+  b->n_comb = 0;
+  b->route_eng = nullptr;
+  if (indexed && e->comb_n) {
+    route.resize(n_sets);
+    uint32_t lo = 0, hi = n_sets;
+    for (uint32_t i = n_sets; i-- > 0;)  // the ladder sets from the back, in ascending order
+      if (!(set_pk_offsets[i + 1] - set_pk_offsets[i] == 1 && pk_indices[set_pk_offsets[i]] < e->comb_n))
+        route[--hi] = i;
+    for (uint32_t i = 0; i < n_sets; i++)
+      if (set_pk_offsets[i + 1] - set_pk_offsets[i] == 1 && pk_indices[set_pk_offsets[i]] < e->comb_n)
+        route[lo++] = i;
+    b->n_comb = lo;
+    b->route_eng = e;
+  }
   struct part {
     dbuf* d;
     const void* src;
@@ -731,9 +771,10 @@ static int32_t batch_fill(lb_engine* e, lb_batch* b, uint32_t n_jobs, const uint
                          (size_t)n_pks * (indexed ? 4 : 96)},
                         {&b->d_msgs, signing_roots, (size_t)n_sets * 32},
                         {&b->d_sigs, signatures, (size_t)n_sets * 96},
-                        {&b->d_sig_sizes, sig_sizes, sig_sizes ? (size_t)n_sets * 4 : 0}};
+                        {&b->d_sig_sizes, sig_sizes, sig_sizes ? (size_t)n_sets * 4 : 0},
+                        {&b->d_route, route.data(), route.size() * 4}};
   // a small batch (a 1-set call, a block) goes up as ONE copy from pinned staging into an arena
-  // the arrays are views of: eight pageable copies were ~0.1 ms of a 1-set call's 3.7
+  // the arrays are views of: one pageable copy per array were ~0.1 ms of a 1-set call's 3.7
   size_t total = 0;
   for (const part& q : parts) total += ((q.bytes > 16 ? q.bytes : 16) + 255) & ~(size_t)255;
   bool staged = total <= kStageMax;
@@ -769,7 +810,7 @@ static int32_t batch_fill(lb_engine* e, lb_batch* b, uint32_t n_jobs, const uint
     // later verify of it reads nothing (round-5 ADVICE)
     for (const part& q : parts) q.d->release();
     b->d_arena.release();
-    b->n_jobs = b->n_sets = b->n_pks = b->n_chunks = 0;
+    b->n_jobs = b->n_sets = b->n_pks = b->n_chunks = b->n_comb = 0;
     b->job_off.assign(1, 0u);
     fprintf(stderr, "lodestar_bls: batch upload failed: %s\n", hipGetErrorString(r));
     return LB_ERR_DEVICE;
@@ -835,6 +876,8 @@ void lb_host_free(void* p) {
 }
 
 uint32_t lb_pubkey_table_size(const lb_engine* e) { return e ? e->table_n : 0; }
+uint32_t lb_pubkey_comb_size(const lb_engine* e) { return e ? e->comb_n : 0; }
+uint64_t lb_pubkey_comb_sets(const lb_engine* e) { return e ? e->comb_sets : 0; }
 
 int32_t lb_pubkey_table_append(lb_engine* e, uint32_t n, const uint8_t* keys, uint32_t key_size, int32_t validate,
                                int32_t* out_status, uint32_t* out_first_index) {
@@ -858,6 +901,31 @@ int32_t lb_pubkey_table_append(lb_engine* e, uint32_t n, const uint8_t* keys, ui
     e->table = nt;
     e->table_cap = cap;
   }
+  // the comb entries grow with the records, up to the budget's key count
+  uint32_t comb_need = std::min(need, e->comb_max);
+  if (comb_need > e->comb_cap) {
+    const uint32_t cap = std::min(e->table_cap, e->comb_max);
+    const size_t rec = (size_t)LB_COMB_ENTRIES * sizeof(g1a);
+    dbuf nc;
+    hipError_t rc = nc.ensure((size_t)cap * rec);
+    if (rc == hipSuccess && e->comb_n)
+      rc = hipMemcpyAsync(nc.p, e->comb.p, (size_t)e->comb_n * rec, hipMemcpyDeviceToDevice, e->stream);
+    if (rc == hipSuccess) rc = hipStreamSynchronize(e->stream);
+    if (rc == hipSuccess) {
+      e->comb.release();
+      e->comb = nc;
+      e->comb_cap = cap;
+    } else {
+      // no memory for more entries: the registration still succeeds, the coverage stays where it
+      // is (the keys registered from here on take the ladder)
+      nc.release();
+      (void)hipGetLastError();
+      fprintf(stderr, "lodestar_bls: no memory for %u keys' window tables (%s): coverage stays at %u keys\n", cap,
+              hipGetErrorString(rc), e->comb_n);
+      e->comb_max = e->comb_n;
+      comb_need = e->comb_n;
+    }
+  }
   dbuf kin, st;
   hipError_t r = kin.ensure((size_t)n * key_size);
   if (r == hipSuccess) r = st.ensure((size_t)n * 4);
@@ -865,6 +933,12 @@ int32_t lb_pubkey_table_append(lb_engine* e, uint32_t n, const uint8_t* keys, ui
   if (r == hipSuccess) {
     hipLaunchKernelGGL(k_table_fill, dim3(nblk(n)), dim3(LB_TPB), 0, e->stream, n, kin.as<uint8_t>(), key_size,
                        validate, first, e->table.as<uint32_t>(), st.as<int32_t>());
+    r = hipGetLastError();
+  }
+  if (r == hipSuccess && comb_need > first) {  // keys [first, comb_need): inside the budget
+    const uint32_t nk = comb_need - first;
+    hipLaunchKernelGGL(k_comb_fill, dim3((nk + 7) / 8, LB_COMB_J), dim3(LB_INV_TPB), 0, e->stream, nk, first,
+                       e->table.as<uint32_t>(), e->comb.as<uint32_t>());
     r = hipGetLastError();
   }
   if (r == hipSuccess) r = hipMemcpyAsync(out_status, st.p, (size_t)n * 4, hipMemcpyDeviceToHost, e->stream);
@@ -876,6 +950,7 @@ int32_t lb_pubkey_table_append(lb_engine* e, uint32_t n, const uint8_t* keys, ui
     return LB_ERR_DEVICE;
   }
   e->table_n = need;
+  e->comb_n = std::max(e->comb_n, comb_need);
   return LB_OK;
 }
 
@@ -1134,7 +1209,29 @@ static int32_t run_pipeline(lb_engine* e, lb_batch* b, const uint64_t* scalars, 
       const uint32_t m0 = (pk_split || e->straus_run) ? 1u : 0u;
       const uint32_t m1 = e->straus_run ? 1u : (pk_split ? 2u : 0u);
       if (e->straus_run) LB_HIP(e->pk3.ensure((size_t)ns * sizeof(g1x3)));
-      for (uint32_t mode = m0; mode <= m1; mode++) {
+      // an indexed batch routed at upload on this engine: the statuses over every set (mode 1),
+      // then the comb over its single-key sets and the ladder over the compacted rest
+      const bool route = b->indexed && b->n_comb && b->route_eng == e && !e->straus_run && !pk_rowp;
+      if (route) {
+        const uint32_t n_lad = n - b->n_comb;
+        const uint32_t* sel = b->d_route.as<uint32_t>();
+        hipLaunchKernelGGL(k_pk_blind, dim3(nblk_inv(n)), dim3(LB_INV_TPB), 0, s3, n, nc, b->d_set_chunk_off.as<uint32_t>(),
+                           e->chunk_acc.as<uint32_t>(), e->chunk_status.as<int32_t>(), e->pk_aff.as<uint32_t>(),
+                           e->scalars.as<uint64_t>(), e->rpk.as<uint32_t>(), e->pk_status.as<int32_t>(), 1u, nullptr,
+                           nullptr, 0u);
+        LB_HIP(hipEventRecord(e->ev_pkst, s3));
+        hipLaunchKernelGGL(k_pk_blind_comb, dim3(nblk(b->n_comb)), dim3(LB_TPB), 0, s3, n, b->n_comb, sel,
+                           b->d_pk_off.as<uint32_t>(), b->d_pks.as<uint32_t>(), e->comb.as<uint32_t>(), e->comb_n,
+                           e->pk_aff.as<uint32_t>(), e->scalars.as<uint64_t>(), e->pk_status.as<int32_t>(),
+                           e->rpk.as<uint32_t>());
+        e->comb_sets += b->n_comb;
+        if (n_lad)
+          hipLaunchKernelGGL(k_pk_blind, dim3(nblk_inv(n_lad)), dim3(LB_INV_TPB), 0, s3, n, nc,
+                             b->d_set_chunk_off.as<uint32_t>(), e->chunk_acc.as<uint32_t>(), e->chunk_status.as<int32_t>(),
+                             e->pk_aff.as<uint32_t>(), e->scalars.as<uint64_t>(), e->rpk.as<uint32_t>(),
+                             e->pk_status.as<int32_t>(), 2u, nullptr, sel + b->n_comb, n_lad);
+      }
+      for (uint32_t mode = m0; !route && mode <= m1; mode++) {
         if (mode == 2u && pk_rowp) {
           hipLaunchKernelGGL(k_pk_blind_rowp, dim3(n), dim3(64), 0, s3, n, e->pk_aff.as<uint32_t>(),
                              e->scalars.as<uint64_t>(), e->rpk.as<uint32_t>(), e->pk_status.as<int32_t>());
@@ -1143,7 +1240,7 @@ static int32_t run_pipeline(lb_engine* e, lb_batch* b, const uint64_t* scalars, 
         hipLaunchKernelGGL(k_pk_blind, dim3(nblk_inv(n)), dim3(LB_INV_TPB), 0, s3, n, nc, b->d_set_chunk_off.as<uint32_t>(),
                            e->chunk_acc.as<uint32_t>(), e->chunk_status.as<int32_t>(), e->pk_aff.as<uint32_t>(),
                            e->scalars.as<uint64_t>(), e->rpk.as<uint32_t>(), e->pk_status.as<int32_t>(), mode,
-                           (mode == 1u && e->straus_run) ? e->pk3.as<uint32_t>() : nullptr);
+                           (mode == 1u && e->straus_run) ? e->pk3.as<uint32_t>() : nullptr, nullptr, 0u);
         if (mode == 1u) LB_HIP(hipEventRecord(e->ev_pkst, s3));
       }
     }
@@ -1796,7 +1893,7 @@ static int32_t search_invalid(lb_engine* e, lb_batch* b, uint32_t mu, int32_t* o
     hipLaunchKernelGGL(k_pk_blind, dim3(nblk_inv(n)), dim3(LB_INV_TPB), 0, e->stream, n, b->n_chunks,
                        b->d_set_chunk_off.as<uint32_t>(), e->chunk_acc.as<uint32_t>(), e->chunk_status.as<int32_t>(),
                        e->pk_aff.as<uint32_t>(), e->scalars.as<uint64_t>(), e->rpk.as<uint32_t>(),
-                       e->pk_status.as<int32_t>(), 2u, nullptr);
+                       e->pk_status.as<int32_t>(), 2u, nullptr, nullptr, 0u);
     LB_HIP(hipGetLastError());
     e->rpk_stale = false;
   }

@@ -1080,12 +1080,16 @@ __global__ void __launch_bounds__(LB_INV_TPB, LB_MINW_G1) k_pk_blind(uint32_t n,
                                                          const uint64_t* __restrict__ scalars,
                                                          uint32_t* __restrict__ rpk,
                                                          int32_t* __restrict__ pk_status, uint32_t mode,
-                                                         uint32_t* __restrict__ pk3) {
+                                                         uint32_t* __restrict__ pk3,
+                                                         const uint32_t* __restrict__ sel, uint32_t n_sel) {
   // mode 0: all; 1: the aggregate, its status and affine form only (pk_status, pk_aff: what the
   // job statuses need, ahead of the ladder); 2: the ladder only, from mode 1's pk_status / pk_aff.
   // pk3 (mode 1, optional): (x, y, beta x) per set, AoS, for the per-root Straus sums
   // (k_gsum_straus), which then replace the ladder
-  const uint32_t i = blockIdx.x * LB_INV_TPB + threadIdx.x;
+  // sel (mode 2, optional): the ladder runs over the n_sel compacted set ids sel[] only (the
+  // sets k_pk_blind_comb does not take), so no wave runs it for a few lanes among comb sets
+  uint32_t i = blockIdx.x * LB_INV_TPB + threadIdx.x;
+  if (mode == 2 && sel != nullptr) i = i < n_sel ? sel[i] : n;  // uniform condition
   const bool act = i < n;
   int st = LB_ERR_ARGUMENT;
   g1j rj = jac_infinity<fp>();
@@ -1160,6 +1164,72 @@ __global__ void __launch_bounds__(LB_INV_TPB, LB_MINW_G1) k_pk_blind(uint32_t n,
   aos_st(rpk, i, rj);  // AoS: the per-root sums and the search gather it by member
   if (ok) soa_st(pk_aff, n, i, pk);  // the unblinded aggregate, for single-set checks of the search
   pk_status[i] = st;
+}
+#endif  // LB_KG
+
+// The resident table's fixed-base comb (lb_curve.h jac_mul_comb_i): per key LB_COMB_ENTRIES affine
+// points E[j][d] = [d 16^j]P of 96 B (Montgomery form, AoS, entry 8 j + d - 1 of key t at record
+// 72 t + 8 j + d - 1 of `comb`), filled once when the key is registered -- a validator's key never
+// changes -- so that r PK of a single-key set is 18 mixed additions instead of the ladder's 32
+// doublings + 32 additions.
+// k_comb_fill: one lane per entry, a block = 8 keys x 8 digits of one position j (blockIdx.y, so
+// the 4 j doublings are uniform), one inversion per block for the affine forms.  Keys whose record
+// is flagged (bad encoding, infinity) get zero entries; no set reaches the comb with them (their
+// pk_status is not LB_OK).
+#if LB_KG(15)
+__global__ void __launch_bounds__(LB_INV_TPB, LB_MINW_G1) k_comb_fill(uint32_t n, uint32_t first,
+                                                          const uint32_t* __restrict__ table,
+                                                          uint32_t* __restrict__ comb) {
+  const uint32_t k = blockIdx.x * 8 + (threadIdx.x >> 3);
+  const int d = (int)(threadIdx.x & 7u) + 1, j = (int)blockIdx.y;
+  const bool in = k < n;
+  const uint32_t t = first + (in ? k : 0u);
+  const bool act = in && table_flag_ld(table, t) == 0u;
+  jac<lb_g1f> acc = jac_infinity<lb_g1f>();
+  if (act) acc = jac_comb_entry_i<lb_g1f>(aff_as<lb_g1f>(table_ld(table, t)), j, d);
+  const bool inf = jac_is_inf(acc);
+  const fp zi = fp_inv_block<true>(inf ? fp_one() : fp{acc.z});  // every thread of the block
+  g1a a{fp_zero(), fp_zero()};
+  if (!inf) {
+    const fp zi2 = fp_sqr(zi);
+    a.x = fp_mul(acc.x, zi2);
+    a.y = fp_mul(fp_mul(acc.y, zi2), zi);
+  }
+  if (in) aos_st(comb + ((size_t)t * LB_COMB_ENTRIES + (size_t)(LB_COMB_D * j + d - 1)) * 24, 0, a);
+}
+#endif  // LB_KG
+
+// r PK for the sets sel[0 .. n_sel): single-key sets whose key (idx[pk_off[i]]) has comb entries
+// (key < comb_n; the host routes by that, lb_engine.hip batch_fill).  pk_status comes from
+// k_pk_blind mode 1, which runs over every set; rpk is the same AoS record k_pk_blind writes.
+#if LB_KG(15)
+__global__ void __launch_bounds__(LB_TPB, LB_MINW_G1) k_pk_blind_comb(uint32_t n, uint32_t n_sel,
+                                                             const uint32_t* __restrict__ sel,
+                                                             const uint32_t* __restrict__ pk_off,
+                                                             const uint32_t* __restrict__ idx,
+                                                             const uint32_t* __restrict__ comb, uint32_t comb_n,
+                                                             const uint32_t* __restrict__ pk_aff,
+                                                             const uint64_t* __restrict__ scalars,
+                                                             const int32_t* __restrict__ pk_status,
+                                                             uint32_t* __restrict__ rpk) {
+  const uint32_t s = lb_tid();
+  if (s >= n_sel) return;
+  const uint32_t i = sel[s];
+  if (i >= n) return;
+  g1j rj = jac_infinity<fp>();
+  if (pk_status[i] == LB_OK) {
+    const uint64_t w = scalars[i];
+    const uint32_t key = idx[pk_off[i]];
+    if (w == 1) {  // the unblinded 1-set call: r PK = PK, kept affine (Z = 1)
+      const g1a pk = soa_ld<g1a>(pk_aff, n, i);
+      rj = g1j{pk.x, pk.y, fp_one()};
+    } else if (key < comb_n) {  // (always: the routing's condition)
+      const uint32_t* base = comb + (size_t)key * LB_COMB_ENTRIES * 24;
+      rj = jac_as<fp>(jac_mul_comb_i<lb_g1f>([&](uint32_t e) { return aff_as<lb_g1f>(aos_ld<g1a>(base, e)); },
+                                             lb_g1f{fp_load(LB_GLV_BETA)}, w));
+    }
+  }
+  aos_st(rpk, i, rj);
 }
 #endif  // LB_KG
 

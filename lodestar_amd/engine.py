@@ -266,6 +266,14 @@ class Engine:
     def pubkey_table_size(self) -> int:
         return int(self.lib.lb_pubkey_table_size(self.h))
 
+    def pubkey_comb_size(self) -> int:
+        """Keys of the table (its first so many) with fixed-base window entries (lb_pubkey_comb_size)."""
+        return int(self.lib.lb_pubkey_comb_size(self.h))
+
+    def pubkey_comb_sets(self) -> int:
+        """Sets whose r PK came from those entries so far (lb_pubkey_comb_sets)."""
+        return int(self.lib.lb_pubkey_comb_sets(self.h))
+
     def aggregate_pubkeys(self, sets_pubkeys: Sequence[Sequence[bytes]]) -> Tuple[List[bytes], List[int]]:
         off = [0]
         flat = []

@@ -56,6 +56,19 @@ def main():
     g1b = avg([L.cnt_g1_blind(pks[0], rnd.getrandbits(64) | 1) for _ in range(16)])
     g2b = avg([L.cnt_g2_blind(sigs[0], rnd.getrandbits(64) | 1) for _ in range(16)])
     per_key = (L.cnt_pk_key(b"".join(pks[:4]), 4) - L.cnt_pk_key(pks[0], 1)) / 3
+    # r PK of a single-key set over a resident key: the fixed-base comb (k_pk_blind_comb), counted
+    # on the CPU build of the same code (tests/harness/lb_comb_harness.cpp)
+    so_c = os.path.join(ROOT, "build", "lb_comb_count.so")
+    subprocess.run(["g++", "-O2", "-shared", "-fPIC", "-DLB_COUNT_OPS", "-I" + os.path.join(ROOT, "include"),
+                    "-I" + os.path.join(ROOT, "lodestar_amd", "csrc"),
+                    os.path.join(ROOT, "tests", "harness", "lb_comb_harness.cpp"), "-o", so_c], check=True)
+    C = ctypes.CDLL(so_c)
+    C.cnt_g1_comb.restype = ctypes.c_ulonglong
+    C.cnt_g1_comb.argtypes = [ctypes.c_char_p, ctypes.c_uint64]
+    tab = ctypes.create_string_buffer(C.c_comb_entries() * C.c_comb_entry_bytes())
+    pt = o.sk_to_pk(sks[0])
+    C.c_comb_build(pt[0].to_bytes(48, "big") + pt[1].to_bytes(48, "big"), tab)
+    g1c = avg([C.cnt_g1_comb(tab, rnd.getrandbits(64) | 1) for _ in range(64)])
     fe = L.cnt_fe()
     out = {
         "mac_per_fp_mul": 300,
@@ -72,11 +85,15 @@ def main():
             "fp12_mul": fp12m, "g2_add": g2add,       # job_leaves / tree_up building blocks
             "node_check": node,                       # per checked tree node (ML + FE)
             "pk_key": per_key,                        # k_pk_chunks: decode + add per pubkey
-            "g1_blind": g1b,                          # k_pk_blind per set (r*PK + affine)
+            "g1_blind": g1c,                          # k_pk_blind_comb per single-key set (r*PK)
+            "g1_blind_ladder": g1b,                   # k_pk_blind per set (r*PK + affine)
             "g2_blind": g2b,                          # k_sig_blind per set (r*sig)
             "final_exp": fe,                          # k_root_check
             "ml_S": c["miller"] + (node - fe - c["miller"] - fp12m),  # k_ml_S: ML + G2 affine
         },
+        "g1_blind_note": "g1_blind is the fixed-base comb's count (single-key sets over a resident key: 94.7 % of "
+                         "the flagship's sets); an aggregate, a set over a key past the comb's budget or a batch of "
+                         "96-byte keys still costs g1_blind_ladder per set",
         "items_per_set": {"decode_sigs": 1, "hash_map": 2, "hash_finish": 1, "pk_blind": 1, "miller": 1},
     }
     out["fp_mul_per_set_k1_estimate"] = (c["decode_sigs"] + 2 * c["hash_map"] + c["hash_finish"] + blind1

@@ -24,7 +24,7 @@ STAGES = {
     "hash_map": ["k_hash_map", "k_hash_map_row"],
     "hash_finish": ["k_hash_finish", "k_hash_finish_g8", "k_hash_finish_row"],
     "pk_chunks": ["k_pk_chunks", "k_pk_chunks_idx"],
-    "pk_blind": ["k_pk_blind"],
+    "pk_blind": ["k_pk_blind", "k_pk_blind_comb"],
     "sig_msm": ["k_msm_count", "k_msm_scatter", "k_msm_chunks", "k_msm_buckets", "k_msm_reduce", "k_msm_buckets_g8",
                 "k_msm_window_g8", "k_msm_horner_g8", "k_sig_blind", "k_sig_blind_g8", "k_g2_sum64"],
     "group_sum": ["k_chunk_fill", "k_gsum_chunks", "k_gsum_straus", "k_gsum_wave", "k_gsum_tree", "k_gsum_final"],
