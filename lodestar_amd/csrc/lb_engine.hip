@@ -139,12 +139,6 @@ struct lb_engine {
   hipStream_t stream = nullptr;   // s1
   hipStream_t stream2 = nullptr;  // s2
   hipStream_t stream3 = nullptr;  // s3: pubkey aggregation + blinding, beside the signature decode
-  // LB_PRIO_MAX=k: batches of at most k sets run on a second stream trio created at the device's
-  // greatest priority (created on first use).  Off by default: measured through the JS drop-in,
-  // verifyOnMainThread under a gossip load took 396-758 ms with it against 9.0-9.2 ms without,
-  // and the pool's throughput fell 3-5x (profiles/r5_prio_streams_ab.txt)
-  hipStream_t hp[3] = {nullptr, nullptr, nullptr};
-  uint32_t prio_max = 0;
   hipEvent_t ev_g1 = nullptr, ev_s = nullptr, ev_fork = nullptr, ev_dec = nullptr, ev_pk = nullptr;
   hipEvent_t ev_pkst = nullptr;  // the pubkey statuses (k_pk_blind mode 1), before the ladder
   // small batches alone (round 6): the decoded signatures (s2) -> r_i sig_i on s3 beside the
@@ -157,20 +151,10 @@ struct lb_engine {
   // message grouping (k_msg_*, k_gsum_*)
   dbuf msg_tab, rep_of, uid_of, uniq_set, n_u, set_uid, gcnt, gpos, goff, gch, chunk_beg, chunk_end, members,
       set_live, gacc, gp_aff, gp_inf, chunk_root;
-  uint32_t gmax_chunks = 0;  // chunks of the largest root (the k_gsum_tree levels), read back with n_u
-  // under load (not alone) the per-root sums fold the blinding in, one Straus chain per chunk
-  // (k_gsum_straus over pk3) instead of k_pk_blind's per-set ladder + the chunk sums; the per-set
-  // r PK (rpk) are then computed only if a search needs them (rpk_stale).  LB_GSUM_STRAUS=1: on.
-  // Off by default: measured 4 % below the per-set ladders at 7 in flight even with the chunks in
-  // size order (10.53-10.59 M against 11.01-11.03 M sets/s, profiles/r6_straus_ab.txt)
-  bool straus = false, straus_run = false, rpk_stale = false;
-  // a batch alone: the per-root sums' chunks combined by a segmented shuffle tree in one launch
-  // (k_gsum_wave, chunks of LB_GROUP_CHUNK_WAVE) instead of the k_gsum_tree launches; LB_GSUM_WAVE=0
-  bool gsum_wave = true;
-  dbuf pk3, corder;  // (x, y, beta x) per set; the Straus lanes' chunk order (+ size counts)
-  bool gsum_tree = true;     // LB_GSUM_TREE=0: the chunk sums added serially per root (A/B)
   // this pipeline run's forms: `alone` (device_alone at its start) picks the latency forms -- the
-  // row engine (row_fe: LB_ROW_FE=0 disables it) and the per-root sum tree over 8-member chunks
+  // row engine (row_fe: LB_ROW_FE=0 disables it) and the per-root sums' chunks combined by a
+  // segmented shuffle tree in one launch (k_gsum_wave, chunks of LB_GROUP_CHUNK_WAVE); under load
+  // k_gsum_chunks over LB_GROUP_CHUNK members, the chunk sums added serially per root
   bool alone = false, row_fe = true;
   int alone_force = -1;  // LB_ALONE=1 / 0 pins device_alone() (tests: the latency forms must run), -1 by load
   uint32_t gchunk = LB_GROUP_CHUNK;
@@ -178,13 +162,6 @@ struct lb_engine {
   dbuf sig_aos, bcnt, bcursor, boff, bch, bchunk_beg, bchunk_end, bmembers, bacc, bsum, wsum;
   // parked lone-lane state: k_hash_finish's points (4 x 72 words per launched lane), k_miller_lane's T
   dbuf park;
-  // per-root chain on speculative liveness (pubkey statuses only), started after the pubkey side
-  // instead of after the signature decode; redone with the full statuses only when a set's
-  // signature failed to decode (k_live_mismatch).  LB_SPEC_GSUM=1; off by default: measured no
-  // gain, the streams then contend for a chip one batch already fills (profiles/r4_spec_ab.txt)
-  bool spec_gsum = false;
-  dbuf set_spec, live_flag;
-  uint32_t* h_flag = nullptr;
   // serial of the batch upload whose lb_batch_partial left its state (trees, statuses, scalars) in
   // this engine's workspace, for lb_batch_search_after_partial; any other pipeline run clears it
   uint64_t partial_serial = 0;
@@ -213,13 +190,7 @@ struct lb_engine {
   uint32_t hash_g8_max = 2048;
   // ... and with a workgroup per root on the row engine while the device is alone.  LB_HASH_ROW_MAX.
   uint32_t hash_row_max = 256;
-  uint32_t hash_row_careful = 0;  // LB_HASH_ROW_CAREFUL=1: the exceptional-case path always (tests)
-  // round 6: the row forms' G2 chains (cofactor clearing, the subgroup ladder, r_i sig_i) in
-  // projective coordinates with the complete formulas; LB_ROW_PROJ=0: the Jacobian programs
-  bool row_proj = true;
-  // round 6, small batches alone: the r PK ladder on rows and r_i sig_i on s3 beside the
-  // subgroup check; LB_SMALL_PAR=0: both on their round-5 streams and forms (A/B)
-  bool small_par = true;
+  bool hash_row_careful = false;  // LB_HASH_ROW_CAREFUL=1: the exceptional-case path always (tests)
   // ... and the signature decode's square roots on rows up to this many sets.  LB_DEC_ROW_MAX.
   uint32_t dec_row_max = 4096;
   // ... and the signatures' subgroup check with 8 lanes per set (k_sig_subgroup_g8).  LB_SUBGROUP_G8_MAX.
@@ -237,7 +208,6 @@ struct lb_engine {
   // per-root signature sums for the search's root-level instances (LB_SEARCH_ROOTSUM)
   dbuf s_root, rs_idx, s_set;
   bool search_rootsum = true;
-  bool search_pre = false;  // later rounds take [w] of the kept per-set terms (LB_SEARCH_PRE)
   // the small rounds' per-position terms: 0 by load (8 lanes per position while the device runs no
   // other batch, one lane under load), 1 one lane, 2 eight lanes (LB_SMSM_FORM=lane / g8)
   int smsm_form = 0;
@@ -470,26 +440,19 @@ int32_t lb_engine_create_ex(int32_t device, uint32_t flags, lb_engine** out) {
   hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest);
   if (const char* mw = getenv("LB_MILLER_WAVE_MAX")) e->miller_wave_max = (uint32_t)strtoul(mw, nullptr, 10);
   if (const char* rm = getenv("LB_ROW_MAX")) e->row_max = (uint32_t)strtoul(rm, nullptr, 10);
-  if (const char* gt = getenv("LB_GSUM_TREE")) e->gsum_tree = std::atoi(gt) != 0;
-  if (const char* gs = getenv("LB_GSUM_STRAUS")) e->straus = std::atoi(gs) != 0;
-  if (const char* gw = getenv("LB_GSUM_WAVE")) e->gsum_wave = std::atoi(gw) != 0;
   if (const char* rf = getenv("LB_ROW_FE")) e->row_fe = std::atoi(rf) != 0;
-  if (const char* pm = getenv("LB_PRIO_MAX")) e->prio_max = (uint32_t)strtoul(pm, nullptr, 10);
   if (const char* ml = getenv("LB_MILLER_LDS3_MAX")) e->miller_lds3_max = (uint32_t)strtoul(ml, nullptr, 10);
   if (const char* mf = getenv("LB_MILLER_FORM")) e->miller_form = !strcmp(mf, "lane") ? 1 : !strcmp(mf, "g8") ? 2 : 0;
   if (const char* hg = getenv("LB_HASH_G8_MAX")) e->hash_g8_max = (uint32_t)strtoul(hg, nullptr, 10);
   if (const char* hr = getenv("LB_HASH_ROW_MAX")) e->hash_row_max = (uint32_t)strtoul(hr, nullptr, 10);
   if (const char* dr = getenv("LB_DEC_ROW_MAX")) e->dec_row_max = (uint32_t)strtoul(dr, nullptr, 10);
-  if (const char* hc = getenv("LB_HASH_ROW_CAREFUL")) e->hash_row_careful = (uint32_t)strtoul(hc, nullptr, 10);
-  if (const char* rp = getenv("LB_ROW_PROJ")) e->row_proj = std::atoi(rp) != 0;
-  if (const char* sp = getenv("LB_SMALL_PAR")) e->small_par = std::atoi(sp) != 0;
+  if (const char* hc = getenv("LB_HASH_ROW_CAREFUL")) e->hash_row_careful = std::atoi(hc) != 0;
   if (const char* sg = getenv("LB_SUBGROUP_G8_MAX")) e->subgroup_g8_max = (uint32_t)strtoul(sg, nullptr, 10);
   if (const char* ss = getenv("LB_SMALL_S_MAX")) e->small_s_max = (uint32_t)strtoul(ss, nullptr, 10);
   if (const char* sg8 = getenv("LB_SMALL_S_G8_MAX")) e->small_s_g8_max = (uint32_t)strtoul(sg8, nullptr, 10);
   if (const char* sm = getenv("LB_SEARCH_SMALL_MAX")) e->search_small_max = (uint32_t)strtoul(sm, nullptr, 10);
   if (const char* sm = getenv("LB_SEARCH_MERGE")) e->search_merge = std::atoi(sm) != 0;
   if (const char* sm = getenv("LB_SEARCH_ROOTSUM")) e->search_rootsum = std::atoi(sm) != 0;
-  if (const char* sm = getenv("LB_SEARCH_PRE")) e->search_pre = std::atoi(sm) != 0;
   if (const char* sf = getenv("LB_SMSM_FORM")) e->smsm_form = !strcmp(sf, "lane") ? 1 : !strcmp(sf, "g8") ? 2 : 0;
   if (const char* sc = getenv("LB_SEARCH_CHUNK")) {
     const uint32_t v = (uint32_t)strtoul(sc, nullptr, 10);
@@ -498,7 +461,6 @@ int32_t lb_engine_create_ex(int32_t device, uint32_t flags, lb_engine** out) {
   if (const char* sm = getenv("LB_SEARCH_BLOCKS")) e->search_blk = std::atoi(sm) != 0;
   if (const char* sm = getenv("LB_ROOT_SHUFFLE")) e->root_shuffle = std::atoi(sm) != 0;
   if (const char* sm = getenv("LB_MSM_G8")) e->msm_g8 = std::atoi(sm) != 0;
-  if (const char* sm = getenv("LB_SPEC_GSUM")) e->spec_gsum = std::atoi(sm) != 0;
   if (const char* al = getenv("LB_ALONE")) e->alone_force = std::atoi(al) != 0 ? 1 : 0;
   {
     const char* on = getenv("LB_PK_COMB");
@@ -543,13 +505,10 @@ int32_t lb_engine_create_ex(int32_t device, uint32_t flags, lb_engine** out) {
                 : hipStreamCreateWithFlags(st, hipStreamNonBlocking);
   };
   if (mk(&e->stream, true) != hipSuccess || mk(&e->stream2, false) != hipSuccess || mk(&e->stream3, false) != hipSuccess ||
-
-      hipHostMalloc((void**)&e->h_nu, 8, hipHostMallocDefault) != hipSuccess ||
-      hipHostMalloc((void**)&e->h_flag, 4, hipHostMallocDefault) != hipSuccess) {
+      hipHostMalloc((void**)&e->h_nu, 4, hipHostMallocDefault) != hipSuccess) {
     if (e->stream) hipStreamDestroy(e->stream);
     if (e->stream2) hipStreamDestroy(e->stream2);
     if (e->stream3) hipStreamDestroy(e->stream3);
-    if (e->h_nu) hipHostFree(e->h_nu);
     std::lock_guard<std::mutex> lk(g_engine_mu);
     g_engine_count[device]--;
     if (e->latency && --g_latency_live[device] == 0) g_latency_cus[device] = 0;
@@ -589,25 +548,18 @@ int32_t lb_engine_create_ex(int32_t device, uint32_t flags, lb_engine** out) {
         // lane), the 8-lane subgroup check and r_i sig_i of small batches (616 / 868 B); s3 the
         // 96-byte-key chunk sums (584 B).  The rest of s2 / s3's kernels need less per lane and
         // fewer lanes (resource table: DESIGN.md section 5.2).
-        // LB_RESERVE_S23 (A/B): 0 none, 1 the decode + s3 only, 2 (default) all of the above
-        const char* rv = getenv("LB_RESERVE_S23");
-        const int res23 = rv ? atoi(rv) : 2;
-        if (res23 >= 1) {
-          hipLaunchKernelGGL(k_decompress_sigs, dim3(4096), dim3(LB_TPB), 0, e->stream2, 0u, nullptr, nullptr, nullptr,
-                             nullptr, nullptr, nullptr);
-          hipLaunchKernelGGL(k_pk_chunks, dim3(4096), dim3(LB_TPB), 0, e->stream3, 0u, nullptr, nullptr, nullptr, nullptr);
-          // the row r PK ladder (one row per set), at the largest small batch
-          hipLaunchKernelGGL(k_pk_blind_rowp, dim3(std::max<uint32_t>(1u, e->row_max)), dim3(64), 0, e->stream3,
-                             0u, nullptr, nullptr, nullptr, nullptr);
-        }
-        if (res23 >= 2) {
-          // (one wave per 8 sets, at least one wave, at most 16 384: more than the device holds)
-          auto g8_waves = [](uint32_t sets) { return dim3(std::min<uint32_t>(16384u, std::max<uint32_t>(1u, sets / 8 + 1))); };
-          hipLaunchKernelGGL(k_sig_subgroup_g8, g8_waves(e->subgroup_g8_max), dim3(64), 0, e->stream2, 0u, nullptr,
-                             nullptr, nullptr);
-          hipLaunchKernelGGL(k_sig_blind_g8, g8_waves(e->small_s_g8_max), dim3(64), 0, e->stream2, 0u, nullptr, nullptr,
-                             nullptr, nullptr, nullptr);
-        }
+        hipLaunchKernelGGL(k_decompress_sigs, dim3(4096), dim3(LB_TPB), 0, e->stream2, 0u, nullptr, nullptr, nullptr,
+                           nullptr, nullptr, nullptr);
+        hipLaunchKernelGGL(k_pk_chunks, dim3(4096), dim3(LB_TPB), 0, e->stream3, 0u, nullptr, nullptr, nullptr, nullptr);
+        // the row r PK ladder (one row per set), at the largest small batch
+        hipLaunchKernelGGL(k_pk_blind_rowp, dim3(std::max<uint32_t>(1u, e->row_max)), dim3(64), 0, e->stream3,
+                           0u, nullptr, nullptr, nullptr, nullptr);
+        // (one wave per 8 sets, at least one wave, at most 16 384: more than the device holds)
+        auto g8_waves = [](uint32_t sets) { return dim3(std::min<uint32_t>(16384u, std::max<uint32_t>(1u, sets / 8 + 1))); };
+        hipLaunchKernelGGL(k_sig_subgroup_g8, g8_waves(e->subgroup_g8_max), dim3(64), 0, e->stream2, 0u, nullptr,
+                           nullptr, nullptr);
+        hipLaunchKernelGGL(k_sig_blind_g8, g8_waves(e->small_s_g8_max), dim3(64), 0, e->stream2, 0u, nullptr, nullptr,
+                           nullptr, nullptr, nullptr);
         ok = hipGetLastError() == hipSuccess && hipStreamSynchronize(e->stream) == hipSuccess &&
              hipStreamSynchronize(e->stream2) == hipSuccess && hipStreamSynchronize(e->stream3) == hipSuccess;
       }
@@ -632,8 +584,8 @@ void lb_engine_destroy(lb_engine* e) {
                   &e->rep_of, &e->uid_of, &e->uniq_set, &e->n_u, &e->set_uid, &e->gcnt, &e->gpos, &e->goff,
                   &e->gch, &e->chunk_beg, &e->chunk_end, &e->members, &e->set_live, &e->gacc, &e->gp_aff,
                   &e->gp_inf, &e->chunk_root, &e->sig_aos, &e->bcnt, &e->bcursor, &e->boff, &e->bch, &e->bchunk_beg,
-                  &e->bchunk_end, &e->bmembers, &e->bacc, &e->bsum, &e->wsum, &e->park, &e->set_spec, &e->live_flag, &e->pk_aff, &e->y_root, &e->kzg_g1,
-                  &e->kzg_g2, &e->s_terms, &e->s_part, &e->s_root, &e->rs_idx, &e->s_set, &e->pk3, &e->corder};
+                  &e->bchunk_end, &e->bmembers, &e->bacc, &e->bsum, &e->wsum, &e->park, &e->pk_aff, &e->y_root, &e->kzg_g1,
+                  &e->kzg_g2, &e->s_terms, &e->s_part, &e->s_root, &e->rs_idx, &e->s_set};
   for (dbuf* b : bufs) b->release();
   for (dbuf& b : e->sx) b.release();
   for (int i = 0; i < kStages; i++) {
@@ -652,16 +604,10 @@ void lb_engine_destroy(lb_engine* e) {
   hipStreamSynchronize(e->stream3);
   if (e->scratch) delete e->scratch;
   if (e->h_nu) hipHostFree(e->h_nu);
-  if (e->h_flag) hipHostFree(e->h_flag);
   if (e->h_stage) hipHostFree(e->h_stage);
   hipStreamDestroy(e->stream2);
   hipStreamDestroy(e->stream3);
   hipStreamDestroy(e->stream);
-  for (hipStream_t h : e->hp)
-    if (h) {
-      hipStreamSynchronize(h);
-      hipStreamDestroy(h);
-    }
   {
     std::lock_guard<std::mutex> lk(g_engine_mu);
     g_engine_count[e->device]--;
@@ -1020,52 +966,34 @@ static hipError_t msm_reduce(lb_engine* e, hipStream_t st, uint32_t bcap, uint32
   return hipGetLastError();
 }
 
-// s1: P_u = sum of r_i PK_i over the sets of root u with live[i] (k_gsum_*), the Miller loops
+// s1: P_u = sum of r_i PK_i over the live sets of root u (set_live; k_gsum_*), the Miller loops
 // (form by root count and device load) into the leaves of the root product tree, the tree.
-static hipError_t per_root_chain(lb_engine* e, uint32_t n, uint32_t nuh, uint32_t mu, const uint32_t* live) {
+static hipError_t per_root_chain(lb_engine* e, uint32_t n, uint32_t nuh, uint32_t mu) {
   hipStream_t s1 = e->stream;
   const uint32_t* nu = e->n_u.as<uint32_t>();
+  const bool row = e->alone && e->row_fe;  // the row engine, up to row_max roots / tree nodes per launch
+  const bool row_roots = row && nuh <= e->row_max;
   {
     stage_scope sc(e, ST_GSUM, s1);
-    // chunks of <= LB_GROUP_CHUNK members: at most nuh + n / LB_GROUP_CHUNK of them
+    // chunks of <= gchunk members: at most nuh + n / gchunk of them
     const uint32_t nch = nuh + n / e->gchunk;
-    const bool wave = e->gsum_tree && e->alone && e->gsum_wave;
-    if (wave)
+    if (e->alone)
       hipLaunchKernelGGL(k_gsum_wave, dim3(nblk(nch)), dim3(LB_TPB), 0, s1, n, nu, e->gch.as<uint32_t>(),
                          e->chunk_beg.as<uint32_t>(), e->chunk_end.as<uint32_t>(), e->chunk_root.as<uint32_t>(),
-                         e->members.as<uint32_t>(), live, e->rpk.as<uint32_t>(), e->gacc.as<uint32_t>());
-    else if (e->straus_run) {
-      hipError_t r = e->corder.ensure((size_t)(nch + 2 * (LB_STRAUS_CHUNK + 1)) * 4);
-      if (r != hipSuccess) return r;
-      uint32_t* cnt = e->corder.as<uint32_t>() + nch;
-      r = hipMemsetAsync(cnt, 0, (size_t)2 * (LB_STRAUS_CHUNK + 1) * 4, s1);
-      if (r != hipSuccess) return r;
-      for (uint32_t pass = 0; pass < 2; pass++)
-        hipLaunchKernelGGL(k_chunk_order, dim3(nblk(nch)), dim3(LB_TPB), 0, s1, nu, e->gch.as<uint32_t>(),
-                           e->chunk_beg.as<uint32_t>(), e->chunk_end.as<uint32_t>(), cnt, e->corder.as<uint32_t>(), pass);
-      hipLaunchKernelGGL(k_gsum_straus, dim3(nblk(nch)), dim3(LB_TPB), 0, s1, n, nu, e->gch.as<uint32_t>(),
-                         e->chunk_beg.as<uint32_t>(), e->chunk_end.as<uint32_t>(), e->corder.as<uint32_t>(),
-                         e->members.as<uint32_t>(), live, e->pk3.as<uint32_t>(), e->scalars.as<uint64_t>(),
-                         e->gacc.as<uint32_t>());
-    }
+                         e->members.as<uint32_t>(), e->set_live.as<uint32_t>(), e->rpk.as<uint32_t>(), e->gacc.as<uint32_t>());
     else
       hipLaunchKernelGGL(k_gsum_chunks, dim3(nblk(nch)), dim3(LB_TPB), 0, s1, n, nu,
                          e->gch.as<uint32_t>(), e->chunk_beg.as<uint32_t>(), e->chunk_end.as<uint32_t>(),
-                         e->members.as<uint32_t>(), live, e->rpk.as<uint32_t>(), e->gacc.as<uint32_t>());
-    // the per-root tree over the chunk sums (levels until one partial per root is left)
-    const bool tree = e->gsum_tree && e->alone && !wave;  // (the Straus chunks under load are 8 members too)
-    for (uint32_t st = 1; tree && st < e->gmax_chunks; st *= LB_GSUM_FAN)
-      hipLaunchKernelGGL(k_gsum_tree, dim3(nblk(nch)), dim3(LB_TPB), 0, s1, n, nu, e->gch.as<uint32_t>(),
-                         e->chunk_root.as<uint32_t>(), st, e->gacc.as<uint32_t>());
+                         e->members.as<uint32_t>(), e->set_live.as<uint32_t>(), e->rpk.as<uint32_t>(), e->gacc.as<uint32_t>());
     hipLaunchKernelGGL(k_gsum_final, dim3(nblk_inv(nuh)), dim3(LB_INV_TPB), 0, s1, n, nu, e->gch.as<uint32_t>(),
                        e->gacc.as<uint32_t>(), e->gp_aff.as<uint32_t>(), e->gp_inf.as<uint32_t>(),
-                       wave ? 2u : (tree ? 0u : 1u));
+                       e->alone ? 1u : 0u);
   }
   {
     stage_scope sc(e, ST_MILLER, s1);
     const bool shared = e->miller_form == 1 ||
                         (e->miller_form == 0 && !device_alone(e));
-    if (nuh <= e->row_max && e->alone && e->row_fe) {
+    if (row_roots) {
       hipLaunchKernelGGL(k_miller_row, dim3(nuh), dim3(LBR_NT), 0, s1, n, mu, nu, e->gp_aff.as<uint32_t>(),
                          e->gp_inf.as<uint32_t>(), e->h_aff.as<uint32_t>(), e->treeP.as<uint32_t>());
     } else if (nuh <= e->miller_wave_max) {
@@ -1091,7 +1019,7 @@ static hipError_t per_root_chain(lb_engine* e, uint32_t n, uint32_t nuh, uint32_
   {
     stage_scope sc(e, ST_TREE_P, s1);
     for (uint32_t lo = mu / 2; lo >= 1; lo /= 2) {
-      if (lo <= e->row_max && e->alone && e->row_fe)
+      if (row && lo <= e->row_max)
         hipLaunchKernelGGL(k_tree_up_row, dim3(lo), dim3(LBR_NT), 0, s1, mu, lo, nu, e->treeP.as<uint32_t>());
       else
         hipLaunchKernelGGL(k_tree_up_U, dim3(lo), dim3(64), 0, s1, mu, lo, nu, e->treeP.as<uint32_t>());
@@ -1108,10 +1036,9 @@ static int32_t run_pipeline(lb_engine* e, lb_batch* b, const uint64_t* scalars, 
   const uint32_t n = b->n_sets, nj = b->n_jobs;
   e->partial_serial = 0;
   e->alone = device_alone(e);
-  e->straus_run = e->straus && !e->alone;
-  e->rpk_stale = e->straus_run;
-  e->gchunk = (e->alone && e->gsum_tree) ? (e->gsum_wave ? LB_GROUP_CHUNK_WAVE : LB_GROUP_CHUNK_ALONE)
-                                          : (e->straus_run ? LB_STRAUS_CHUNK : LB_GROUP_CHUNK);
+  e->gchunk = e->alone ? LB_GROUP_CHUNK_WAVE : LB_GROUP_CHUNK;
+  const bool row = e->alone && e->row_fe;         // the row engine's forms, each up to its own item count
+  const bool row_small = row && n <= e->row_max;  // ... those over the sets of a small batch
   const bool one_unblinded = n == 1 && !scalars && unblinded;
   int st = fill_scalars(e, n, scalars, unblinded);
   if (st != LB_OK) return st;
@@ -1142,7 +1069,7 @@ static int32_t run_pipeline(lb_engine* e, lb_batch* b, const uint64_t* scalars, 
   for (dbuf* d : per_set) LB_HIP(d->ensure((size_t)ns * 4));
   LB_HIP(e->goff.ensure((size_t)(ns + 1) * 4));
   LB_HIP(e->gch.ensure((size_t)(ns + 1) * 4));
-  LB_HIP(e->n_u.ensure(8));
+  LB_HIP(e->n_u.ensure(4));
   LB_HIP(e->gacc.ensure((size_t)ns * sizeof(g1j)));
   LB_HIP(e->gp_aff.ensure((size_t)ns * sizeof(g1a)));
   const uint32_t bcap = (2 * LB_MSM_W * ns) / LB_MSM_CHUNK + LB_MSM_NB;  // bucket chunks, upper bound
@@ -1180,9 +1107,7 @@ static int32_t run_pipeline(lb_engine* e, lb_batch* b, const uint64_t* scalars, 
     // two would contend with the per-root chain on s1 for the whole chip
     // (also for a large batch alone on the device: its s1 chain then slowed by more than the s2
     // chain gained, 5.2 -> 5.1 M sets/s, round-3 A/B)
-    // (with the speculative per-root chain the pubkey side always runs on s3: the chain starts
-    // when it is done, beside the decode)
-    const hipStream_t s3 = (e->spec_gsum || n <= e->small_s_max) ? s3_ : s2;
+    const hipStream_t s3 = n <= e->small_s_max ? s3_ : s2;
     {
       stage_scope sc(e, ST_PK_CHUNKS, s3);
       if (nc && b->indexed)
@@ -1199,26 +1124,22 @@ static int32_t run_pipeline(lb_engine* e, lb_batch* b, const uint64_t* scalars, 
     // small batches alone: the r PK ladder (k_pk_blind mode 2) with row products, one 16-lane row
     // per set (on s3, before r_i sig_i; a fourth stream per engine, round 6, put 7 engines' 28
     // streams past what the device schedules without stalls: +10 ms on some batches)
-    const bool pk_rowp = e->small_par && pk_split && !e->straus_run && n <= e->row_max && e->alone && e->row_fe;
+    const bool pk_rowp = pk_split && row_small;
     // r_i sig_i on s3 beside the subgroup check (small batches alone, row forms, one-workgroup sum)
-    const bool sb_par = e->small_par && pk_split && !one_unblinded && n <= e->small_s_max && n <= e->small_s_g8_max &&
-                        n <= e->row_max && e->alone && e->row_fe && !e->straus_run;
+    const bool sb_par = pk_split && !one_unblinded && row_small && n <= e->small_s_max && n <= e->small_s_g8_max;
     {
       stage_scope sc(e, ST_PK_BLIND, s3);
-      // modes: 0 all, 1 aggregate + status (+ pk3 for the Straus sums), 2 the per-set ladder
-      const uint32_t m0 = (pk_split || e->straus_run) ? 1u : 0u;
-      const uint32_t m1 = e->straus_run ? 1u : (pk_split ? 2u : 0u);
-      if (e->straus_run) LB_HIP(e->pk3.ensure((size_t)ns * sizeof(g1x3)));
+      // modes: 0 all; split: 1 aggregate + status, then 2 the per-set ladder
+      const uint32_t m0 = pk_split ? 1u : 0u, m1 = pk_split ? 2u : 0u;
       // an indexed batch routed at upload on this engine: the statuses over every set (mode 1),
       // then the comb over its single-key sets and the ladder over the compacted rest
-      const bool route = b->indexed && b->n_comb && b->route_eng == e && !e->straus_run && !pk_rowp;
+      const bool route = b->indexed && b->n_comb && b->route_eng == e && !pk_rowp;
       if (route) {
         const uint32_t n_lad = n - b->n_comb;
         const uint32_t* sel = b->d_route.as<uint32_t>();
         hipLaunchKernelGGL(k_pk_blind, dim3(nblk_inv(n)), dim3(LB_INV_TPB), 0, s3, n, nc, b->d_set_chunk_off.as<uint32_t>(),
                            e->chunk_acc.as<uint32_t>(), e->chunk_status.as<int32_t>(), e->pk_aff.as<uint32_t>(),
-                           e->scalars.as<uint64_t>(), e->rpk.as<uint32_t>(), e->pk_status.as<int32_t>(), 1u, nullptr,
-                           nullptr, 0u);
+                           e->scalars.as<uint64_t>(), e->rpk.as<uint32_t>(), e->pk_status.as<int32_t>(), 1u, nullptr, 0u);
         LB_HIP(hipEventRecord(e->ev_pkst, s3));
         hipLaunchKernelGGL(k_pk_blind_comb, dim3(nblk(b->n_comb)), dim3(LB_TPB), 0, s3, n, b->n_comb, sel,
                            b->d_pk_off.as<uint32_t>(), b->d_pks.as<uint32_t>(), e->comb.as<uint32_t>(), e->comb_n,
@@ -1229,7 +1150,7 @@ static int32_t run_pipeline(lb_engine* e, lb_batch* b, const uint64_t* scalars, 
           hipLaunchKernelGGL(k_pk_blind, dim3(nblk_inv(n_lad)), dim3(LB_INV_TPB), 0, s3, n, nc,
                              b->d_set_chunk_off.as<uint32_t>(), e->chunk_acc.as<uint32_t>(), e->chunk_status.as<int32_t>(),
                              e->pk_aff.as<uint32_t>(), e->scalars.as<uint64_t>(), e->rpk.as<uint32_t>(),
-                             e->pk_status.as<int32_t>(), 2u, nullptr, sel + b->n_comb, n_lad);
+                             e->pk_status.as<int32_t>(), 2u, sel + b->n_comb, n_lad);
       }
       for (uint32_t mode = m0; !route && mode <= m1; mode++) {
         if (mode == 2u && pk_rowp) {
@@ -1239,8 +1160,7 @@ static int32_t run_pipeline(lb_engine* e, lb_batch* b, const uint64_t* scalars, 
         }
         hipLaunchKernelGGL(k_pk_blind, dim3(nblk_inv(n)), dim3(LB_INV_TPB), 0, s3, n, nc, b->d_set_chunk_off.as<uint32_t>(),
                            e->chunk_acc.as<uint32_t>(), e->chunk_status.as<int32_t>(), e->pk_aff.as<uint32_t>(),
-                           e->scalars.as<uint64_t>(), e->rpk.as<uint32_t>(), e->pk_status.as<int32_t>(), mode,
-                           (mode == 1u && e->straus_run) ? e->pk3.as<uint32_t>() : nullptr, nullptr, 0u);
+                           e->scalars.as<uint64_t>(), e->rpk.as<uint32_t>(), e->pk_status.as<int32_t>(), mode, nullptr, 0u);
         if (mode == 1u) LB_HIP(hipEventRecord(e->ev_pkst, s3));
       }
     }
@@ -1248,7 +1168,7 @@ static int32_t run_pipeline(lb_engine* e, lb_batch* b, const uint64_t* scalars, 
     // signatures: decoded while s1 groups and hashes the messages
     {
       stage_scope sc(e, ST_DECODE, s2);
-      if (n <= e->dec_row_max && e->alone && e->row_fe)
+      if (row && n <= e->dec_row_max)
         hipLaunchKernelGGL(k_decompress_sigs_row, dim3(LB_H2C_FOLD ? (n + 1) / 2 : (n + 3) / 4), dim3(64), 0, s2, n, b->d_sigs.as<uint8_t>(),
                            b->has_sizes ? b->d_sig_sizes.as<uint32_t>() : nullptr, e->sig_aff.as<uint32_t>(),
                            e->sig_aos.as<uint4>(), e->sig_inf.as<uint32_t>(), e->sig_status.as<int32_t>());
@@ -1259,12 +1179,9 @@ static int32_t run_pipeline(lb_engine* e, lb_batch* b, const uint64_t* scalars, 
       if (sb_par) LB_HIP(hipEventRecord(e->ev_sdec, s2));
       // (8 lanes per signature also for a slot while the device is otherwise idle ran slower:
       // 13.5 vs 13.0 ms per slot, profiles/r3_idle_forms_ab.txt)
-      if (n <= e->row_max && e->alone && e->row_fe && e->small_par)  // one wave per signature (round 6)
+      if (row_small)  // one wave per signature (round 6)
         hipLaunchKernelGGL(k_sig_subgroup_w4, dim3(n), dim3(64), 0, s2, n, e->sig_aff.as<uint32_t>(),
                            e->sig_inf.as<uint32_t>(), e->sig_status.as<int32_t>());
-      else if (n <= e->row_max && e->alone && e->row_fe)
-        hipLaunchKernelGGL(k_sig_subgroup_row, dim3(n), dim3(LBR_NT), 0, s2, n, e->sig_aff.as<uint32_t>(),
-                           e->sig_inf.as<uint32_t>(), e->sig_status.as<int32_t>(), e->row_proj ? 1u : 0u);
       else if (n <= e->subgroup_g8_max)
         hipLaunchKernelGGL(k_sig_subgroup_g8, dim3((n + 7) / 8), dim3(64), 0, s2, n, e->sig_aff.as<uint32_t>(),
                            e->sig_inf.as<uint32_t>(), e->sig_status.as<int32_t>());
@@ -1340,7 +1257,7 @@ static int32_t run_pipeline(lb_engine* e, lb_batch* b, const uint64_t* scalars, 
                              e->uid_of.as<uint32_t>(), e->set_uid.as<uint32_t>(), e->gcnt.as<uint32_t>(),
                              e->gpos.as<uint32_t>());
         hipLaunchKernelGGL(k_msg_scan, dim3(1), dim3(1024), 0, s1, nu, 0u, e->gchunk, e->gcnt.as<uint32_t>(), e->goff.as<uint32_t>(),
-                           e->gch.as<uint32_t>(), nullptr, nullptr, nullptr, e->n_u.as<uint32_t>() + 1);
+                           e->gch.as<uint32_t>(), nullptr, nullptr, nullptr);
         hipLaunchKernelGGL(k_chunk_fill, dim3(nblk(n + n / e->gchunk + 1)), dim3(LB_TPB), 0, s1, nu,
                            e->gchunk, e->goff.as<uint32_t>(), e->gch.as<uint32_t>(),
                            e->chunk_beg.as<uint32_t>(), e->chunk_end.as<uint32_t>(), e->chunk_root.as<uint32_t>());
@@ -1349,24 +1266,23 @@ static int32_t run_pipeline(lb_engine* e, lb_batch* b, const uint64_t* scalars, 
       }
       // distinct-root count to the host: the per-root kernels below are launched over it (a
       // launch over the set count would size their private-segment scratch for n lanes)
-      // (one set: one root of one chunk, known without the round trip)
+      // (one set: one root, known without the round trip)
       if (n == 1) {
-        e->h_nu[0] = 1;
-        e->h_nu[1] = 1;
+        *e->h_nu = 1;
       } else {
-        LB_HIP(hipMemcpyAsync(e->h_nu, e->n_u.p, 8, hipMemcpyDeviceToHost, s1));
+        LB_HIP(hipMemcpyAsync(e->h_nu, e->n_u.p, 4, hipMemcpyDeviceToHost, s1));
         LB_HIP(hipStreamSynchronize(s1));
       }
     }
-    const uint32_t nuh = e->h_nu[0];
-    e->gmax_chunks = e->h_nu[1];
+    const uint32_t nuh = *e->h_nu;
+    const bool row_hash = row && nuh <= e->hash_row_max;  // hash_to_G2 on the row engine
     if (nuh == 0 || nuh > n) return LB_ERR_DEVICE;
     mu = 1;
     while (mu < nuh) mu <<= 1;
     // ---- s1: hash_to_G2 once per distinct root
     {
       stage_scope sc(e, ST_HASH_MAP, s1);
-      if (nuh <= e->hash_row_max && e->alone && e->row_fe)
+      if (row_hash)
         hipLaunchKernelGGL(k_hash_map_row, dim3(LB_H2C_FOLD ? (LBR_FP2_W4 ? 2 * nuh : nuh) : (2 * nuh + 3) / 4), dim3(64), 0, s1, n, nuh,
                            e->uniq_set.as<uint32_t>(), b->d_msgs.as<uint8_t>(), e->q.as<uint32_t>());
       else
@@ -1378,9 +1294,9 @@ static int32_t run_pipeline(lb_engine* e, lb_batch* b, const uint64_t* scalars, 
       // 8 lanes per root when the device runs no other batch (a few hundred waves on 1 024 SIMDs:
       // latency), one lane per root under load (2.5x less work), as for the Miller loops below
       const bool alone = e->miller_form == 0 && device_alone(e);
-      if (nuh <= e->hash_row_max && e->alone && e->row_fe)
+      if (row_hash)
         hipLaunchKernelGGL(k_hash_finish_row, dim3(nuh), dim3(LBR_NT), 0, s1, n, nu, e->q.as<uint32_t>(),
-                           e->h_aff.as<uint32_t>(), e->hash_row_careful ? 1u : (e->row_proj ? 0u : 2u));
+                           e->h_aff.as<uint32_t>(), e->hash_row_careful ? 1u : 0u);
       else if (nuh <= e->hash_g8_max || (LB_HASH_ALONE_G8 && alone))
         hipLaunchKernelGGL(k_hash_finish_g8, dim3((nuh + 7) / 8), dim3(64), 0, s1, n, nu, e->q.as<uint32_t>(),
                            e->h_aff.as<uint32_t>());
@@ -1406,11 +1322,7 @@ static int32_t run_pipeline(lb_engine* e, lb_batch* b, const uint64_t* scalars, 
       stage_scope sc(e, ST_SIG_MSM, s2);
       LB_HIP(e->s_terms.ensure((size_t)n * sizeof(g2j)));
       LB_HIP(e->s_part.ensure((size_t)((n + 63) / 64) * sizeof(g2j)));
-      if (n <= e->row_max && e->alone && e->row_fe)
-        hipLaunchKernelGGL(k_sig_blind_row, dim3(n), dim3(LBR_NT), 0, s2, n, e->sig_aff.as<uint32_t>(),
-                           e->scalars.as<uint64_t>(), e->set_live.as<uint32_t>(), e->sig_inf.as<uint32_t>(),
-                           e->s_terms.as<uint32_t>(), e->row_proj ? 1u : 0u);
-      else if (n <= e->small_s_g8_max)
+      if (n <= e->small_s_g8_max)
         hipLaunchKernelGGL(k_sig_blind_g8, dim3((n + 7) / 8), dim3(64), 0, s2, n, e->sig_aff.as<uint32_t>(),
                            e->scalars.as<uint64_t>(), e->set_live.as<uint32_t>(), e->sig_inf.as<uint32_t>(),
                            e->s_terms.as<uint32_t>());
@@ -1443,7 +1355,7 @@ static int32_t run_pipeline(lb_engine* e, lb_batch* b, const uint64_t* scalars, 
       hipLaunchKernelGGL(k_msg_scan, dim3(1), dim3(1024), 0, s2, nullptr, (uint32_t)LB_MSM_NB, (uint32_t)LB_MSM_CHUNK,
                          e->bcnt.as<uint32_t>(),
                          e->boff.as<uint32_t>(), e->bch.as<uint32_t>(), e->bchunk_beg.as<uint32_t>(),
-                         e->bchunk_end.as<uint32_t>(), nullptr, nullptr);
+                         e->bchunk_end.as<uint32_t>(), nullptr);
       hipLaunchKernelGGL(k_msm_scatter, dim3(nblk(n)), dim3(LB_TPB), 0, s2, n, e->scalars.as<uint64_t>(),
                          e->set_live.as<uint32_t>(), e->sig_inf.as<uint32_t>(), e->boff.as<uint32_t>(),
                          e->bcursor.as<uint32_t>(), e->bmembers.as<uint32_t>());
@@ -1453,19 +1365,10 @@ static int32_t run_pipeline(lb_engine* e, lb_batch* b, const uint64_t* scalars, 
       LB_HIP(msm_reduce(e, s2, bcap, LB_MSM_NB, 1u, LB_MSM_W, e->treeS.as<uint32_t>(), 2 * mj, 1u,
                         (uint64_t)2 * LB_MSM_W * n, LB_MSM_CHUNK));
     }
-    // ---- s1: per-root sums of r_i PK_i and the Miller loops: on speculative liveness (the pubkey
-    // side only) as soon as it is done, else after the signature decode
-    if (e->spec_gsum) {
-      LB_HIP(e->set_spec.ensure((size_t)ns * 4));
-      LB_HIP(hipStreamWaitEvent(s1, e->ev_pk, 0));
-      hipLaunchKernelGGL(k_spec_live, dim3(nblk(nj)), dim3(LB_TPB), 0, s1, nj, b->d_job_off.as<uint32_t>(),
-                         e->pk_status.as<int32_t>(), e->set_spec.as<uint32_t>());
-      LB_HIP(per_root_chain(e, n, nuh, mu, e->set_spec.as<uint32_t>()));
-    } else {
-      LB_HIP(hipStreamWaitEvent(s1, e->ev_dec, 0));
-      LB_HIP(hipStreamWaitEvent(s1, e->ev_pk, 0));  // r PK (the decode's wait covered the statuses only)
-      LB_HIP(per_root_chain(e, n, nuh, mu, e->set_live.as<uint32_t>()));
-    }
+    // ---- s1: per-root sums of r_i PK_i and the Miller loops, after the signature decode
+    LB_HIP(hipStreamWaitEvent(s1, e->ev_dec, 0));
+    LB_HIP(hipStreamWaitEvent(s1, e->ev_pk, 0));  // r PK (the decode's wait covered the statuses only)
+    LB_HIP(per_root_chain(e, n, nuh, mu));
   } else {
     // no sets: every job is empty; the message tree is the single identity leaf
     LB_HIP(hipEventRecord(e->ev_dec, s2));
@@ -1481,7 +1384,7 @@ static int32_t run_pipeline(lb_engine* e, lb_batch* b, const uint64_t* scalars, 
   // ---- s2: ML(-G1, S_root)
   {
     stage_scope sc(e, ST_ML_S, s2);
-    if (e->alone && e->row_fe)
+    if (row)
       hipLaunchKernelGGL(k_ml_S_row, dim3(1), dim3(LBR_NT), 0, s2, mj, e->treeS.as<uint32_t>(), e->fS.as<uint32_t>());
     else
       hipLaunchKernelGGL(k_ml_S, dim3(1), dim3(64), 0, s2, mj, e->treeS.as<uint32_t>(), e->fS.as<uint32_t>());
@@ -1489,17 +1392,6 @@ static int32_t run_pipeline(lb_engine* e, lb_batch* b, const uint64_t* scalars, 
   LB_HIP(hipEventRecord(e->ev_s, s2));
   LB_HIP(hipStreamWaitEvent(s1, e->ev_s, 0));  // join
   LB_HIP(hipGetLastError());
-  if (n && e->spec_gsum) {
-    // a set counted in the speculative sums whose signature failed to decode: redo the per-root
-    // chain with the full statuses (batches with malformed signatures only)
-    LB_HIP(e->live_flag.ensure(4));
-    LB_HIP(hipMemsetAsync(e->live_flag.p, 0, 4, s1));
-    hipLaunchKernelGGL(k_live_mismatch, dim3(nblk(n)), dim3(LB_TPB), 0, s1, n, e->set_live.as<uint32_t>(),
-                       e->set_spec.as<uint32_t>(), e->live_flag.as<uint32_t>());
-    LB_HIP(hipMemcpyAsync(e->h_flag, e->live_flag.p, 4, hipMemcpyDeviceToHost, s1));
-    LB_HIP(hipStreamSynchronize(s1));
-    if (*e->h_flag) LB_HIP(per_root_chain(e, n, *e->h_nu, mu, e->set_live.as<uint32_t>()));
-  }
   return LB_OK;
 }
 
@@ -1708,8 +1600,7 @@ static int32_t search_round(lb_engine* e, const search_ctx& x, const std::vector
   auto U = [&](int k) { return e->sx[k].as<uint32_t>(); };
   {
     stage_scope sc(e, ST_FALLBACK, s1);
-    const bool pre = x.rs && e->search_pre;
-    if (cm && T && (rs_path || pre || T <= e->search_small_max)) {
+    if (cm && T && (rs_path || T <= e->search_small_max)) {
       // small or root-level round: per-position terms + per-instance segmented sums (no bucket MSM)
       std::vector<uint32_t> blo, bhi, bo{0};
       for (uint32_t j = 0; j < cm; j++) {
@@ -1729,9 +1620,6 @@ static int32_t search_round(lb_engine* e, const search_ctx& x, const std::vector
       if (rs_path)
         hipLaunchKernelGGL(k_rsm_terms, dim3(nblk(T)), dim3(LB_TPB), 0, s1, T, cm, ma, e->s_root.as<uint32_t>(), x.nu,
                            e->s_terms.as<uint32_t>());
-      else if (pre)  // the per-set terms r_i sig_i are kept from search_root_sums
-        hipLaunchKernelGGL(k_smsm_terms_pre, dim3(nblk(T)), dim3(LB_TPB), 0, s1, T, cm, ma, e->members.as<uint32_t>(),
-                           e->set_uid.as<uint32_t>(), e->s_set.as<uint32_t>(), n, e->s_terms.as<uint32_t>());
       else if (e->smsm_form == 1 ||
                (e->smsm_form == 0 && !device_alone(e)))
         hipLaunchKernelGGL(k_smsm_terms_lane, dim3(nblk_inv(T)), dim3(LB_INV_TPB), 0, s1, T, cm, ma,
@@ -1772,7 +1660,7 @@ static int32_t search_round(lb_engine* e, const search_ctx& x, const std::vector
       }
       hipLaunchKernelGGL(k_msg_scan, dim3(1), dim3(1024), 0, s1, nullptr, nb, schunk, e->bcnt.as<uint32_t>(),
                          e->boff.as<uint32_t>(), e->bch.as<uint32_t>(), e->bchunk_beg.as<uint32_t>(),
-                         e->bchunk_end.as<uint32_t>(), nullptr, nullptr);
+                         e->bchunk_end.as<uint32_t>(), nullptr);
       if (T) {
         if (w4)
           hipLaunchKernelGGL(k_smsm_scatter<LB_MSM_W>, dim3(nblk(T)), dim3(LB_TPB), 0, s1, T, cm, ma,
@@ -1888,15 +1776,6 @@ static int32_t search_root_sums(lb_engine* e, const search_ctx& x) {
 
 static int32_t search_invalid(lb_engine* e, lb_batch* b, uint32_t mu, int32_t* out_job) {
   const uint32_t n = b->n_sets, nj = b->n_jobs;
-  if (e->rpk_stale && n) {
-    // the per-root sums ran the Straus form (no per-set r PK): the search's range sums need them
-    hipLaunchKernelGGL(k_pk_blind, dim3(nblk_inv(n)), dim3(LB_INV_TPB), 0, e->stream, n, b->n_chunks,
-                       b->d_set_chunk_off.as<uint32_t>(), e->chunk_acc.as<uint32_t>(), e->chunk_status.as<int32_t>(),
-                       e->pk_aff.as<uint32_t>(), e->scalars.as<uint64_t>(), e->rpk.as<uint32_t>(),
-                       e->pk_status.as<int32_t>(), 2u, nullptr, nullptr, 0u);
-    LB_HIP(hipGetLastError());
-    e->rpk_stale = false;
-  }
   search_ctx x;
   x.n = n;
   x.mu = mu;
@@ -2084,41 +1963,9 @@ static void finish_profile(lb_engine* e) {
   }
 }
 
-// The engine's streams for the duration of one call: the high-priority trio for small batches
-// (created once, at the greatest priority), the normal trio otherwise.  The caller holds e->mu.
-struct stream_choice {
-  lb_engine* e;
-  bool swapped = false;
-  stream_choice(lb_engine* e_, uint32_t n_sets) : e(e_) {
-    if (!e->prio_max || n_sets > e->prio_max) return;
-    if (!e->hp[0]) {
-      int least = 0, greatest = 0;
-      hipDeviceGetStreamPriorityRange(&least, &greatest);
-      for (int k = 0; k < 3; k++)
-        if (hipStreamCreateWithPriority(&e->hp[k], hipStreamNonBlocking, greatest) != hipSuccess) {
-          for (int j = 0; j <= k; j++)
-            if (e->hp[j]) hipStreamDestroy(e->hp[j]);
-          e->hp[0] = e->hp[1] = e->hp[2] = nullptr;
-          return;  // the normal streams still work
-        }
-    }
-    std::swap(e->stream, e->hp[0]);
-    std::swap(e->stream2, e->hp[1]);
-    std::swap(e->stream3, e->hp[2]);
-    swapped = true;
-  }
-  ~stream_choice() {
-    if (!swapped) return;
-    std::swap(e->stream, e->hp[0]);
-    std::swap(e->stream2, e->hp[1]);
-    std::swap(e->stream3, e->hp[2]);
-  }
-};
-
 // caller holds e->mu
 static int32_t verify_locked(lb_engine* e, lb_batch* b, const uint64_t* scalars, int32_t* out_job) {
   LB_HIP(hipSetDevice(e->device));
-  stream_choice sch(e, b->n_sets);
   const uint32_t nj = b->n_jobs;
   if (nj == 0) return LB_OK;
   uint32_t m = 1, mu = 1;

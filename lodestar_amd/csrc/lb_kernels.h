@@ -327,66 +327,6 @@ __global__ void __launch_bounds__(64) k_sig_subgroup_g8(uint32_t n, const uint32
 }
 #endif  // LB_KG
 
-// The same check on the row engine for small batches while alone (one workgroup per signature):
-// [|x|]P by the op list's fast ladder (a zero Z, the mark of any exceptional case, reruns it with
-// the tested additions: inputs here are adversarial), psi(P) by one program, the comparison on
-// thread 0 (jac_eq on the exported canonical words).
-#if LB_KG(12)
-__global__ void __launch_bounds__(LBR_NT) k_sig_subgroup_row(uint32_t n, const uint32_t* __restrict__ sig_aff,
-                                                           const uint32_t* __restrict__ sig_inf,
-                                                           int32_t* __restrict__ sig_status, uint32_t proj) {
-  LBR_SHARED_N(S, LBR_PROGS_END - LBR_G2DBL);
-  const uint32_t i = blockIdx.x;
-  if (i >= n) return;
-  if (sig_status[i] != LB_OK || sig_inf[i]) return;  // uniform
-  r_init(S, LBR_PROGS_END - LBR_G2DBL, LBR_G2DBL);
-  const int P = LBR_A(3), X = LBR_A(4), PSI = LBR_A(4) + 6;
-  {
-    const int t = r_tid();
-    if (t < 6) {
-      fp v;
-      if (t < 4)
-        LB_UNROLL for (int w = 0; w < 12; w++) v.v[w] = sig_aff[(size_t)(12 * t + w) * n + i];
-      else
-        v = t == 4 ? fp_one() : fp_zero();
-      r_stage_fp(S, t, v);
-    }
-    r_sync();
-    r_import_staged(S, P, 6);
-  }
-  if (proj) {
-    // round 6: the [|x|] ladder in projective coordinates with the complete formulas (no
-    // exceptional case, no rerun), then psi(P) = -acc <=> X1 Z2 = X2 Z1 and Y1 Z2 = -Y2 Z1 (PEQN;
-    // an infinite acc leaves Y2 Z1 != 0)
-    r_run(S, &LBR_OPS_XLADDER_P, LBR_OPS_XLADDER_P.n);
-    r_g2_psi(S, PSI, P);
-    r_gather(S, LBR_IN, 12, [&](int e) { return e < 6 ? PSI + e : X + e - 6; });
-    r_exec(S, LBR_PEQN);
-    const lds_i32* pq = r_progs(S) + LBR_PEQN;
-    const uint32_t mz = r_zero_mask(S, 4, [&](int e) { return pq[2 + e]; });
-    if (r_tid() == 0 && mz != 0xf) sig_status[i] = LB_POINT_NOT_IN_GROUP;
-    return;
-  }
-  r_run(S, &LBR_OPS_XLADDER, LBR_OPS_XLADDER.n);
-  if (r_zero_mask(S, 2, [&](int e) { return X + 4 + e; }) == 3) r_g2_mul_xabs<false>(S, X, P);
-  r_g2_psi(S, PSI, P);
-  // psi(P) == -acc on the row, from G2ADD's exceptional-case values (round 6: the lane-0 jac_eq
-  // epilogue cost the kernel 1.5 KB of private segment per lane at the 1 024-thread workgroup's
-  // 128 VGPRs): with both points finite, H = 0 <=> equal x, and then r = 0 <=> equal y, so
-  // psi(P) = -acc <=> H = 0 and (r != 0 or y(acc) = 0).  Bits: 0-1 Z of psi(P), 2-3 Z of acc,
-  // 4-5 H, 6-7 r, 8-9 y of acc (r_zero_mask tests canonical values: exact)
-  r_gather(S, LBR_IN, 12, [&](int e) { return e < 6 ? PSI + e : X + e - 6; });
-  r_exec(S, LBR_G2ADD);
-  const lds_i32* prog = r_progs(S) + LBR_G2ADD;
-  const uint32_t m = r_zero_mask(S, 10, [&](int e) {
-    return e < 2 ? PSI + 4 + e : (e < 4 ? X + 2 + e : (e < 8 ? prog[4 + e] : X + 2 + (e - 8)));
-  });
-  const bool ok = (m & 0x3) != 0x3 && (m & 0xc) != 0xc && (m & 0x30) == 0x30 &&
-                  ((m & 0xc0) != 0xc0 || (m & 0x300) == 0x300);
-  if (r_tid() == 0 && !ok) sig_status[i] = LB_POINT_NOT_IN_GROUP;
-}
-#endif  // LB_KG
-
 // ---------------------------------------------------------------- hash_to_G2
 // ---- expand_message_xmd for a 32-byte message at word level (no byte buffers: the byte-wise
 // SHA-256 message builder kept its buffers on the stack, ~1.5 KB of private segment per lane).
@@ -856,23 +796,17 @@ __global__ void __launch_bounds__(LBR_NT) k_hash_finish_row(uint32_t n, const ui
     r_sync();
     r_import_staged(S, Q0, 12);
   }
-  // careful bit 0 (LB_HASH_ROW_CAREFUL, tests): the Jacobian chain with the exceptional-case
-  // tests; bit 1 (LB_ROW_PROJ=0): the Jacobian fast chain (rerun with the tests on Z = 0).
-  // Default (round 6): projective coordinates, complete additions, no rerun.
+  // careful = 1 (LB_HASH_ROW_CAREFUL, the tests' reference): the Jacobian chain with the
+  // exceptional-case tests.  0, the default (round 6): projective coordinates, complete
+  // additions, no exceptional case.
   const bool proj = careful == 0;
   if (proj) {
     r_g2_prog(S, LBR_JTOP, Q0, Q0);
     r_g2_prog(S, LBR_JTOP, Q1, Q1);
     r_run(S, &LBR_OPS_HASH_P, LBR_OPS_HASH_P.n);  // Q0 + Q1, cofactor clearing into H
   } else {
-    r_copy(S, LBR_A(5), Q0, 12);  // Q0, Q1 kept for a recomputation
-    r_run(S, &LBR_OPS_HASH, LBR_OPS_HASH.n);  // Q0 + Q1, cofactor clearing into H (fast path)
-    // Z = 0 (or `careful` bit 0, LB_HASH_ROW_CAREFUL for the tests): again with the tests
-    if (r_zero_mask(S, 2, [&](int e) { return H + 4 + e; }) == 3 || (careful & 1)) {
-      r_copy(S, Q0, LBR_A(5), 12);
-      r_g2_add(S, Q0, Q0, Q1);
-      r_g2_clear_cofactor<false>(S, H, Q0);
-    }
+    r_g2_add(S, Q0, Q0, Q1);
+    r_g2_clear_cofactor<false>(S, H, Q0);
   }
   r_export(S, H, 6);
   if (r_tid() == 0) {
@@ -980,10 +914,6 @@ __global__ void __launch_bounds__(LB_TPB, LB_MINW) k_pk_chunks(uint32_t nc, cons
 // << 1) | is_infinity.  A gather by validator index touches one L2 line (a word-major layout
 // touched 24 lines + 1 for the flag: with a mainnet-sized table every one a miss).
 #define LB_TABLE_REC 32
-// an affine G1 point with beta x (the GLV endomorphism [lambda]P = (beta x, y)): 144 B, AoS
-struct g1x3 {
-  fp x, y, bx;
-};
 __device__ __forceinline__ g1a table_ld(const uint32_t* __restrict__ table, uint32_t t) {
   return aos_ld<g1a>(table + (size_t)LB_TABLE_REC * t, 0);
 }
@@ -1080,12 +1010,9 @@ __global__ void __launch_bounds__(LB_INV_TPB, LB_MINW_G1) k_pk_blind(uint32_t n,
                                                          const uint64_t* __restrict__ scalars,
                                                          uint32_t* __restrict__ rpk,
                                                          int32_t* __restrict__ pk_status, uint32_t mode,
-                                                         uint32_t* __restrict__ pk3,
                                                          const uint32_t* __restrict__ sel, uint32_t n_sel) {
   // mode 0: all; 1: the aggregate, its status and affine form only (pk_status, pk_aff: what the
   // job statuses need, ahead of the ladder); 2: the ladder only, from mode 1's pk_status / pk_aff.
-  // pk3 (mode 1, optional): (x, y, beta x) per set, AoS, for the per-root Straus sums
-  // (k_gsum_straus), which then replace the ladder
   // sel (mode 2, optional): the ladder runs over the n_sel compacted set ids sel[] only (the
   // sets k_pk_blind_comb does not take), so no wave runs it for a few lanes among comb sets
   uint32_t i = blockIdx.x * LB_INV_TPB + threadIdx.x;
@@ -1144,7 +1071,6 @@ __global__ void __launch_bounds__(LB_INV_TPB, LB_MINW_G1) k_pk_blind(uint32_t n,
   if (mode == 1) {  // uniform
     if (!act) return;
     if (ok) soa_st(pk_aff, n, i, pk);
-    if (pk3 != nullptr) aos_st(pk3, i, g1x3{pk.x, pk.y, ok ? fp_mul(pk.x, fp_load(LB_GLV_BETA)) : fp_zero()});
     pk_status[i] = st;
     return;
   }
@@ -1356,7 +1282,7 @@ __global__ void __launch_bounds__(64) k_sig_subgroup_w4(uint32_t n, const uint32
   if (!ok && threadIdx.x == 0) sig_status[i] = LB_POINT_NOT_IN_GROUP;
 }
 #endif  // LB_KG
-// r_i sig_i of every decoded set (k_sig_blind_row's GLV double-and-add over sig, [lambda] sig =
+// r_i sig_i of every decoded set (k_sig_blind_g8's GLV double-and-add over sig, [lambda] sig =
 // -psi^2(sig), [1 + lambda] sig = -psi^4(sig), all affine) without the exceptional additions: for
 // sig in G2 the running scalar never meets +-T_d (the GLV lattice argument of k_pk_blind_rowp);
 // a set whose signature is not in G2 is not live, and k_g2_sum_g8 masks its term.
@@ -1580,18 +1506,13 @@ __global__ void __launch_bounds__(64) k_miller_wave(uint32_t n, uint32_t m, cons
 // slot 0xffffffff), probed from a keyed hash of the root (key from the engine's CSPRNG, so crafted
 // roots cannot be aimed at one probe chain); equality is decided on all 32 bytes.  A slot, once
 // claimed by compare-and-swap, never changes, so a loser can compare against its owner at once.
-// members summed per lane in k_gsum_chunks: 8 with the k_gsum_tree levels for a batch alone on
-// the device (latency), 32 with the chunk sums added per root on one lane under load (the tree's
-// wide launches cost the batches in flight throughput, profiles/r5_row_ab.txt); lb_engine.hip
-#ifndef LB_GROUP_CHUNK_ALONE
-#define LB_GROUP_CHUNK_ALONE 8
-#endif
+// members summed per lane: 32 in k_gsum_chunks, the chunk sums then added per root on one lane
+// (under load: wide per-root tree launches cost the batches in flight throughput,
+// profiles/r5_row_ab.txt); 4 in k_gsum_wave for a batch alone on the device (latency), whose
+// shuffle tree combines the 64 chunks of a wave (256 members); lb_engine.hip
 #define LB_GROUP_CHUNK 32
 #ifndef LB_GROUP_CHUNK_WAVE
-#define LB_GROUP_CHUNK_WAVE 4  // ... with k_gsum_wave's shuffle tree (64 chunks of a wave: 256 members)
-#endif
-#ifndef LB_GSUM_FAN
-#define LB_GSUM_FAN 4     // partial sums combined per lane and level in k_gsum_tree
+#define LB_GROUP_CHUNK_WAVE 4
 #endif
 #ifndef LB_MSM_CHUNK
 #define LB_MSM_CHUNK 16  // bucket members summed per lane in k_msm_chunks (the batch MSM's serial chain)
@@ -1648,7 +1569,6 @@ __global__ void __launch_bounds__(64) k_dedup_one(uint32_t* __restrict__ rep_of,
   uid_of[0] = 0;
   uniq_set[0] = 0;
   n_u[0] = 1;  // distinct roots
-  n_u[1] = 1;  // chunks of the largest root
   set_uid[0] = 0;
   cnt[0] = 1;
   pos[0] = 0;
@@ -1715,22 +1635,18 @@ __global__ void __launch_bounds__(1024) k_msg_scan(const uint32_t* __restrict__ 
                                                    const uint32_t* __restrict__ cnt,
                                                    uint32_t* __restrict__ goff, uint32_t* __restrict__ gch,
                                                    uint32_t* __restrict__ chunk_beg, uint32_t* __restrict__ chunk_end,
-                                                   uint32_t* __restrict__ chunk_root, uint32_t* __restrict__ max_chunks) {
-  __shared__ uint32_t s_m[1024], s_c[1024], s_x;
+                                                   uint32_t* __restrict__ chunk_root) {
+  __shared__ uint32_t s_m[1024], s_c[1024];
   const uint32_t nu = n_u ? *n_u : nu_const, t = threadIdx.x, per = (nu + 1023u) / 1024u;
   const uint32_t a = min(t * per, nu), b = min(a + per, nu);
-  uint32_t sm = 0, sc = 0, mx = 0;
+  uint32_t sm = 0, sc = 0;
   for (uint32_t u = a; u < b; u++) {
     sm += cnt[u];
-    const uint32_t cu = (cnt[u] + chunk - 1) / chunk;
-    sc += cu;
-    mx = max(mx, cu);
+    sc += (cnt[u] + chunk - 1) / chunk;
   }
-  if (t == 0) s_x = 0;
   s_m[t] = sm;
   s_c[t] = sc;
   __syncthreads();
-  if (max_chunks) atomicMax(&s_x, mx);
   for (uint32_t d = 1; d < 1024; d <<= 1) {
     const uint32_t vm = t >= d ? s_m[t - d] : 0u, vc = t >= d ? s_c[t - d] : 0u;
     __syncthreads();
@@ -1758,7 +1674,6 @@ __global__ void __launch_bounds__(1024) k_msg_scan(const uint32_t* __restrict__ 
     goff[nu] = s_m[1023];
     gch[nu] = s_c[1023];
   }
-  if (max_chunks && t == 0) *max_chunks = s_x;  // (the atomics completed before the scan's barriers)
 }
 #endif  // LB_KG
 
@@ -2169,74 +2084,6 @@ __global__ void __launch_bounds__(64) k_g2_sum64(uint32_t n_in, const uint32_t* 
 // product levels instead of 43 serial products per addition): 64 groups each add a strided share,
 // then a 6-level tree over the groups through LDS.  For the small-S path up to small_s_g8_max
 // terms (a block: ~0.6 ms of lone-lane 64:1 trees -> ~0.1 ms).
-// r_i sig_i for small batches on the row engine (one workgroup per set; lb_row.h G2 programs):
-// the GLV double-and-add of k_sig_blind_g8 over the table t1 = sig, t2 = [lambda] sig =
-// -psi^2(sig), t3 = t1 + t2, starting from the top non-zero digit (no infinity in the ladder), the
-// additions with the exceptional-case tests (r_g2_add).  Jacobian result, canonical words.
-#if LB_KG(12)
-__global__ void __launch_bounds__(LBR_NT) k_sig_blind_row(uint32_t n, const uint32_t* __restrict__ sig_aff,
-                                                        const uint64_t* __restrict__ scalars,
-                                                        const uint32_t* __restrict__ set_live,
-                                                        const uint32_t* __restrict__ sig_inf,
-                                                        uint32_t* __restrict__ terms, uint32_t proj) {
-  LBR_SHARED_N(S, LBR_PROGS_END - LBR_G2DBL);
-  const uint32_t i = blockIdx.x;
-  if (i >= n) return;
-  if (!msm_live(i, set_live, sig_inf)) {  // uniform
-    if (threadIdx.x == 0) soa_st(terms, n, i, jac_infinity<fp2>());
-    return;
-  }
-  r_init(S, LBR_PROGS_END - LBR_G2DBL, LBR_G2DBL);
-  const int T1 = LBR_A(0), T2 = LBR_A(0) + 6, T3 = LBR_A(1), ACC = LBR_A(1) + 6;
-  {
-    const int t = r_tid();
-    if (t < 6) {  // x.c0 x.c1 y.c0 y.c1 from the affine SoA, z = 1
-      fp v;
-      if (t < 4)
-        LB_UNROLL for (int w = 0; w < 12; w++) v.v[w] = sig_aff[(size_t)(12 * t + w) * n + i];
-      else
-        v = t == 4 ? fp_one() : fp_zero();
-      r_stage_fp(S, t, v);
-    }
-    r_sync();
-    r_import_staged(S, T1, 6);
-  }
-  r_g2_psi2(S, T2, T1);
-  r_g2_neg(S, T2);  // [lambda] sig = -psi^2(sig)
-  // proj (round 6): the table and the ladder in projective coordinates with the complete
-  // formulas (T1 = (x : y : 1) as it is; psi^2 and the negation act the same), the result back
-  // to Jacobian (PTOJ) for the S sum
-  if (proj) r_g2_prog(S, LBR_PADD, T3, T1, T2);
-  else r_g2_add(S, T3, T1, T2);
-  const uint64_t w = scalars[i];
-  const uint32_t k0 = (uint32_t)w, k1 = (uint32_t)(w >> 32);
-  auto digit = [&](int b) { return ((k0 >> b) & 1u) | (((k1 >> b) & 1u) << 1); };
-  int b = 31;
-  while (b >= 0 && digit(b) == 0) b--;
-  if (b < 0) {  // r = 0 (never for the engine's scalars): the identity
-    if (threadIdx.x == 0) soa_st(terms, n, i, jac_infinity<fp2>());
-    return;
-  }
-  auto tab = [&](uint32_t d) { return d == 1 ? T1 : (d == 2 ? T2 : T3); };
-  r_copy(S, ACC, tab(digit(b)), 6);
-  for (b--; b >= 0; b--) {
-    const uint32_t d = digit(b);
-    if (proj) {
-      r_g2_prog(S, LBR_PDBL1, ACC, ACC);
-      if (d) r_g2_prog(S, LBR_PADD, ACC, ACC, tab(d));
-    } else {
-      r_g2_dbl(S, ACC, ACC);
-      if (d) r_g2_add(S, ACC, ACC, tab(d));
-    }
-  }
-  if (proj) r_g2_prog(S, LBR_PTOJ, ACC, ACC);
-  r_export(S, ACC, 6);
-  if (threadIdx.x < 6) {
-    const fp v = r_fp_of_staged(S, threadIdx.x);
-    LB_UNROLL for (int k = 0; k < 12; k++) terms[(size_t)(12 * threadIdx.x + k) * n + i] = v.v[k];
-  }
-}
-#endif  // LB_KG
 #define LB_SUM_G8_GROUPS 64
 #if LB_KG(9)
 __global__ void __launch_bounds__(8 * LB_SUM_G8_GROUPS) k_g2_sum_g8(uint32_t n, const uint32_t* __restrict__ in,
@@ -2491,29 +2338,6 @@ __global__ void __launch_bounds__(LB_TPB) k_rsm_terms(uint32_t T, uint32_t c, sm
   for (int b = 6; b >= 0; b--) {
     r = jac_dbl_i(r);
     if ((wt >> b) & 1u) r = jac_add_i<fp2, true>(r, su);
-  }
-  soa_st(terms, T, t, r);
-}
-#endif  // LB_KG
-
-// The set-level instances of a round once the per-set terms T_i = r_i sig_i exist (search_root_sums
-// keeps them): position t's term is [w] T_i, w <= LB_WT_MAX, by an LB_WT_BITS-bit ladder in one lane
-// instead of the 43-bit weighted scalar by 8 lanes (k_smsm_terms_g8).
-#if LB_KG(7)
-__global__ void __launch_bounds__(LB_TPB) k_smsm_terms_pre(uint32_t T, uint32_t c, smsm_args a,
-                                                           const uint32_t* __restrict__ members,
-                                                           const uint32_t* __restrict__ set_uid,
-                                                           const uint32_t* __restrict__ set_terms, uint32_t n,
-                                                           uint32_t* __restrict__ terms) {
-  const uint32_t t = lb_tid();
-  if (t >= T) return;
-  uint32_t j, i, wt;
-  smsm_member(a, c, t, members, set_uid, j, i, wt);
-  const g2j ti = soa_ld<g2j>(set_terms, n, i);  // infinity for a set outside the equation
-  g2j r = jac_infinity<fp2>();
-  for (int b = LB_WT_BITS - 1; b >= 0; b--) {
-    r = jac_dbl_i(r);
-    if ((wt >> b) & 1u) r = jac_add_i<fp2, true>(r, ti);
   }
   soa_st(terms, T, t, r);
 }
@@ -2858,31 +2682,6 @@ __global__ void __launch_bounds__(LB_TPB) k_job_status(uint32_t n_jobs, const ui
 }
 #endif  // LB_KG
 
-// Speculative liveness for the per-root sums: set_spec[i] = 1 iff set i's job would be live if
-// every signature decodes (the pubkey statuses alone), so the per-root chain needs only the
-// pubkey side, not the signature decode.  A decode failure can only clear a set's liveness:
-// k_live_mismatch flags any set counted in the sums that the full statuses exclude.
-#if LB_KG(0)
-__global__ void __launch_bounds__(LB_TPB) k_spec_live(uint32_t n_jobs, const uint32_t* __restrict__ job_off,
-                                                      const int32_t* __restrict__ pk_status,
-                                                      uint32_t* __restrict__ set_spec) {
-  const uint32_t j = lb_tid();
-  if (j >= n_jobs) return;
-  const uint32_t a = job_off[j], e = job_off[j + 1];
-  bool live = a != e;
-  for (uint32_t i = a; i < e; i++) live &= pk_status[i] == LB_OK;
-  for (uint32_t i = a; i < e; i++) set_spec[i] = live ? 1u : 0u;
-}
-#endif  // LB_KG
-#if LB_KG(0)
-__global__ void __launch_bounds__(LB_TPB) k_live_mismatch(uint32_t n, const uint32_t* __restrict__ set_live,
-                                                          const uint32_t* __restrict__ set_spec,
-                                                          uint32_t* __restrict__ flag) {
-  const uint32_t i = lb_tid();
-  if (i < n && set_spec[i] && !set_live[i]) *flag = 1u;
-}
-#endif  // LB_KG
-
 // chunk c of a group: Jacobian sum of r_i PK_i over its live members -> gacc (stride n)
 #if LB_KG(4)
 __global__ void __launch_bounds__(LB_TPB, LB_MINW_GSUM) k_gsum_chunks(uint32_t n, const uint32_t* __restrict__ n_u,
@@ -2905,101 +2704,10 @@ __global__ void __launch_bounds__(LB_TPB, LB_MINW_GSUM) k_gsum_chunks(uint32_t n
 }
 #endif  // LB_KG
 
-// Chunk c of a group (<= LB_STRAUS_CHUNK members of one root): sum over its live members of
-// r_i PK_i with the blinding folded in (round 6, the loaded-device form): r_i = lo_i + hi_i lambda,
-// so the chunk sum is a joint (Straus) double-and-add over the 32 bit positions of all its
-// members' lo / hi halves, ONE doubling chain per chunk instead of one per set:
-//   acc = 2 acc;  acc += T_k[d_k]  for each member k with digit d_k = lo_k bit + 2 hi_k bit,
-//   T_k = {PK, [lambda]PK = (beta x, y), PK + [lambda]PK = (beta^2 x, -y) = (-x - beta x, -y)}.
-// Per set ~32 mixed additions + 32/8 doublings against k_pk_blind's per-set ladder (32 + 32) and
-// the chunk sum's Jacobian addition.  Equal keys in a chunk (duplicate validators) meet P = +-Q:
-// jac_add_aff_i handles them.  The per-set r_i PK_i (the search's) come from k_pk_blind mode 2
-// when a search needs them.
-#ifndef LB_STRAUS_CHUNK
-#define LB_STRAUS_CHUNK 8
-#endif
-// The lanes take the chunks in order of decreasing member count (k_chunk_order: a counting sort
-// by size), so a wave's chunks have equal counts but at its edges and the member loop runs to the
-// wave's largest count: in root order the single-member roots' chunks (every aggregate-and-proof
-// root) shared waves with 8-member chunks and idled 7 of 8 additions (measured: the Straus form
-// 5 % below the per-set ladders before the ordering).
-#if LB_KG(14)
-__global__ void __launch_bounds__(LB_TPB) k_chunk_order(const uint32_t* __restrict__ n_u, const uint32_t* __restrict__ gch,
-                                                        const uint32_t* __restrict__ chunk_beg,
-                                                        const uint32_t* __restrict__ chunk_end,
-                                                        uint32_t* __restrict__ cnt, uint32_t* __restrict__ order,
-                                                        uint32_t pass) {
-  // pass 0: cnt[m] = chunks of m members (m <= LB_STRAUS_CHUNK); pass 1: order (m descending),
-  // cnt[LB_STRAUS_CHUNK + 1 + m] the per-size cursors (zeroed with the counts)
-  const uint32_t c = lb_tid();
-  if (c >= gch[*n_u]) return;
-  const uint32_t m = chunk_end[c] - chunk_beg[c];
-  if (pass == 0) {
-    atomicAdd(&cnt[m], 1u);
-    return;
-  }
-  uint32_t base = 0;
-  for (uint32_t q = LB_STRAUS_CHUNK; q > m; q--) base += cnt[q];
-  order[base + atomicAdd(&cnt[LB_STRAUS_CHUNK + 1 + m], 1u)] = c;
-}
-#endif  // LB_KG
-#if LB_KG(14)
-__global__ void __launch_bounds__(LB_TPB, LB_MINW_GSUM) k_gsum_straus(uint32_t n, const uint32_t* __restrict__ n_u,
-                                                        const uint32_t* __restrict__ gch,
-                                                        const uint32_t* __restrict__ chunk_beg,
-                                                        const uint32_t* __restrict__ chunk_end,
-                                                        const uint32_t* __restrict__ order,
-                                                        const uint32_t* __restrict__ members,
-                                                        const uint32_t* __restrict__ set_live,
-                                                        const uint32_t* __restrict__ pk3,
-                                                        const uint64_t* __restrict__ scalars,
-                                                        uint32_t* __restrict__ gacc) {
-  const uint32_t t = lb_tid(), nch = gch[*n_u];
-  if (blockIdx.x * LB_TPB >= nch) return;  // whole wave idle (uniform)
-  const bool act = t < nch;
-  const uint32_t c = act ? order[t] : 0u;
-  const uint32_t b = act ? chunk_beg[c] : 0u, m = act ? chunk_end[c] - b : 0u;
-  // the wave's largest count: its first lane's (decreasing order)
-  const uint32_t mw = (uint32_t)__builtin_amdgcn_readfirstlane((int)m);
-  uint32_t idx[LB_STRAUS_CHUNK], lo[LB_STRAUS_CHUNK], hi[LB_STRAUS_CHUNK];
-  LB_UNROLL for (int k = 0; k < LB_STRAUS_CHUNK; k++) {
-    idx[k] = 0;
-    lo[k] = hi[k] = 0;  // absent or dead members: digit 0 throughout
-    if ((uint32_t)k < m) {
-      const uint32_t i = members[b + k];
-      idx[k] = i;
-      if (set_live[i]) {
-        const uint64_t w = scalars[i];
-        lo[k] = (uint32_t)w;
-        hi[k] = (uint32_t)(w >> 32);
-      }
-    }
-  }
-  jac<lb_g1f> acc = jac_infinity<lb_g1f>();
-#pragma clang loop unroll(disable)
-  for (int bit = 31; bit >= 0; bit--) {
-    if (!jac_is_inf(acc)) acc = jac_dbl_i(acc);
-    LB_UNROLL for (int k = 0; k < LB_STRAUS_CHUNK; k++) {
-      if ((uint32_t)k >= mw) break;  // wave-uniform
-      const uint32_t d = ((lo[k] >> bit) & 1u) | (((hi[k] >> bit) & 1u) << 1);
-      if (d != 0u) {
-        const g1x3 t = aos_ld<g1x3>(pk3, idx[k]);
-        aff<lb_g1f> q;
-        q.x = lb_g1f{d == 1u ? t.x : (d == 2u ? t.bx : fp_neg(fp_add(t.x, t.bx)))};
-        q.y = lb_g1f{d == 3u ? fp_neg(t.y) : t.y};
-        acc = jac_add_aff_i<lb_g1f, true>(acc, q);
-      }
-    }
-  }
-  if (act) soa_st(gacc, n, c, jac_as<fp>(acc));
-}
-#endif  // LB_KG
-
-// Per-root sums of a batch alone (round 6; replaces k_gsum_chunks + the k_gsum_tree launches):
-// the chunk sums of r_i PK_i (<= gchunk members per lane), then a segmented shuffle tree over the
-// wave's 64 chunks by root (wave_seg_sum); the first lane of each (root, wave) segment writes the
-// segment's sum to gacc, and k_gsum_final (mode 2) adds a root's segment heads.  One launch, the
-// partials in registers, log2(64) levels.
+// Per-root sums of a batch alone (round 6): the chunk sums of r_i PK_i (<= gchunk members per
+// lane), then a segmented shuffle tree over the wave's 64 chunks by root (wave_seg_sum); the first
+// lane of each (root, wave) segment writes the segment's sum to gacc, and k_gsum_final
+// (wave_heads) adds a root's segment heads.  One launch, the partials in registers, log2(64) levels.
 #if LB_KG(14)
 __global__ void __launch_bounds__(LB_TPB, LB_MINW_GSUM) k_gsum_wave(uint32_t n, const uint32_t* __restrict__ n_u,
                                                       const uint32_t* __restrict__ gch,
@@ -3030,48 +2738,25 @@ __global__ void __launch_bounds__(LB_TPB, LB_MINW_GSUM) k_gsum_wave(uint32_t n, 
 }
 #endif  // LB_KG
 
-// One level of the per-root sum tree over the chunk sums (in place, strided): at stride s, the
-// lane of chunk c with (c - gch[u]) a multiple of LB_GSUM_FAN s adds the partials at c + k s,
-// k = 1 .. LB_GSUM_FAN - 1, of its own root; after the levels with s < max chunks per root,
-// gacc[gch[u]] holds P_u.  The reads of one lane, [c, c + FAN s), are nobody else's writes.
-// (The serial chains this replaces, up to 32 members per lane and then up to 32 chunk sums per
-// root on one lane, were the longest per-root latency of a batch alone: VERDICT r4.)
-#if LB_KG(4)
-__global__ void __launch_bounds__(LB_TPB, LB_MINW_GSUM) k_gsum_tree(uint32_t n, const uint32_t* __restrict__ n_u,
-                                                      const uint32_t* __restrict__ gch,
-                                                      const uint32_t* __restrict__ chunk_root, uint32_t s,
-                                                      uint32_t* __restrict__ gacc) {
-  const uint32_t c = lb_tid();
-  if (c >= gch[*n_u]) return;
-  const uint32_t u = chunk_root[c], base = gch[u], end = gch[u + 1];
-  if ((c - base) % (LB_GSUM_FAN * s) != 0 || c + s >= end) return;
-  jac<lb_g1f> acc = jac_as<lb_g1f>(soa_ld<g1j>(gacc, n, c));
-  LB_UNROLL for (uint32_t k = 1; k < LB_GSUM_FAN; k++)
-    if (c + k * s < end) acc = jac_add_i<lb_g1f, true>(acc, jac_as<lb_g1f>(soa_ld<g1j>(gacc, n, c + k * s)));
-  soa_st(gacc, n, c, jac_as<fp>(acc));
-}
-#endif  // LB_KG
-
-// P_u (the tree's root at gacc[gch[u]]) to affine (one batched inversion per block); gp_inf[u]
-// flags P_u = infinity (no live member, or members cancelling), whose Miller value is 1.
+// P_u = the sum of root u's partials in gacc, to affine (one batched inversion per block);
+// gp_inf[u] flags P_u = infinity (no live member, or members cancelling), whose Miller value is 1.
+// wave_heads = 0: every chunk sum of the root (k_gsum_chunks); 1: its segment heads (k_gsum_wave)
 #if LB_KG(4)
 __global__ void __launch_bounds__(LB_INV_TPB, LB_MINW) k_gsum_final(uint32_t n, const uint32_t* __restrict__ n_u,
                                                            const uint32_t* __restrict__ gch,
                                                            const uint32_t* __restrict__ gacc,
                                                            uint32_t* __restrict__ gp_aff,
-                                                           uint32_t* __restrict__ gp_inf, uint32_t serial) {
+                                                           uint32_t* __restrict__ gp_inf, uint32_t wave_heads) {
   const uint32_t u = blockIdx.x * LB_INV_TPB + threadIdx.x;
   const uint32_t nu = *n_u;
   if (blockIdx.x * LB_INV_TPB >= nu) return;  // whole block idle (uniform)
   const bool act = u < nu;
   g1j acc = jac_infinity<fp>();
   if (act) {
-    if (serial == 1)  // (under load, and A/B: LB_GSUM_TREE=0) the root's chunk sums added on this lane
-      for (uint32_t c = gch[u]; c < gch[u + 1]; c++) acc = jac_add(acc, soa_ld<g1j>(gacc, n, c));
-    else if (serial == 2)  // k_gsum_wave: the root's segment heads (first chunk, then wave boundaries)
+    if (wave_heads)  // the root's first chunk, then its chunks at wave boundaries
       for (uint32_t c = gch[u]; c < gch[u + 1]; c = (c / LB_TPB + 1) * LB_TPB) acc = jac_add(acc, soa_ld<g1j>(gacc, n, c));
-    else  // k_gsum_tree: the tree's root
-      acc = soa_ld<g1j>(gacc, n, gch[u]);
+    else  // (under load) the root's chunk sums added on this lane
+      for (uint32_t c = gch[u]; c < gch[u + 1]; c++) acc = jac_add(acc, soa_ld<g1j>(gacc, n, c));
   }
   const bool zero = jac_is_inf(acc);
   // a block whose sums all have Z = 1 (the unblinded 1-set call's affine PK) skips the inversion

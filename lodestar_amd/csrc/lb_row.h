@@ -1395,24 +1395,11 @@ constexpr r_opl r_ops_hash_finish_p(int dst, int q) {
   o.op(RK_PADD, dst, T3, W);
   return o;
 }
-constexpr r_opl r_ops_xladder_p(int dst, int p) {
-  r_opl o;
-  o.p_mul_xabs(dst, p);
-  return o;
-}
 static __device__ const r_opl LBR_OPS_HASH_P = r_ops_hash_finish_p(LBR_A(4), LBR_A(3));
-static __device__ const r_opl LBR_OPS_XLADDER_P = r_ops_xladder_p(LBR_A(4), LBR_A(3));
 static __device__ const r_opl LBR_OPS_FE_A0 = r_ops_fe_tail(LBR_A(0), LBR_A(0));
 static __device__ const r_opl LBR_OPS_ML_A0 = r_ops_miller(LBR_A(0));
 static __device__ const r_opl LBR_OPS_ML_A7 = r_ops_miller(LBR_A(7));
 static __device__ const r_opl LBR_OPS_HASH = r_ops_hash_finish(LBR_A(4), LBR_A(3));
-// [|x|] p for the signature subgroup check (k_sig_subgroup_row): A(4) = [|x|] A(3), fast additions
-constexpr r_opl r_ops_xladder(int dst, int p) {
-  r_opl o;
-  o.g2_mul_xabs(dst, p);
-  return o;
-}
-static __device__ const r_opl LBR_OPS_XLADDER = r_ops_xladder(LBR_A(4), LBR_A(3));
 static_assert(r_ops_fe_tail(LBR_A(0), LBR_A(0)).n <= LBR_MAX_OPS && r_ops_hash_finish(LBR_A(4), LBR_A(3)).n <= LBR_MAX_OPS,
               "lb_row.h: op list size");
 
@@ -1819,8 +1806,8 @@ __device__ void r_g2_add_fast(int32_t* S, int dst, int a, int b) {
 // areas 0..2 besides.  FAST: no exceptional-case tests.  Every exceptional case of the
 // formulas (an operand at infinity, P = +-Q in an addition, a doubling of a point of order 2)
 // yields Z = 0, and a zero Z stays zero through every later doubling, addition, psi and psi^2:
-// a FAST result with Z != 0 is exact; Z = 0 (negligible probability for hash outputs) is
-// recomputed with the tests (k_hash_finish_row).
+// a FAST result with Z != 0 is exact; Z = 0 (negligible probability for hash outputs) has to be
+// recomputed with the tests.
 template <bool FAST>
 __device__ void r_g2_clear_cofactor(int32_t* S, int dst, int p) {
   const int T1 = LBR_A(0), T3 = LBR_A(0) + 6, T2 = LBR_A(1), X = LBR_A(1) + 6, W = LBR_A(2);

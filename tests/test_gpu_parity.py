@@ -526,13 +526,18 @@ def small_order_signatures():
 @pytest.mark.parametrize("g8_max,row_fe", [("0", "0"), (str(1 << 31), "0"), (str(1 << 31), "1")])
 def test_small_order_signatures_not_in_group(monkeypatch, g8_max, row_fe):
     """Every subgroup-check kernel (one lane per set: k_sig_subgroup; 8 lanes: k_sig_subgroup_g8;
-    a row workgroup per set: k_sig_subgroup_row, whose fast ladder meets the exceptional cases of
-    small-order points and reruns with the tested additions) rejects points of small order with
-    BLST_POINT_NOT_IN_GROUP, in one batch beside valid sets."""
+    one wave per set: k_sig_subgroup_w4, whose ladder skips the exceptional-case tests and, on a
+    zero final Z, the mark of the cases small-order points meet, reruns with them) rejects points of small
+    order with BLST_POINT_NOT_IN_GROUP, in one batch beside valid sets.  The row case pins the
+    latency forms (LB_ALONE=1), so k_sig_subgroup_w4 runs whatever ran on the device just before,
+    and with it k_sig_blind_w4 over every decoded signature, the small-order ones included, whose
+    terms the liveness-masked k_g2_sum_g8 must leave out of S."""
     from lodestar_amd import _native as N
     from lodestar_amd.engine import Engine
     monkeypatch.setenv("LB_SUBGROUP_G8_MAX", g8_max)
     monkeypatch.setenv("LB_ROW_FE", row_fe)
+    if row_fe == "1":
+        monkeypatch.setenv("LB_ALONE", "1")
     cases, jobs = case_jobs()
     valid = jobs[[c["name"] for c in cases].index("single_valid_0")]
     pk, root = valid[0].pubkeys, valid[0].signing_root
@@ -579,14 +584,14 @@ def test_search_c3_invalid_two_slots(engine):
 
 @pytest.mark.parametrize("knobs", ["LB_SEARCH_MERGE=0", "LB_ROOT_SHUFFLE=0", "LB_SEARCH_BLOCKS=0",
                                    "LB_SEARCH_BLOCKS=0+LB_SEARCH_MERGE=0",
-                                   "LB_SEARCH_BLOCKS=0+LB_SEARCH_ROOTSUM=0", "LB_SEARCH_BLOCKS=0+LB_SEARCH_PRE=1",
+                                   "LB_SEARCH_BLOCKS=0+LB_SEARCH_ROOTSUM=0",
                                    "LB_SMSM_FORM=lane", "LB_SMSM_FORM=lane+LB_SEARCH_BLOCKS=0+LB_SEARCH_ROOTSUM=0",
                                    "LB_SEARCH_CHUNK=32", "LB_SEARCH_CHUNK=1"])
 def test_search_forms_find_the_same_sets(monkeypatch, knobs):
     """Every selectable form of the invalid-set search (lb_engine.hip: look-ahead tests in a
     separate launch pair; the first round over per-root sums with look-ahead tests instead of
-    direct subtree checks from one 4-window MSM; that round over the 6-window bucket MSM; later
-    rounds over the kept per-set terms; roots numbered in input order) names exactly the planted jobs of c3 with one wrong
+    direct subtree checks from one 4-window MSM; that round over the 6-window bucket MSM; roots
+    numbered in input order) names exactly the planted jobs of c3 with one wrong
     attestation per slot (2 slots: above LB_SEARCH_SMALL_MAX, so the large-batch rounds run)."""
     from lodestar_amd.engine import Engine
     from lodestar_amd import workloads as W
@@ -726,15 +731,13 @@ def test_per_root_kernel_forms_agree(monkeypatch, name):
     assert outs[0] == outs[1] == outs[2] == outs[3] == outs[4] == outs[5]
 
 
-@pytest.mark.parametrize("spec", ["1", "0"])
-def test_speculative_per_root_chain(monkeypatch, spec):
-    """The per-root sums and Miller loops start on speculative liveness (pubkey statuses only,
-    LB_SPEC_GSUM=1) and are redone with the full statuses when a signature fails to decode.  c4
-    plants malformed signatures in jobs whose roots are shared with valid sets (the sync-committee
-    root): verdicts must equal the planted expectation either way; a valid c2 block too."""
+def test_search_after_partial_with_malformed_in_shared_roots():
+    """verify(), then partial() followed by search_after_partial() on one upload.  c4 plants
+    malformed signatures in jobs whose roots are shared with valid sets (the sync-committee root):
+    the per-root sums must leave those sets out, and both verdict paths must equal the planted
+    expectation; a valid c2 block too."""
     from lodestar_amd.engine import Engine
     from lodestar_amd import workloads as W
-    monkeypatch.setenv("LB_SPEC_GSUM", spec)
     with Engine(0) as e:
         for name in ("c4", "c2"):
             wl = W.make(e, name)
@@ -888,21 +891,16 @@ def test_engine_cap_reserves_scratch():
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", ["c3_mixed", "c4", "c2"])
 def test_per_root_sum_forms_agree(monkeypatch, name):
-    """Round 6 per-root sum forms, each pinned with LB_ALONE: under load (LB_ALONE=0) the Straus
-    chunk sums with the blinding folded in (k_gsum_straus; the per-set r PK computed only for a
-    search) against the per-set ladder + chunk sums (LB_GSUM_STRAUS=0); alone (LB_ALONE=1) the
-    segmented shuffle tree (k_gsum_wave) against the k_gsum_tree launches (LB_GSUM_WAVE=0) and the
-    serial chunk combine (LB_GSUM_TREE=0).  Same verdicts (c4 carries wrong and malformed sets, so
-    its search runs from the Straus form's lazily computed r PK), byte-identical root partials."""
+    """The two per-root sum forms, each pinned with LB_ALONE: under load (LB_ALONE=0) the chunk
+    sums of 32 members per lane (k_gsum_chunks) added serially per root (k_gsum_final over every
+    chunk sum); alone (LB_ALONE=1) chunks of 4 members combined by the segmented shuffle tree
+    (k_gsum_wave), k_gsum_final over the segment heads.  Same verdicts (c4 carries wrong and
+    malformed sets, so its search runs too), byte-identical root partials."""
     from lodestar_amd.engine import Engine
     from lodestar_amd import workloads as W
     outs = []
-    for alone, straus, wave, tree in (("0", "1", "1", "1"), ("0", "0", "1", "1"), ("1", "1", "1", "1"),
-                                      ("1", "1", "0", "1"), ("1", "1", "1", "0")):
+    for alone in ("0", "1"):
         monkeypatch.setenv("LB_ALONE", alone)
-        monkeypatch.setenv("LB_GSUM_STRAUS", straus)
-        monkeypatch.setenv("LB_GSUM_WAVE", wave)
-        monkeypatch.setenv("LB_GSUM_TREE", tree)
         with Engine(0) as e:
             wl = W.make(e, name)
             b = e.upload(W.indexed_for(e, wl))
@@ -912,6 +910,6 @@ def test_per_root_sum_forms_agree(monkeypatch, name):
                 part = bytes(b.partial(scalars=sc)[0])
             finally:
                 b.free()
-        assert np.array_equal(got, wl.expected), (alone, straus, wave, tree, np.nonzero(got != wl.expected))
+        assert np.array_equal(got, wl.expected), (alone, np.nonzero(got != wl.expected))
         outs.append(part)
     assert all(o == outs[0] for o in outs), [o[:8].hex() for o in outs]

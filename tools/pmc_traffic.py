@@ -27,7 +27,7 @@ STAGES = {
     "pk_blind": ["k_pk_blind", "k_pk_blind_comb"],
     "sig_msm": ["k_msm_count", "k_msm_scatter", "k_msm_chunks", "k_msm_buckets", "k_msm_reduce", "k_msm_buckets_g8",
                 "k_msm_window_g8", "k_msm_horner_g8", "k_sig_blind", "k_sig_blind_g8", "k_g2_sum64"],
-    "group_sum": ["k_chunk_fill", "k_gsum_chunks", "k_gsum_straus", "k_gsum_wave", "k_gsum_tree", "k_gsum_final"],
+    "group_sum": ["k_chunk_fill", "k_gsum_chunks", "k_gsum_wave", "k_gsum_final"],
     "miller": ["k_miller_g8", "k_miller_lane", "k_miller_wave", "k_miller_row"],
     "tree_up_P": ["k_tree_up_U", "k_tree_up_row"],
     "ml_S": ["k_ml_S", "k_ml_S_row"],

@@ -14,7 +14,7 @@ def parse(text):
             cur = m.group(1)
             out[cur] = {}
             continue
-        m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[bytes/(?:lane|block)\])?: (\S+) \[", line)
+        m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[[^\]]*\])?: (\S+) \[", line)
         if m and cur:
             out[cur][m.group(1).strip()] = m.group(2)
     return out
@@ -37,6 +37,6 @@ if __name__ == "__main__":
         if flt and not any(f in short for f in flt):
             continue
         r = d[n]
-        print(f"{short[:34]:34s} vgpr {r.get('VGPRs','?'):>4} agpr {r.get('AGPRs','?'):>4} "
-              f"scratch {r.get('ScratchSize','?'):>6} occ {r.get('Occupancy [waves/SIMD]', r.get('Occupancy','?')):>2} "
+        print(f"{short[:34]:34s} vgpr {r.get('VGPRs','?'):>4} agpr {r.get('AGPRs','?'):>4} sgpr {r.get('TotalSGPRs','?'):>4} "
+              f"scratch {r.get('ScratchSize','?'):>6} occ {r.get('Occupancy','?'):>2} "
               f"lds {r.get('LDS Size','?'):>6} spillV {r.get('VGPRs Spill','?')}")
