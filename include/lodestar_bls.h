@@ -202,8 +202,10 @@ int32_t lb_merkleize(lb_engine* e, uint32_t n_trees, const uint32_t* chunk_offse
 
 /*
  * KZG (EIP-4844 blobs; the c-kzg calls behind packages/beacon-node/src/util/kzg.ts:15-65, SURVEY.md
- * §8(f) row 4).  The host side (lodestar_amd/kzg.py) does the scalar-field work; these do the group
- * work on the GPU.
+ * §8(f) row 4).  Two levels: the group calls (lb_g1_lincomb, lb_kzg_verify_proof), for a host that
+ * does the scalar-field work itself (lodestar_amd/kzg.py with field="host"), and the blob-level
+ * calls further down (lb_kzg_blob_to_commitment ...), which take blobs and do the field work on the
+ * GPU as well.
  *
  * lb_kzg_load_setup (ckzg.loadTrustedSetup, kzg.ts:54-67): the monomial-form setup as Lodestar's
  * trusted_setup.bin holds it -- n_g1 compressed [tau^i] G1 (48 B each) and at least two compressed
@@ -227,6 +229,38 @@ int32_t lb_g1_lincomb(lb_engine* e, uint32_t n, const uint8_t* points48, const u
  */
 int32_t lb_kzg_verify_proof(lb_engine* e, const uint8_t* commitment48, const uint8_t* z32, const uint8_t* y32,
                             const uint8_t* proof48, int32_t* ok);
+
+/*
+ * Blob-level KZG: bytes in, commitment / proof / verdict out, the scalar-field work (inverse NTT of
+ * the blob's evaluations, aggregation, evaluation, quotient: lb_kzg_field.h) and the group work both
+ * on the GPU; only the Fiat-Shamir transcript is hashed on the host.  A blob is 4096 field
+ * elements of 32 big-endian bytes (131 072 bytes), its polynomial's values at the bit-reversed
+ * 4096th roots of unity.  Every call needs a loaded setup of exactly 4096 G1 points
+ * (LB_ERR_ARGUMENT otherwise); a blob element >= r is LB_BAD_SCALAR.  The semantics are those of
+ * lodestar_amd/kzg.py (the EIP-4844 spec of consensus-specs v1.3.0-alpha.2); byte parity with c-kzg
+ * is unpinned, as for the group calls.
+ *
+ * lb_kzg_blob_to_commitment (ckzg.blobToKzgCommitment) for n_blobs blobs: out48[b], and
+ * out_status[b] = LB_OK or LB_BAD_SCALAR (out48[b] is then zeroed); returns LB_OK when the call
+ * itself ran.
+ * lb_kzg_compute_proof: the proof that the blob's polynomial takes the value y at z (z32le, y32le:
+ * little-endian, z below r else LB_BAD_SCALAR); z on the evaluation domain is allowed.
+ * lb_kzg_compute_aggregate_proof (ckzg.computeAggregateKzgProof): commitments, challenges r and x
+ * from the transcript, the proof of sum r^j poly_j at x.  Zero blobs: the point at infinity.
+ * lb_kzg_verify_aggregate_proof (ckzg.verifyAggregateKzgProof): *ok = 1 / 0, or -code for a
+ * commitment or proof that fails to decode or lies outside G1.  Zero blobs still decode the proof
+ * (1 iff it is the point at infinity).
+ * lb_kzg_blob_coefficients: the blob's polynomial in monomial form, 4096 little-endian 32-byte
+ * coefficients (the scalars whose lb_g1_lincomb is the commitment).
+ */
+int32_t lb_kzg_blob_to_commitment(lb_engine* e, uint32_t n_blobs, const uint8_t* blobs, uint8_t* out48,
+                                  int32_t* out_status);
+int32_t lb_kzg_compute_proof(lb_engine* e, const uint8_t* blob, const uint8_t* z32le, uint8_t* out_proof48,
+                             uint8_t* out_y32le);
+int32_t lb_kzg_compute_aggregate_proof(lb_engine* e, uint32_t n_blobs, const uint8_t* blobs, uint8_t* out48);
+int32_t lb_kzg_verify_aggregate_proof(lb_engine* e, uint32_t n_blobs, const uint8_t* blobs,
+                                      const uint8_t* commitments48, const uint8_t* proof48, int32_t* ok);
+int32_t lb_kzg_blob_coefficients(lb_engine* e, const uint8_t* blob, uint8_t* out_coeffs32le /* 4096 x 32 */);
 
 /*
  * Synthetic-data helpers for tests and the benchmark (not on the verification path):

@@ -131,6 +131,23 @@ def build_comb_harness(force=False, verbose=True):
     return COMB_HARNESS
 
 
+FR_HARNESS = os.path.join(ROOT, "build", "lb_fr_harness.so")
+
+
+def build_fr_harness(force=False, verbose=True):
+    """the scalar field, its transform and the evaluate-and-divide scan on the CPU (tests/test_fr_cpu.py)"""
+    src = os.path.join(ROOT, "tests", "harness", "lb_fr_harness.cpp")
+    os.makedirs(os.path.dirname(FR_HARNESS), exist_ok=True)
+    if not force and not _stale(FR_HARNESS, _deps() + [src]):
+        return FR_HARNESS
+    cmd = ["g++", "-O2", "-shared", "-fPIC", "-I" + INC, "-I" + CSRC, src, "-o", FR_HARNESS + ".tmp"]
+    if verbose:
+        print("[build]", " ".join(cmd), flush=True)
+    subprocess.run(cmd, check=True)
+    os.replace(FR_HARNESS + ".tmp", FR_HARNESS)
+    return FR_HARNESS
+
+
 def build_cpu_pool(force=False, verbose=True):
     src = os.path.join(ROOT, "oracle", "cpu_pool.cpp")
     if not os.path.exists(src):
@@ -190,6 +207,7 @@ def build_all(force=False):
     build_napi(force)
     build_harness(force)
     build_comb_harness(force)
+    build_fr_harness(force)
     build_cpu_pool(force)
     build_ubench(force)
 

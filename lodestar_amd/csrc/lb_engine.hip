@@ -23,6 +23,7 @@
 
 #include "lb_kernels.h"
 #include "lb_kzg.h"
+#include "lb_kzg_field.h"
 #include "lb_kdecl.h"  // kernels of the other translation units (split build)
 
 #define LB_ABI_VERSION 1
@@ -237,6 +238,9 @@ struct lb_engine {
   // KZG trusted setup (lb_kzg_load_setup): [tau^i] G1 as g1a SoA (kzg_n entries), [tau^0,1] G2
   dbuf kzg_g1, kzg_g2;
   uint32_t kzg_n = 0;
+  // ... and the inverse transform's twiddles for the blob-level calls (lb_fr.h fr_intt_table(12):
+  // 2048 powers of the inverse root and 1 / 4096, Montgomery form), built on the host at load
+  dbuf kzg_tw;
   // profiling
   bool profiling = false;
   hipEvent_t ev0[kStages] = {}, ev1[kStages] = {};
@@ -585,7 +589,7 @@ void lb_engine_destroy(lb_engine* e) {
                   &e->gch, &e->chunk_beg, &e->chunk_end, &e->members, &e->set_live, &e->gacc, &e->gp_aff,
                   &e->gp_inf, &e->chunk_root, &e->sig_aos, &e->bcnt, &e->bcursor, &e->boff, &e->bch, &e->bchunk_beg,
                   &e->bchunk_end, &e->bmembers, &e->bacc, &e->bsum, &e->wsum, &e->park, &e->pk_aff, &e->y_root, &e->kzg_g1,
-                  &e->kzg_g2, &e->s_terms, &e->s_part, &e->s_root, &e->rs_idx, &e->s_set};
+                  &e->kzg_g2, &e->kzg_tw, &e->s_terms, &e->s_part, &e->s_root, &e->rs_idx, &e->s_set};
   for (dbuf* b : bufs) b->release();
   for (dbuf& b : e->sx) b.release();
   for (int i = 0; i < kStages; i++) {
@@ -2373,8 +2377,38 @@ extern "C" int32_t lb_kzg_load_setup(lb_engine* e, const uint8_t* g1_48, uint32_
       e->kzg_n = 0;
       return out_status[i];
     }
+  {
+    // the blob-level calls' inverse-transform table (lb_fr.h), computed here on the host
+    std::vector<fr> tw(LB_FR_TW_LEN);
+    fr_intt_table(tw.data(), LB_FR_LOGN);
+    std::lock_guard<std::mutex> lk(e->mu);
+    LB_HIP(hipSetDevice(e->device));
+    LB_HIP(e->kzg_tw.ensure(tw.size() * sizeof(fr)));
+    LB_HIP(hipMemcpyAsync(e->kzg_tw.p, tw.data(), tw.size() * sizeof(fr), hipMemcpyHostToDevice, e->stream));
+    LB_HIP(hipStreamSynchronize(e->stream));
+  }
   e->kzg_n = n_g1;
   return LB_OK;
+}
+
+// The launches of out48 = compress(sum_i s_i P_i) over device buffers: P_i = setup point i
+// (d_pts48 null) or n compressed points; d_scalars n x 8 LE words; d_terms n and d_part
+// ceil(n / 64) g1j (SoA); d_status n codes (LB_OK for setup points).  n >= 1.
+static void g1_lincomb_launch(lb_engine* e, uint32_t n, const uint8_t* d_pts48, const uint32_t* d_scalars,
+                              uint32_t* d_terms, uint32_t* d_part, int32_t* d_status, uint8_t* d_out48) {
+  hipLaunchKernelGGL(k_g1_terms, dim3(nblk(n)), dim3(LB_TPB), 0, e->stream, n, d_pts48, e->kzg_g1.as<uint32_t>(),
+                     e->kzg_n, d_scalars, d_terms, d_status);
+  // reduce 64:1 per level, ping-ponging between the term buffer and the partials buffer
+  uint32_t* bufs[2] = {d_terms, d_part};
+  uint32_t m = n;
+  int cur = 0;
+  while (m > 1) {
+    const uint32_t mo = (m + 63) / 64;
+    hipLaunchKernelGGL(k_g1_sum64, dim3(mo), dim3(64), 0, e->stream, m, bufs[cur], mo, bufs[cur ^ 1]);
+    m = mo;
+    cur ^= 1;
+  }
+  hipLaunchKernelGGL(k_g1_out48, dim3(1), dim3(64), 0, e->stream, bufs[cur], m, d_out48);
 }
 
 extern "C" int32_t lb_g1_lincomb(lb_engine* e, uint32_t n, const uint8_t* points48, const uint8_t* scalars32,
@@ -2386,8 +2420,6 @@ extern "C" int32_t lb_g1_lincomb(lb_engine* e, uint32_t n, const uint8_t* points
     out48[0] = 0xc0;
     return LB_OK;
   }
-  uint32_t levels = 0;
-  for (uint32_t m = n; m > 1; m = (m + 63) / 64) levels++;
   const uint32_t n1 = (n + 63) / 64;
   std::vector<int32_t> st(n, LB_OK);
   lb_engine* ee = e;
@@ -2396,20 +2428,8 @@ extern "C" int32_t lb_g1_lincomb(lb_engine* e, uint32_t n, const uint8_t* points
           {nullptr, (size_t)n * sizeof(g1j), true, nullptr}, {nullptr, (size_t)n1 * sizeof(g1j), true, nullptr},
           {nullptr, (size_t)n * 4, true, st.data()}, {nullptr, 48, true, out48}},
       [&](std::vector<void*>& p) {
-        hipLaunchKernelGGL(k_g1_terms, dim3(nblk(n)), dim3(LB_TPB), 0, ee->stream, n,
-                           points48 ? (const uint8_t*)p[0] : nullptr, ee->kzg_g1.as<uint32_t>(), ee->kzg_n,
-                           (const uint32_t*)p[1], (uint32_t*)p[2], (int32_t*)p[4]);
-        // reduce 64:1 per level, ping-ponging between the term buffer and the partials buffer
-        uint32_t* bufs[2] = {(uint32_t*)p[2], (uint32_t*)p[3]};
-        uint32_t m = n;
-        int cur = 0;
-        for (uint32_t l = 0; l < levels; l++) {
-          const uint32_t mo = (m + 63) / 64;
-          hipLaunchKernelGGL(k_g1_sum64, dim3(mo), dim3(64), 0, ee->stream, m, bufs[cur], mo, bufs[cur ^ 1]);
-          m = mo;
-          cur ^= 1;
-        }
-        hipLaunchKernelGGL(k_g1_out48, dim3(1), dim3(64), 0, ee->stream, bufs[cur], m, (uint8_t*)p[5]);
+        g1_lincomb_launch(ee, n, points48 ? (const uint8_t*)p[0] : nullptr, (const uint32_t*)p[1], (uint32_t*)p[2],
+                          (uint32_t*)p[3], (int32_t*)p[4], (uint8_t*)p[5]);
       });
   if (r != LB_OK) return r;
   for (uint32_t i = 0; i < n; i++)
@@ -2433,4 +2453,346 @@ extern "C" int32_t lb_kzg_verify_proof(lb_engine* e, const uint8_t* commitment48
                       hipLaunchKernelGGL(k_kzg_check, dim3(1), dim3(64), 0, ee->stream, (const uint8_t*)p[0],
                                          (const uint32_t*)p[1], ee->kzg_g2.as<uint32_t>(), (int32_t*)p[2]);
                     });
+}
+
+// ---------------------------------------------------------------- KZG, blob level (lb_kzg_field.h)
+namespace {
+// SHA-256 of the Fiat-Shamir transcript, streamed through lb_h2c.h's sha256_compress on the host
+struct sha_stream {
+  uint32_t h[8];
+  uint8_t buf[64];
+  size_t fill = 0;
+  uint64_t total = 0;
+  sha_stream() { sha256_init(h); }
+  void block(const uint8_t* b) {
+    uint32_t w[16];
+    for (int i = 0; i < 16; i++)
+      w[i] = ((uint32_t)b[4 * i] << 24) | ((uint32_t)b[4 * i + 1] << 16) | ((uint32_t)b[4 * i + 2] << 8) | b[4 * i + 3];
+    sha256_compress(h, w);
+  }
+  void update(const uint8_t* d, size_t n) {
+    total += n;
+    if (fill) {
+      const size_t k = std::min(n, sizeof(buf) - fill);
+      memcpy(buf + fill, d, k);
+      fill += k;
+      d += k;
+      n -= k;
+      if (fill < sizeof(buf)) return;
+      block(buf);
+      fill = 0;
+    }
+    for (; n >= 64; d += 64, n -= 64) block(d);
+    if (n) memcpy(buf, d, n);
+    fill = n;
+  }
+  void finish(uint8_t out[32]) {
+    const uint64_t bits = total * 8;
+    uint8_t pad[72] = {0x80};
+    const size_t padn = (fill < 56 ? 56 : 120) - fill;
+    uint8_t len[8];
+    for (int i = 0; i < 8; i++) len[i] = (uint8_t)(bits >> (56 - 8 * i));
+    update(pad, padn);
+    update(len, 8);
+    for (int i = 0; i < 8; i++)
+      for (int k = 0; k < 4; k++) out[4 * i + k] = (uint8_t)(h[i] >> (24 - 8 * k));
+  }
+};
+
+// hash_to_bls_field(h || tag): SHA-256, read as a big-endian integer, mod r (Montgomery form)
+fr kzg_hash_to_field(const uint8_t h[32], uint8_t tag) {
+  sha_stream s;
+  s.update(h, 32);
+  s.update(&tag, 1);
+  uint8_t d[32];
+  s.finish(d);
+  uint32_t w[8];
+  for (int k = 0; k < 8; k++)
+    w[k] = ((uint32_t)d[28 - 4 * k] << 24) | ((uint32_t)d[29 - 4 * k] << 16) | ((uint32_t)d[30 - 4 * k] << 8) | d[31 - 4 * k];
+  return fr_reduce256(w);
+}
+
+// compute_challenges (lodestar_amd/kzg.py): transcript = domain || 4096 and n as 8-byte BE || the
+// blobs' field elements (32-byte BE: a valid blob's own bytes) || the commitments;
+// r = H(h || 0), x = H(h || 1)
+void kzg_challenges(uint32_t n, const uint8_t* blobs, const uint8_t* commitments48, fr& r, fr& x) {
+  sha_stream s;
+  s.update(reinterpret_cast<const uint8_t*>("FSBLOBVERIFY_V1_"), 16);
+  uint8_t be[16] = {0};
+  be[6] = (uint8_t)(LB_FR_N >> 8);
+  be[7] = (uint8_t)LB_FR_N;
+  for (int i = 0; i < 4; i++) be[12 + i] = (uint8_t)(n >> (24 - 8 * i));
+  s.update(be, 16);
+  if (n) s.update(blobs, (size_t)n * LB_FR_N * 32);
+  if (n) s.update(commitments48, (size_t)n * 48);
+  uint8_t h[32];
+  s.finish(h);
+  r = kzg_hash_to_field(h, 0);
+  x = kzg_hash_to_field(h, 1);
+}
+
+constexpr size_t kBlobBytes = (size_t)LB_FR_N * 32;
+constexpr uint32_t kMaxBlobs = 1024;  // per call (the spec's MAX_BLOBS_PER_BLOCK is 4)
+
+// device workspace of one blob-level call, freed when it returns.  Field elements: 8 words each.
+struct kzg_ws {
+  dbuf blobs;   // n blobs as given
+  dbuf polys;   // ... as Montgomery Fr (k_fr_blob_load)
+  dbuf status;  // per-blob status
+  dbuf agg;     // sum r^j poly_j
+  dbuf coef;    // monomial coefficients, Montgomery (k_fr_eval_quotient's input)
+  dbuf le;      // scalars for k_g1_terms: n polynomials' coefficients, or one quotient
+  dbuf terms, part, tstatus;  // g1_lincomb_launch
+  dbuf pts;     // n x 48: commitments out (blob_to_commitment) or in (verify)
+  dbuf pw, pw_le;  // r^j, Montgomery and plain LE
+  dbuf z;       // evaluation point, Montgomery
+  dbuf io, yz;  // k_kzg_check's inputs: C || proof, y || z as LE words
+  std::vector<int32_t> h_status;
+  ~kzg_ws() {
+    for (dbuf* b : {&blobs, &polys, &status, &agg, &coef, &le, &terms, &part, &tstatus, &pts, &pw, &pw_le, &z, &io, &yz})
+      b->release();
+  }
+};
+
+#define LB_KZG_TRY(call)                                                                          \
+  do {                                                                                            \
+    hipError_t _e = (call);                                                                       \
+    if (_e != hipSuccess) {                                                                       \
+      fprintf(stderr, "lodestar_bls: %s failed: %s (%s:%d)\n", #call, hipGetErrorString(_e), __FILE__, __LINE__); \
+      return LB_ERR_DEVICE;                                                                       \
+    }                                                                                             \
+  } while (0)
+
+// upload n blobs and turn them into Montgomery Fr; h_status[b] = LB_OK / LB_BAD_SCALAR (synchronises).
+// Also sizes the buffers every call shares.  Caller holds e->mu.
+int32_t kzg_load_blobs(lb_engine* e, kzg_ws& w, uint32_t n, const uint8_t* blobs) {
+  LB_KZG_TRY(hipSetDevice(e->device));
+  LB_KZG_TRY(w.blobs.ensure(n * kBlobBytes));
+  LB_KZG_TRY(w.polys.ensure(n * kBlobBytes));
+  LB_KZG_TRY(w.status.ensure((size_t)n * 4));
+  LB_KZG_TRY(w.terms.ensure((size_t)LB_FR_N * sizeof(g1j)));
+  LB_KZG_TRY(w.part.ensure((size_t)(LB_FR_N / 64) * sizeof(g1j)));
+  LB_KZG_TRY(w.tstatus.ensure((size_t)LB_FR_N * 4));
+  LB_KZG_TRY(hipMemcpyAsync(w.blobs.p, blobs, n * kBlobBytes, hipMemcpyHostToDevice, e->stream));
+  LB_KZG_TRY(hipMemsetAsync(w.status.p, 0, (size_t)n * 4, e->stream));
+  const uint32_t n_elems = n * LB_FR_N;
+  hipLaunchKernelGGL(k_fr_blob_load, dim3((n_elems + 255) / 256), dim3(256), 0, e->stream, n_elems,
+                     w.blobs.as<uint8_t>(), w.polys.as<uint32_t>(), w.status.as<int32_t>());
+  LB_KZG_TRY(hipGetLastError());
+  w.h_status.assign(n, LB_OK);
+  LB_KZG_TRY(hipMemcpyAsync(w.h_status.data(), w.status.p, (size_t)n * 4, hipMemcpyDeviceToHost, e->stream));
+  LB_KZG_TRY(hipStreamSynchronize(e->stream));
+  return LB_OK;
+}
+
+// n_polys polynomials of evaluations -> coefficients (one workgroup each, the polynomial in LDS)
+int32_t kzg_intt(lb_engine* e, uint32_t n_polys, const uint32_t* in, uint32_t* out_mont, uint32_t* out_le) {
+  LB_KZG_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_fr_intt4096),
+                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)LB_FR_INTT_LDS));
+  hipLaunchKernelGGL(k_fr_intt4096, dim3(n_polys), dim3(LB_FR_WG), LB_FR_INTT_LDS, e->stream, in,
+                     e->kzg_tw.as<uint32_t>(), out_mont, out_le);
+  LB_KZG_TRY(hipGetLastError());
+  return LB_OK;
+}
+
+// commitments of the n loaded blobs -> w.pts (device, 48 B each): coefficients as LE scalars, one
+// 4096-term linear combination of the setup per blob
+int32_t kzg_commit(lb_engine* e, kzg_ws& w, uint32_t n) {
+  LB_KZG_TRY(w.le.ensure(n * kBlobBytes));
+  LB_KZG_TRY(w.pts.ensure((size_t)n * 48));
+  const int32_t rc = kzg_intt(e, n, w.polys.as<uint32_t>(), nullptr, w.le.as<uint32_t>());
+  if (rc != LB_OK) return rc;
+  for (uint32_t b = 0; b < n; b++)
+    g1_lincomb_launch(e, LB_FR_N, nullptr, w.le.as<uint32_t>() + (size_t)b * LB_FR_N * 8, w.terms.as<uint32_t>(),
+                      w.part.as<uint32_t>(), w.tstatus.as<int32_t>(), w.pts.as<uint8_t>() + (size_t)48 * b);
+  LB_KZG_TRY(hipGetLastError());
+  return LB_OK;
+}
+
+// evaluations `evals` (Montgomery, device) and the point z -> y = p(z) as LE words at d_y and the
+// quotient's scalars in w.le; if d_proof48, also the proof = commitment to the quotient
+int32_t kzg_open(lb_engine* e, kzg_ws& w, const uint32_t* evals, const fr& z, uint32_t* d_y, uint8_t* d_proof48) {
+  LB_KZG_TRY(w.coef.ensure(kBlobBytes));
+  LB_KZG_TRY(w.le.ensure(kBlobBytes));
+  LB_KZG_TRY(w.z.ensure(sizeof(fr)));
+  LB_KZG_TRY(hipMemcpyAsync(w.z.p, &z, sizeof(fr), hipMemcpyHostToDevice, e->stream));
+  const int32_t rc = kzg_intt(e, 1, evals, w.coef.as<uint32_t>(), nullptr);
+  if (rc != LB_OK) return rc;
+  hipLaunchKernelGGL(k_fr_eval_quotient, dim3(1), dim3(LB_FR_WG), LB_FR_EQ_LDS, e->stream, w.coef.as<uint32_t>(),
+                     w.z.as<uint32_t>(), w.le.as<uint32_t>(), d_y);
+  LB_KZG_TRY(hipGetLastError());
+  if (d_proof48) {
+    g1_lincomb_launch(e, LB_FR_N, nullptr, w.le.as<uint32_t>(), w.terms.as<uint32_t>(), w.part.as<uint32_t>(),
+                      w.tstatus.as<int32_t>(), d_proof48);
+    LB_KZG_TRY(hipGetLastError());
+  }
+  return LB_OK;
+}
+
+// sum_j r^j poly_j of the n loaded blobs -> w.agg; the powers also as LE scalars in w.pw_le
+int32_t kzg_aggregate(lb_engine* e, kzg_ws& w, uint32_t n, const fr& r) {
+  std::vector<fr> pw(n), pw_le(n);
+  fr p = fr_one();
+  for (uint32_t j = 0; j < n; j++) {
+    pw[j] = p;
+    fr_to_le_words(pw_le[j].l, p);
+    p = fr_mul(p, r);
+  }
+  LB_KZG_TRY(w.pw.ensure(n * sizeof(fr)));
+  LB_KZG_TRY(w.pw_le.ensure(n * sizeof(fr)));
+  LB_KZG_TRY(w.agg.ensure(kBlobBytes));
+  LB_KZG_TRY(hipMemcpyAsync(w.pw.p, pw.data(), n * sizeof(fr), hipMemcpyHostToDevice, e->stream));
+  LB_KZG_TRY(hipMemcpyAsync(w.pw_le.p, pw_le.data(), n * sizeof(fr), hipMemcpyHostToDevice, e->stream));
+  hipLaunchKernelGGL(k_fr_aggregate, dim3(LB_FR_N / 256), dim3(256), 0, e->stream, n, w.polys.as<uint32_t>(),
+                     w.pw.as<uint32_t>(), w.agg.as<uint32_t>());
+  LB_KZG_TRY(hipGetLastError());
+  // pageable uploads return once staged, but pw / pw_le die with this frame: be safe
+  LB_KZG_TRY(hipStreamSynchronize(e->stream));
+  return LB_OK;
+}
+
+bool kzg_ready(const lb_engine* e) { return e && e->kzg_n == LB_FR_N && e->kzg_tw.p; }
+}  // namespace
+
+extern "C" int32_t lb_kzg_blob_to_commitment(lb_engine* e, uint32_t n_blobs, const uint8_t* blobs, uint8_t* out48,
+                                             int32_t* out_status) {
+  if (!kzg_ready(e) || n_blobs > kMaxBlobs || (n_blobs && (!blobs || !out48 || !out_status))) return LB_ERR_ARGUMENT;
+  if (!n_blobs) return LB_OK;
+  std::lock_guard<std::mutex> lk(e->mu);
+  kzg_ws w;
+  int32_t rc = kzg_load_blobs(e, w, n_blobs, blobs);
+  if (rc == LB_OK) rc = kzg_commit(e, w, n_blobs);
+  if (rc != LB_OK) return rc;
+  LB_KZG_TRY(hipMemcpyAsync(out48, w.pts.p, (size_t)n_blobs * 48, hipMemcpyDeviceToHost, e->stream));
+  LB_KZG_TRY(hipStreamSynchronize(e->stream));
+  for (uint32_t b = 0; b < n_blobs; b++) {
+    out_status[b] = w.h_status[b];
+    if (w.h_status[b] != LB_OK) memset(out48 + (size_t)48 * b, 0, 48);
+  }
+  return LB_OK;
+}
+
+extern "C" int32_t lb_kzg_blob_coefficients(lb_engine* e, const uint8_t* blob, uint8_t* out_coeffs32le) {
+  if (!kzg_ready(e) || !blob || !out_coeffs32le) return LB_ERR_ARGUMENT;
+  std::lock_guard<std::mutex> lk(e->mu);
+  kzg_ws w;
+  int32_t rc = kzg_load_blobs(e, w, 1, blob);
+  if (rc != LB_OK) return rc;
+  if (w.h_status[0] != LB_OK) return w.h_status[0];
+  LB_KZG_TRY(w.le.ensure(kBlobBytes));
+  rc = kzg_intt(e, 1, w.polys.as<uint32_t>(), nullptr, w.le.as<uint32_t>());
+  if (rc != LB_OK) return rc;
+  LB_KZG_TRY(hipMemcpyAsync(out_coeffs32le, w.le.p, kBlobBytes, hipMemcpyDeviceToHost, e->stream));
+  LB_KZG_TRY(hipStreamSynchronize(e->stream));
+  return LB_OK;
+}
+
+extern "C" int32_t lb_kzg_compute_proof(lb_engine* e, const uint8_t* blob, const uint8_t* z32le, uint8_t* out_proof48,
+                                        uint8_t* out_y32le) {
+  if (!kzg_ready(e) || !blob || !z32le || !out_proof48 || !out_y32le) return LB_ERR_ARGUMENT;
+  fr zp;
+  for (int k = 0; k < 8; k++)
+    zp.l[k] = (uint32_t)z32le[4 * k] | ((uint32_t)z32le[4 * k + 1] << 8) | ((uint32_t)z32le[4 * k + 2] << 16) |
+              ((uint32_t)z32le[4 * k + 3] << 24);
+  if (!fr_lt_mod(zp)) return LB_BAD_SCALAR;
+  std::lock_guard<std::mutex> lk(e->mu);
+  kzg_ws w;
+  int32_t rc = kzg_load_blobs(e, w, 1, blob);
+  if (rc != LB_OK) return rc;
+  if (w.h_status[0] != LB_OK) return w.h_status[0];
+  LB_KZG_TRY(w.yz.ensure(64));
+  LB_KZG_TRY(w.io.ensure(96));
+  const fr z = fr_to_mont(zp);  // outlives the upload: the stream is synchronised below
+  rc = kzg_open(e, w, w.polys.as<uint32_t>(), z, w.yz.as<uint32_t>(), w.io.as<uint8_t>());
+  if (rc != LB_OK) return rc;
+  LB_KZG_TRY(hipMemcpyAsync(out_proof48, w.io.p, 48, hipMemcpyDeviceToHost, e->stream));
+  LB_KZG_TRY(hipMemcpyAsync(out_y32le, w.yz.p, 32, hipMemcpyDeviceToHost, e->stream));
+  LB_KZG_TRY(hipStreamSynchronize(e->stream));
+  return LB_OK;
+}
+
+extern "C" int32_t lb_kzg_compute_aggregate_proof(lb_engine* e, uint32_t n_blobs, const uint8_t* blobs, uint8_t* out48) {
+  if (!kzg_ready(e) || n_blobs > kMaxBlobs || !out48 || (n_blobs && !blobs)) return LB_ERR_ARGUMENT;
+  if (!n_blobs) {  // the zero polynomial's proof: infinity
+    memset(out48, 0, 48);
+    out48[0] = 0xc0;
+    return LB_OK;
+  }
+  std::lock_guard<std::mutex> lk(e->mu);
+  kzg_ws w;
+  int32_t rc = kzg_load_blobs(e, w, n_blobs, blobs);
+  if (rc != LB_OK) return rc;
+  for (uint32_t b = 0; b < n_blobs; b++)
+    if (w.h_status[b] != LB_OK) return w.h_status[b];
+  rc = kzg_commit(e, w, n_blobs);
+  if (rc != LB_OK) return rc;
+  std::vector<uint8_t> comms((size_t)n_blobs * 48);
+  LB_KZG_TRY(hipMemcpyAsync(comms.data(), w.pts.p, comms.size(), hipMemcpyDeviceToHost, e->stream));
+  LB_KZG_TRY(hipStreamSynchronize(e->stream));
+  fr r, x;
+  kzg_challenges(n_blobs, blobs, comms.data(), r, x);
+  rc = kzg_aggregate(e, w, n_blobs, r);
+  if (rc != LB_OK) return rc;
+  LB_KZG_TRY(w.yz.ensure(64));
+  LB_KZG_TRY(w.io.ensure(96));
+  rc = kzg_open(e, w, w.agg.as<uint32_t>(), x, w.yz.as<uint32_t>(), w.io.as<uint8_t>());
+  if (rc != LB_OK) return rc;
+  LB_KZG_TRY(hipMemcpyAsync(out48, w.io.p, 48, hipMemcpyDeviceToHost, e->stream));
+  LB_KZG_TRY(hipStreamSynchronize(e->stream));
+  return LB_OK;
+}
+
+extern "C" int32_t lb_kzg_verify_aggregate_proof(lb_engine* e, uint32_t n_blobs, const uint8_t* blobs,
+                                                 const uint8_t* commitments48, const uint8_t* proof48, int32_t* ok) {
+  if (!kzg_ready(e) || n_blobs > kMaxBlobs || !proof48 || !ok || (n_blobs && (!blobs || !commitments48)))
+    return LB_ERR_ARGUMENT;
+  std::lock_guard<std::mutex> lk(e->mu);
+  kzg_ws w;
+  LB_KZG_TRY(hipSetDevice(e->device));
+  LB_KZG_TRY(w.yz.ensure(64));
+  LB_KZG_TRY(w.io.ensure(96));
+  LB_KZG_TRY(w.status.ensure(4));
+  fr r, x;
+  if (!n_blobs) {
+    // aggregated commitment = infinity, y = 0: e(proof, [tau - x] G2) == 1 iff the proof is infinity
+    kzg_challenges(0, nullptr, nullptr, r, x);
+    uint8_t inf48[48] = {0xc0};
+    LB_KZG_TRY(hipMemcpyAsync(w.io.p, inf48, 48, hipMemcpyHostToDevice, e->stream));
+    LB_KZG_TRY(hipMemsetAsync(w.yz.p, 0, 32, e->stream));
+  } else {
+    int32_t rc = kzg_load_blobs(e, w, n_blobs, blobs);
+    if (rc != LB_OK) return rc;
+    for (uint32_t b = 0; b < n_blobs; b++)
+      if (w.h_status[b] != LB_OK) return w.h_status[b];
+    kzg_challenges(n_blobs, blobs, commitments48, r, x);
+    rc = kzg_aggregate(e, w, n_blobs, r);
+    if (rc != LB_OK) return rc;
+    // y = agg(x) (the quotient the scan also yields is not needed here)
+    rc = kzg_open(e, w, w.agg.as<uint32_t>(), x, w.yz.as<uint32_t>(), nullptr);
+    if (rc != LB_OK) return rc;
+    // C = sum r^j C_j; the commitments are curve- and subgroup-checked by k_g1_terms
+    LB_KZG_TRY(w.pts.ensure((size_t)n_blobs * 48));
+    LB_KZG_TRY(hipMemcpyAsync(w.pts.p, commitments48, (size_t)n_blobs * 48, hipMemcpyHostToDevice, e->stream));
+    g1_lincomb_launch(e, n_blobs, w.pts.as<uint8_t>(), w.pw_le.as<uint32_t>(), w.terms.as<uint32_t>(),
+                      w.part.as<uint32_t>(), w.tstatus.as<int32_t>(), w.io.as<uint8_t>());
+    LB_KZG_TRY(hipGetLastError());
+    std::vector<int32_t> tst(n_blobs, LB_OK);
+    LB_KZG_TRY(hipMemcpyAsync(tst.data(), w.tstatus.p, (size_t)n_blobs * 4, hipMemcpyDeviceToHost, e->stream));
+    LB_KZG_TRY(hipStreamSynchronize(e->stream));
+    for (uint32_t b = 0; b < n_blobs; b++)
+      if (tst[b] != LB_OK) {
+        *ok = -tst[b];
+        return LB_OK;
+      }
+  }
+  uint32_t x_le[8];
+  fr_to_le_words(x_le, x);
+  LB_KZG_TRY(hipMemcpyAsync(w.io.as<uint8_t>() + 48, proof48, 48, hipMemcpyHostToDevice, e->stream));
+  LB_KZG_TRY(hipMemcpyAsync(w.yz.as<uint8_t>() + 32, x_le, 32, hipMemcpyHostToDevice, e->stream));
+  hipLaunchKernelGGL(k_kzg_check, dim3(1), dim3(64), 0, e->stream, w.io.as<uint8_t>(), w.yz.as<uint32_t>(),
+                     e->kzg_g2.as<uint32_t>(), w.status.as<int32_t>());
+  LB_KZG_TRY(hipGetLastError());
+  LB_KZG_TRY(hipMemcpyAsync(ok, w.status.p, 4, hipMemcpyDeviceToHost, e->stream));
+  LB_KZG_TRY(hipStreamSynchronize(e->stream));
+  return LB_OK;
 }

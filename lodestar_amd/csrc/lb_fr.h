@@ -1,0 +1,281 @@
+// The BLS12-381 scalar field Fr (r = 0x73eda753 299d7d48 3339d808 09a1d805 53bda402 fffe5bfe
+// ffffffff 00000001, the G1 subgroup order): the field of KZG blob elements, polynomial
+// coefficients and Fiat-Shamir challenges.  LB_HD like the rest of the arithmetic, so the same
+// source runs in the gfx950 kernels (lb_kzg_field.h), in lb_engine.hip's host code (twiddle
+// table, challenges) and in the CPU harness (tests/harness/lb_fr_harness.cpp).
+//
+// Representation: Montgomery form with R = 2^256, eight 32-bit limbs, little endian.  Products are
+// CIOS over (uint64_t)a * b + c + d, which the device compiles to v_mad_u64_u32.  r < 2^255, so
+// a product of two values below r is below 2 r before its one conditional subtraction.
+//
+// The transform (fr_ntt_*) and the evaluate-and-divide scan (fr_eq_*) are written per lane over
+// an accessor, with the barriers left to the caller: a kernel runs one call per thread between
+// __syncthreads(), the CPU harness loops over the lanes between the phases.
+#pragma once
+#include "lb_common.h"
+
+struct fr {
+  uint32_t l[8];
+};
+
+#define LB_FR_MOD_WORDS \
+  { 0x00000001u, 0xffffffffu, 0xfffe5bfeu, 0x53bda402u, 0x09a1d805u, 0x3339d808u, 0x299d7d48u, 0x73eda753u }
+// 2^256 mod r (Montgomery one) and 2^512 mod r
+#define LB_FR_ONE_WORDS \
+  { 0xfffffffeu, 0x00000001u, 0x00034802u, 0x5884b7fau, 0xecbc4ff5u, 0x998c4fefu, 0xacc5056fu, 0x1824b159u }
+#define LB_FR_R2_WORDS \
+  { 0xf3f29c6du, 0xc999e990u, 0x87925c23u, 0x2b6cedcbu, 0x7254398fu, 0x05d31496u, 0x9f59ff11u, 0x0748d9d9u }
+// 7^((r - 1) / 4096): the primitive 4096th root of unity of the blob domain (plain form)
+#define LB_FR_ROOT4096_WORDS \
+  { 0xa5d36306u, 0xe206da11u, 0x378fbf96u, 0x0ad1347bu, 0xe0f8245fu, 0xfc3e8acfu, 0xa0f704f4u, 0x564c0a11u }
+// -r^-1 mod 2^32 (r = 1 mod 2^32)
+#define LB_FR_N0 0xffffffffu
+
+LB_HD fr fr_zero() {
+  fr z;
+  LB_UNROLL for (int i = 0; i < 8; i++) z.l[i] = 0;
+  return z;
+}
+LB_HD fr fr_from_words(const uint32_t w[8]) {
+  fr a;
+  LB_UNROLL for (int i = 0; i < 8; i++) a.l[i] = w[i];
+  return a;
+}
+LB_HD fr fr_one() {
+  const uint32_t w[8] = LB_FR_ONE_WORDS;
+  return fr_from_words(w);
+}
+LB_HD bool fr_is_zero(const fr& a) {
+  uint32_t o = 0;
+  LB_UNROLL for (int i = 0; i < 8; i++) o |= a.l[i];
+  return o == 0;
+}
+LB_HD bool fr_eq(const fr& a, const fr& b) {
+  uint32_t o = 0;
+  LB_UNROLL for (int i = 0; i < 8; i++) o |= a.l[i] ^ b.l[i];
+  return o == 0;
+}
+
+// a - r if that is >= 0 (or `carry` says a stands for a + 2^256), else a
+LB_HD fr fr_csub(const fr& a, uint32_t carry) {
+  const uint32_t m[8] = LB_FR_MOD_WORDS;
+  fr d;
+  uint32_t bw = 0;
+  LB_UNROLL for (int i = 0; i < 8; i++) d.l[i] = LB_SUBC(a.l[i], m[i], bw, &bw);
+  const bool take = carry != 0 || bw == 0;
+  fr o;
+  LB_UNROLL for (int i = 0; i < 8; i++) o.l[i] = take ? d.l[i] : a.l[i];
+  return o;
+}
+// a plain 256-bit value below r?
+LB_HD bool fr_lt_mod(const fr& a) {
+  const uint32_t m[8] = LB_FR_MOD_WORDS;
+  uint32_t bw = 0;
+  LB_UNROLL for (int i = 0; i < 8; i++) (void)LB_SUBC(a.l[i], m[i], bw, &bw);
+  return bw != 0;
+}
+
+LB_HD fr fr_add(const fr& a, const fr& b) {
+  fr s;
+  uint32_t c = 0;
+  LB_UNROLL for (int i = 0; i < 8; i++) s.l[i] = LB_ADDC(a.l[i], b.l[i], c, &c);
+  return fr_csub(s, c);  // a + b < 2 r < 2^256: c is 0, kept for inputs that are not reduced
+}
+LB_HD fr fr_sub(const fr& a, const fr& b) {
+  const uint32_t m[8] = LB_FR_MOD_WORDS;
+  fr d;
+  uint32_t bw = 0;
+  LB_UNROLL for (int i = 0; i < 8; i++) d.l[i] = LB_SUBC(a.l[i], b.l[i], bw, &bw);
+  const uint32_t mask = 0u - bw;
+  uint32_t c = 0;
+  LB_UNROLL for (int i = 0; i < 8; i++) d.l[i] = LB_ADDC(d.l[i], m[i] & mask, c, &c);
+  return d;
+}
+LB_HD fr fr_neg(const fr& a) { return fr_sub(fr_zero(), a); }
+
+// Montgomery product a b / 2^256 mod r (CIOS, one 32-bit limb of b per round)
+LB_HD fr fr_mul(const fr& a, const fr& b) {
+  const uint32_t m[8] = LB_FR_MOD_WORDS;
+  uint32_t t[10];
+  LB_UNROLL for (int i = 0; i < 10; i++) t[i] = 0;
+  LB_UNROLL for (int i = 0; i < 8; i++) {
+    uint64_t uv;
+    uint32_t c = 0;
+    LB_UNROLL for (int j = 0; j < 8; j++) {
+      uv = (uint64_t)a.l[j] * b.l[i] + t[j] + c;
+      t[j] = (uint32_t)uv;
+      c = (uint32_t)(uv >> 32);
+    }
+    uv = (uint64_t)t[8] + c;
+    t[8] = (uint32_t)uv;
+    t[9] = (uint32_t)(uv >> 32);
+    const uint32_t q = t[0] * LB_FR_N0;
+    uv = (uint64_t)q * m[0] + t[0];
+    c = (uint32_t)(uv >> 32);
+    LB_UNROLL for (int j = 1; j < 8; j++) {
+      uv = (uint64_t)q * m[j] + t[j] + c;
+      t[j - 1] = (uint32_t)uv;
+      c = (uint32_t)(uv >> 32);
+    }
+    uv = (uint64_t)t[8] + c;
+    t[7] = (uint32_t)uv;
+    t[8] = t[9] + (uint32_t)(uv >> 32);
+  }
+  fr o;
+  LB_UNROLL for (int i = 0; i < 8; i++) o.l[i] = t[i];
+  return fr_csub(o, t[8]);
+}
+LB_HD fr fr_sqr(const fr& a) { return fr_mul(a, a); }
+
+LB_HD fr fr_to_mont(const fr& plain) {
+  const uint32_t r2[8] = LB_FR_R2_WORDS;
+  return fr_mul(plain, fr_from_words(r2));
+}
+LB_HD fr fr_from_mont(const fr& a) {
+  fr one = fr_zero();
+  one.l[0] = 1;
+  return fr_mul(a, one);
+}
+// Montgomery form of a small integer
+LB_HD fr fr_from_u32(uint32_t v) {
+  fr p = fr_zero();
+  p.l[0] = v;
+  return fr_to_mont(p);
+}
+
+// a^e, e = 8 little-endian words (plain integer); a and the result in Montgomery form
+LB_HD fr fr_pow(const fr& a, const uint32_t e[8]) {
+  fr acc = fr_one();
+  for (int i = 255; i >= 0; i--) {
+    acc = fr_sqr(acc);
+    if ((e[i >> 5] >> (i & 31)) & 1) acc = fr_mul(acc, a);
+  }
+  return acc;
+}
+// a^(r - 2): the inverse (0 -> 0).  Fermat; nothing hot inverts.
+LB_HD fr fr_inv(const fr& a) {
+  const uint32_t m[8] = LB_FR_MOD_WORDS;
+  uint32_t e[8], bw = 0;
+  LB_UNROLL for (int i = 0; i < 8; i++) e[i] = LB_SUBC(m[i], i == 0 ? 2u : 0u, bw, &bw);
+  return fr_pow(a, e);
+}
+
+// 32 big-endian bytes -> Montgomery form; false if the value is >= r (out is then the value
+// reduced, still a field element: callers report the element, nothing downstream misbehaves)
+template <class B>
+LB_HD bool fr_from_be32(fr& out, const B* b) {
+  fr p;
+  LB_UNROLL for (int w = 0; w < 8; w++) {
+    const int o = 28 - 4 * w;
+    p.l[w] = ((uint32_t)b[o] << 24) | ((uint32_t)b[o + 1] << 16) | ((uint32_t)b[o + 2] << 8) | (uint32_t)b[o + 3];
+  }
+  const bool ok = fr_lt_mod(p);
+  out = fr_to_mont(p);  // fr_mul takes any 256-bit operand beside one below r
+  return ok;
+}
+// the plain value as 8 little-endian words: the scalar layout k_g1_terms reads
+LB_HD void fr_to_le_words(uint32_t out[8], const fr& a) {
+  const fr p = fr_from_mont(a);
+  LB_UNROLL for (int i = 0; i < 8; i++) out[i] = p.l[i];
+}
+// any 256-bit value (8 LE words) mod r -> Montgomery form.  2^256 < 3 r: two subtractions at most
+// (hash_to_bls_field: a SHA-256 digest read as an integer)
+LB_HD fr fr_reduce256(const uint32_t w[8]) {
+  fr p = fr_from_words(w);
+  p = fr_csub(p, 0);
+  p = fr_csub(p, 0);
+  return fr_to_mont(p);
+}
+
+// ------------------------------------------------------------------ radix-2 transform
+// The in-order transform of lodestar_amd/kzg.py _ntt over n = 2^logn elements:
+//   out[k] = sum_j a[j] w^(j k),  tw(k) = w^k for k < n / 2 (Montgomery form).
+// `A` is an accessor with fr ld(uint32_t i) and void st(uint32_t i, const fr&): a flat array on
+// the CPU, limb-major LDS in k_fr_intt4096.  Lane `tid` of `nthr` does its share of each phase;
+// the caller puts a barrier between phases:
+//   fr_ntt_bitrev;  barrier;  for s in 0 .. logn - 1: fr_ntt_stage(s);  barrier.
+// The inverse transform is the same with tw(k) = w^-k and a final scaling by 1 / n.  The
+// evaluations of a blob stand at the BIT-REVERSED roots, so for them fr_ntt_bitrev is skipped:
+// un-reversing the input and the transform's own reversal cancel.
+LB_HD uint32_t fr_bitrev(uint32_t i, int logn) {
+  uint32_t r = 0;
+  for (int b = 0; b < logn; b++) r |= ((i >> b) & 1u) << (logn - 1 - b);
+  return r;
+}
+template <class A>
+LB_HD void fr_ntt_bitrev(A& a, int logn, uint32_t tid, uint32_t nthr) {
+  const uint32_t n = 1u << logn;
+  for (uint32_t i = tid; i < n; i += nthr) {
+    const uint32_t j = fr_bitrev(i, logn);
+    if (i < j) {
+      const fr x = a.ld(i), y = a.ld(j);
+      a.st(i, y);
+      a.st(j, x);
+    }
+  }
+}
+// stage s: butterflies of span m = 2^s; butterfly b pairs s0 + j and s0 + j + m with
+// j = b mod m, s0 = 2 m (b div m), twiddle w^(j n / 2m)
+template <class A, class T>
+LB_HD void fr_ntt_stage(A& a, int logn, int s, const T& tw, uint32_t tid, uint32_t nthr) {
+  const uint32_t half = 1u << (logn - 1), m = 1u << s;
+  for (uint32_t b = tid; b < half; b += nthr) {
+    const uint32_t j = b & (m - 1), lo = ((b >> s) << (s + 1)) + j, hi = lo + m;
+    const fr u = a.ld(lo), v = fr_mul(a.ld(hi), tw(j << (logn - 1 - s)));
+    a.st(lo, fr_add(u, v));
+    a.st(hi, fr_sub(u, v));
+  }
+}
+// The inverse transform's table over the blob domain's subgroup of order n = 2^logn <= 4096:
+// tw[k] = w_n^-k for k < n / 2 with w_n = 7^((r - 1) / n), and tw[n / 2] = 1 / n (n / 2 + 1 entries)
+#define LB_FR_INTT_TABLE_LEN(logn) ((1u << ((logn)-1)) + 1u)
+LB_HD void fr_intt_table(fr* tw, int logn) {
+  const uint32_t rw[8] = LB_FR_ROOT4096_WORDS;
+  fr w = fr_to_mont(fr_from_words(rw));
+  for (int i = logn; i < 12; i++) w = fr_sqr(w);
+  const fr winv = fr_inv(w);
+  const uint32_t half = 1u << (logn - 1);
+  tw[0] = fr_one();
+  for (uint32_t k = 1; k < half; k++) tw[k] = fr_mul(tw[k - 1], winv);
+  tw[half] = fr_inv(fr_from_u32(1u << logn));
+}
+
+// ------------------------------------------------------------------ evaluate and divide
+// For coefficients a[0 .. n - 1] and a point z: the suffix sums S[k] = sum_{j >= k} a[j] z^(j - k)
+// (S[k] = a[k] + z S[k + 1]), which are at once the value y = p(z) = S[0] and the quotient
+// (p(X) - y) / (X - z) = sum_k S[k + 1] X^k.  No division: z on the evaluation domain is no
+// special case.  n / 4 lanes; lane t owns a[4 t .. 4 t + 3]:
+//   fr_eq_local   T[t] = its four coefficients by Horner = S restricted to its own chunk
+//   fr_eq_scan    log2(n / 4) steps d = 1, 2, 4, ...: dst[t] = src[t] + z^(4 d) src[t + d]; after
+//                 the last one T[t] = S[4 t].  src and dst are distinct buffers of n / 4 values,
+//                 barrier between steps, w = z^(4 d) (fr_eq_weight, squared by the caller per step)
+//   fr_eq_finish  S[4 t + 3 .. 4 t] from T[t + 1], written as plain LE words: q[k - 1] = S[k]
+//                 (q has n entries; q[n - 1] = 0), y = S[0]
+template <class A>
+LB_HD fr fr_eq_local(const A& a, const fr& z, uint32_t t) {
+  fr acc = a.ld(4 * t + 3);
+  LB_UNROLL for (int k = 2; k >= 0; k--) acc = fr_add(fr_mul(acc, z), a.ld(4 * t + k));
+  return acc;
+}
+LB_HD fr fr_eq_weight(const fr& z) { return fr_sqr(fr_sqr(z)); }  // z^4: the weight of step d = 1
+LB_HD fr fr_eq_scan(const fr* src, uint32_t lanes, uint32_t d, const fr& w, uint32_t t) {
+  fr v = src[t];
+  if (t + d < lanes) v = fr_add(v, fr_mul(w, src[t + d]));
+  return v;
+}
+template <class A>
+LB_HD void fr_eq_finish(const A& a, const fr& z, const fr* T, uint32_t lanes, uint32_t t, uint32_t* q_le,
+                        uint32_t* y_le) {
+  fr s = t + 1 < lanes ? T[t + 1] : fr_zero();
+  LB_UNROLL for (int k = 3; k >= 0; k--) {
+    s = fr_add(fr_mul(s, z), a.ld(4 * t + k));  // S[4 t + k]
+    const uint32_t idx = 4 * t + k;
+    if (idx > 0)
+      fr_to_le_words(q_le + (size_t)8 * (idx - 1), s);
+    else
+      fr_to_le_words(y_le, s);
+  }
+  if (t + 1 == lanes) {
+    LB_UNROLL for (int w = 0; w < 8; w++) q_le[(size_t)8 * (4 * lanes - 1) + w] = 0;
+  }
+}

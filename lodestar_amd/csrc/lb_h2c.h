@@ -7,15 +7,26 @@
 #include "lb_curve.h"
 
 // ------------------------------------------------------------------ SHA-256
-LB_CONST uint32_t LB_SHA_K[64] = {
-    0x428a2f98, 0x71374491, 0xb5c0fbcf, 0xe9b5dba5, 0x3956c25b, 0x59f111f1, 0x923f82a4, 0xab1c5ed5,
-    0xd807aa98, 0x12835b01, 0x243185be, 0x550c7dc3, 0x72be5d74, 0x80deb1fe, 0x9bdc06a7, 0xc19bf174,
-    0xe49b69c1, 0xefbe4786, 0x0fc19dc6, 0x240ca1cc, 0x2de92c6f, 0x4a7484aa, 0x5cb0a9dc, 0x76f988da,
-    0x983e5152, 0xa831c66d, 0xb00327c8, 0xbf597fc7, 0xc6e00bf3, 0xd5a79147, 0x06ca6351, 0x14292967,
-    0x27b70a85, 0x2e1b2138, 0x4d2c6dfc, 0x53380d13, 0x650a7354, 0x766a0abb, 0x81c2c92e, 0x92722c85,
-    0xa2bfe8a1, 0xa81a664b, 0xc24b8b70, 0xc76c51a3, 0xd192e819, 0xd6990624, 0xf40e3585, 0x106aa070,
-    0x19a4c116, 0x1e376c08, 0x2748774c, 0x34b0bcb5, 0x391c0cb3, 0x4ed8aa4a, 0x5b9cca4f, 0x682e6ff3,
-    0x748f82ee, 0x78a5636f, 0x84c87814, 0x8cc70208, 0x90befffa, 0xa4506ceb, 0xbef9a3f7, 0xc67178f2};
+#define LB_SHA_K_WORDS                                                                                  \
+  {                                                                                                     \
+      0x428a2f98, 0x71374491, 0xb5c0fbcf, 0xe9b5dba5, 0x3956c25b, 0x59f111f1, 0x923f82a4, 0xab1c5ed5,   \
+      0xd807aa98, 0x12835b01, 0x243185be, 0x550c7dc3, 0x72be5d74, 0x80deb1fe, 0x9bdc06a7, 0xc19bf174,   \
+      0xe49b69c1, 0xefbe4786, 0x0fc19dc6, 0x240ca1cc, 0x2de92c6f, 0x4a7484aa, 0x5cb0a9dc, 0x76f988da,   \
+      0x983e5152, 0xa831c66d, 0xb00327c8, 0xbf597fc7, 0xc6e00bf3, 0xd5a79147, 0x06ca6351, 0x14292967,   \
+      0x27b70a85, 0x2e1b2138, 0x4d2c6dfc, 0x53380d13, 0x650a7354, 0x766a0abb, 0x81c2c92e, 0x92722c85,   \
+      0xa2bfe8a1, 0xa81a664b, 0xc24b8b70, 0xc76c51a3, 0xd192e819, 0xd6990624, 0xf40e3585, 0x106aa070,   \
+      0x19a4c116, 0x1e376c08, 0x2748774c, 0x34b0bcb5, 0x391c0cb3, 0x4ed8aa4a, 0x5b9cca4f, 0x682e6ff3,   \
+      0x748f82ee, 0x78a5636f, 0x84c87814, 0x8cc70208, 0x90befffa, 0xa4506ceb, 0xbef9a3f7, 0xc67178f2    \
+  }
+LB_CONST uint32_t LB_SHA_K[64] = LB_SHA_K_WORDS;
+// hipcc's host pass: a __constant__ array has no value on the host, so host callers of
+// sha256_compress (lb_engine.hip's KZG transcript hash) read a plain copy
+#if defined(__HIPCC__) && !defined(__HIP_DEVICE_COMPILE__)
+static const uint32_t LB_SHA_K_HOST[64] = LB_SHA_K_WORDS;
+#define LB_SHA_K_AT(i) LB_SHA_K_HOST[i]
+#else
+#define LB_SHA_K_AT(i) LB_SHA_K[i]
+#endif
 
 LB_HD uint32_t lb_rotr(uint32_t x, int n) { return (x >> n) | (x << (32 - n)); }
 
@@ -37,7 +48,7 @@ LB_NI void sha256_compress(uint32_t h[8], const uint32_t blk[16]) {
     }
     uint32_t S1 = lb_rotr(e, 6) ^ lb_rotr(e, 11) ^ lb_rotr(e, 25);
     uint32_t ch = (e & f) ^ (~e & g);
-    uint32_t t1 = hh + S1 + ch + LB_SHA_K[i] + wi;
+    uint32_t t1 = hh + S1 + ch + LB_SHA_K_AT(i) + wi;
     uint32_t S0 = lb_rotr(a, 2) ^ lb_rotr(a, 13) ^ lb_rotr(a, 22);
     uint32_t mj = (a & b) ^ (a & c) ^ (b & c);
     uint32_t t2 = S0 + mj;

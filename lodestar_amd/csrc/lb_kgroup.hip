@@ -3,4 +3,5 @@
 #define LB_KDECL_INSTANTIATE
 #include "lb_kernels.h"
 #include "lb_kzg.h"
+#include "lb_kzg_field.h"
 #include "lb_kdecl.h"

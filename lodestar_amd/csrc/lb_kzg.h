@@ -3,8 +3,11 @@
 // The GPU does the group work: G1 linear combinations of the resident trusted setup (a 4 096-term
 // multi-scalar multiplication per commitment or proof) or of given points (the aggregated
 // commitment), and the proof check as one two-pair pairing product.  The scalar-field work
-// (inverse FFT, Fiat-Shamir challenges, evaluations, quotients) is host code
-// (lodestar_amd/kzg.py).
+// (inverse FFT, aggregation, evaluations, quotients) is either the caller's (lodestar_amd/kzg.py
+// and js/kzg.js with field = "host", over lb_g1_lincomb / lb_kzg_verify_proof) or the GPU's too:
+// the k_fr_* kernels of lb_kzg_field.h behind the blob-level calls (lb_kzg_blob_to_commitment,
+// lb_kzg_compute_aggregate_proof, lb_kzg_verify_aggregate_proof ...), which feed the kernels below
+// from device memory.  The Fiat-Shamir transcript is hashed on the host either way.
 //
 // Setup layout: the monomial-form points [tau^i] G1 (what Lodestar's trusted_setup.bin holds; a
 // commitment to p(X) = sum a_i X^i is sum a_i [tau^i] G1, the same point as the spec's Lagrange

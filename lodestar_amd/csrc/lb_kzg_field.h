@@ -1,0 +1,140 @@
+// KZG scalar-field work on the GPU (lb_fr.h): a blob's 4096 big-endian field elements become
+// Montgomery Fr in device memory, are aggregated over the blobs (sum r^j poly_j), transformed to
+// monomial coefficients (inverse NTT), evaluated at a challenge and divided by (X - z), and leave
+// as the plain little-endian scalars k_g1_terms reads -- so between the blob's bytes and the
+// 48-byte commitment or proof nothing travels back to the host (lb_engine.hip lb_kzg_blob_*,
+// lb_kzg_compute_*, lb_kzg_verify_aggregate_proof).  Field elements in device buffers are 8 words
+// each, array of structures.
+#pragma once
+#include "lb_fr.h"
+#include "lb_kernels.h"
+
+#define LB_FR_N 4096u        // FIELD_ELEMENTS_PER_BLOB
+#define LB_FR_LOGN 12
+#define LB_FR_WG 1024        // lanes of the one-workgroup kernels: 4 elements / 2 butterflies each
+#define LB_FR_TW_LEN LB_FR_INTT_TABLE_LEN(LB_FR_LOGN)  // 2048 twiddles + 1 / 4096
+#define LB_FR_INTT_LDS (LB_FR_N * 32u)                  // 131 072 B of gfx950's 163 840 per workgroup
+#define LB_FR_EQ_LDS (2u * (LB_FR_N / 4) * 32u)         // two scan buffers of 1024 values
+
+__device__ __forceinline__ fr fr_ldg(const uint32_t* __restrict__ p) {
+  const uint4 a = reinterpret_cast<const uint4*>(p)[0], b = reinterpret_cast<const uint4*>(p)[1];
+  return fr{{a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w}};
+}
+__device__ __forceinline__ void fr_stg(uint32_t* __restrict__ p, const fr& v) {
+  reinterpret_cast<uint4*>(p)[0] = make_uint4(v.l[0], v.l[1], v.l[2], v.l[3]);
+  reinterpret_cast<uint4*>(p)[1] = make_uint4(v.l[4], v.l[5], v.l[6], v.l[7]);
+}
+// a polynomial in global memory
+struct fr_gpoly {
+  const uint32_t* p;
+  __device__ __forceinline__ fr ld(uint32_t i) const { return fr_ldg(p + (size_t)8 * i); }
+};
+struct fr_gtable {
+  const uint32_t* p;
+  __device__ __forceinline__ fr operator()(uint32_t k) const { return fr_ldg(p + (size_t)8 * k); }
+};
+// a 4096-element polynomial in LDS, limb-major: word w of element i at w * 4096 + i.  A wave's 64
+// lanes touch 64 consecutive elements (or a stride-2^k comb of them in the first six stages), one
+// dword each per access: consecutive banks, where 32-byte elements side by side would put every
+// eighth lane on the same bank (8-way conflict).
+struct fr_lds_poly {
+  uint32_t* w;
+  __device__ __forceinline__ fr ld(uint32_t i) const {
+    fr v;
+    LB_UNROLL for (int k = 0; k < 8; k++) v.l[k] = w[k * LB_FR_N + i];
+    return v;
+  }
+  __device__ __forceinline__ void st(uint32_t i, const fr& v) {
+    LB_UNROLL for (int k = 0; k < 8; k++) w[k * LB_FR_N + i] = v.l[k];
+  }
+};
+
+// blobs (n_blobs x 4096 x 32 bytes, big endian) -> Montgomery Fr; status[b] = LB_BAD_SCALAR if
+// blob b holds an element >= r (status zeroed by the caller; the lanes that find one all store
+// the same code, so the plain stores need no ordering)
+#if LB_KG(16)
+__global__ void __launch_bounds__(256) k_fr_blob_load(uint32_t n_elems, const uint8_t* __restrict__ blobs,
+                                                      uint32_t* __restrict__ out, int32_t* __restrict__ status) {
+  const uint32_t i = lb_tid();
+  if (i >= n_elems) return;
+  uint8_t b[32];
+  ld_bytes<32>(b, blobs + (size_t)32 * i);
+  fr v;
+  const bool ok = fr_from_be32(v, b);
+  fr_stg(out + (size_t)8 * i, v);
+  if (!ok) status[i / LB_FR_N] = LB_BAD_SCALAR;
+}
+#endif  // LB_KG
+
+// agg[i] = sum_j pw[j] polys[j][i] over n_blobs polynomials of 4096 elements
+#if LB_KG(16)
+__global__ void __launch_bounds__(256) k_fr_aggregate(uint32_t n_blobs, const uint32_t* __restrict__ polys,
+                                                      const uint32_t* __restrict__ pw, uint32_t* __restrict__ agg) {
+  const uint32_t i = lb_tid();
+  if (i >= LB_FR_N) return;
+  fr acc = fr_zero();
+  for (uint32_t j = 0; j < n_blobs; j++)
+    acc = fr_add(acc, fr_mul(fr_ldg(pw + (size_t)8 * j), fr_ldg(polys + ((size_t)j * LB_FR_N + i) * 8)));
+  fr_stg(agg + (size_t)8 * i, acc);
+}
+#endif  // LB_KG
+
+// One workgroup per polynomial: its 4096 evaluations at the bit-reversed roots of unity -> monomial
+// coefficients.  The transform's input reversal and the evaluations' own bit-reversed order cancel
+// (lb_fr.h), so the twelve butterfly stages run on the values as they stand, in LDS, then every
+// coefficient is scaled by 1 / 4096.  tw = fr_intt_table(12) (lb_kzg_load_setup).  out_mont /
+// out_le (either may be null): Montgomery form for k_fr_eval_quotient, plain LE words for
+// k_g1_terms.  LB_FR_INTT_LDS bytes of dynamic LDS.
+#if LB_KG(16)
+__global__ void __launch_bounds__(LB_FR_WG) k_fr_intt4096(const uint32_t* __restrict__ in, const uint32_t* __restrict__ tw,
+                                                          uint32_t* __restrict__ out_mont, uint32_t* __restrict__ out_le) {
+  extern __shared__ uint32_t lb_fr_lds[];
+  const size_t base = (size_t)blockIdx.x * LB_FR_N * 8;
+  fr_lds_poly A{lb_fr_lds};
+  const fr_gtable T{tw};
+  for (uint32_t i = threadIdx.x; i < LB_FR_N; i += LB_FR_WG) A.st(i, fr_ldg(in + base + (size_t)8 * i));
+  __syncthreads();
+  for (int s = 0; s < LB_FR_LOGN; s++) {
+    fr_ntt_stage(A, LB_FR_LOGN, s, T, threadIdx.x, LB_FR_WG);
+    __syncthreads();
+  }
+  const fr inv_n = T(LB_FR_N / 2);
+  for (uint32_t i = threadIdx.x; i < LB_FR_N; i += LB_FR_WG) {
+    const fr c = fr_mul(A.ld(i), inv_n);
+    if (out_mont) fr_stg(out_mont + base + (size_t)8 * i, c);
+    if (out_le) {
+      uint32_t w[8];
+      fr_to_le_words(w, c);
+      fr_stg(out_le + base + (size_t)8 * i, fr_from_words(w));
+    }
+  }
+}
+#endif  // LB_KG
+
+// y = p(z) and q = (p - y) / (X - z) for the 4096 coefficients `a` (Montgomery) and the point *z
+// (Montgomery): lb_fr.h fr_eq_*, lane t owning a[4 t .. 4 t + 3], the ten scan steps ping-ponging
+// between two LDS buffers.  q_le: 4096 scalars (plain LE words, q[4095] = 0), y_le: 8 words.
+// One workgroup; LB_FR_EQ_LDS bytes of dynamic LDS.
+#if LB_KG(16)
+__global__ void __launch_bounds__(LB_FR_WG) k_fr_eval_quotient(const uint32_t* __restrict__ a, const uint32_t* __restrict__ z_mont,
+                                                               uint32_t* __restrict__ q_le, uint32_t* __restrict__ y_le) {
+  extern __shared__ uint32_t lb_fr_lds[];
+  const uint32_t lanes = LB_FR_N / 4, t = threadIdx.x;
+  fr* src = reinterpret_cast<fr*>(lb_fr_lds);
+  fr* dst = src + lanes;
+  const fr_gpoly A{a};
+  const fr z = fr_ldg(z_mont);
+  src[t] = fr_eq_local(A, z, t);
+  __syncthreads();
+  fr w = fr_eq_weight(z);
+  for (uint32_t d = 1; d < lanes; d *= 2) {
+    dst[t] = fr_eq_scan(src, lanes, d, w, t);
+    __syncthreads();
+    fr* x = src;
+    src = dst;
+    dst = x;
+    w = fr_sqr(w);
+  }
+  fr_eq_finish(A, z, src, lanes, t, q_le, y_le);
+}
+#endif  // LB_KG

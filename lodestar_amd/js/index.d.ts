@@ -73,3 +73,17 @@ export declare function chunkifyMaximizeChunkSize<T>(arr: T[], minPerChunk: numb
 export declare const MAX_SIGNATURE_SETS_PER_JOB: number;
 export declare const MAX_BUFFERED_SIGS: number;
 export declare const MAX_BUFFER_WAIT_MS: number;
+
+/**
+ * The c-kzg module surface of lodestar_amd/js/kzg.js (`require("@lodestar/bls-mi355x/kzg")`, the
+ * calls of packages/beacon-node/src/util/kzg.ts:15-65).  field "host" (default): scalar-field work
+ * in BigInt, group work on the GPU; "device": both on the GPU (lb_kzg_blob_to_commitment ...).
+ */
+export type KzgOptions = {field?: "host" | "device"};
+export interface CKzg {
+  loadTrustedSetup(filePath: string, device?: number, options?: KzgOptions): void;
+  blobToKzgCommitment(blob: Uint8Array): Uint8Array;
+  computeAggregateKzgProof(blobs: Uint8Array[]): Uint8Array;
+  verifyAggregateKzgProof(blobs: Uint8Array[], expectedKzgCommitments: Uint8Array[], kzgAggregatedProof: Uint8Array): boolean;
+  readonly G1_INFINITY48: Uint8Array;
+}

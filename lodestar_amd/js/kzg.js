@@ -13,6 +13,11 @@
  * kzg.ts writes (trustedSetupJsonToTxt: "4096", "65", then hex points) or Lodestar's
  * trusted_setup.bin.  Field elements are big-endian (blobsSidecar.ts:138-150).  Parity with
  * c-kzg's bytes is unpinned (DESIGN.md §5.1); calls are synchronous, as c-kzg's are.
+ *
+ * loadTrustedSetup(filePath, device, {field: "device"}) moves the scalar-field work to the GPU too:
+ * the three calls then hand the blobs' bytes to the addon's blob-level calls (kzgBlobToCommitment /
+ * kzgComputeAggregateProof / kzgVerifyAggregateProof -> lb_kzg_blob_to_commitment ...) and no BigInt
+ * arithmetic runs.  The default, {field: "host"}, is the BigInt path above; both give the same bytes.
  */
 const crypto = require("crypto");
 const fs = require("fs");
@@ -163,11 +168,27 @@ function parseSetup(filePath) {
   return {g1: Buffer.concat(g1), g2: Buffer.concat(g2)};
 }
 
-function loadTrustedSetup(filePath, device = 0) {
+let field = "host";
+function loadTrustedSetup(filePath, device = 0, options = {field: "host"}) {
+  const f = (options && options.field) || "host";
+  if (f !== "host" && f !== "device") throw Error('loadTrustedSetup: options.field must be "host" or "device"');
   const {g1, g2} = parseSetup(filePath);
   const e = engine || addon.createEngine(device);
   addon.kzgLoadSetup(e, new Uint8Array(g1), new Uint8Array(g2));
   engine = e;
+  field = f;
+}
+
+function checkBlob(blob) {
+  if (!(blob instanceof Uint8Array) || blob.length !== BYTES_PER_BLOB) throw Error("blob length != 131072");
+}
+function concatBlobs(blobs) {
+  const out = new Uint8Array(BYTES_PER_BLOB * blobs.length);
+  blobs.forEach((b, i) => {
+    checkBlob(b);
+    out.set(b, BYTES_PER_BLOB * i);
+  });
+  return out;
 }
 
 function commitCoefficients(coeffs) {
@@ -175,6 +196,10 @@ function commitCoefficients(coeffs) {
 }
 function blobToKzgCommitment(blob) {
   requireSetup();
+  if (field === "device") {
+    checkBlob(blob);
+    return addon.kzgBlobToCommitment(engine, blob);
+  }
   return commitCoefficients(evaluationsToCoefficients(blobToPolynomial(blob)));
 }
 function aggregate(blobs, commitments) {
@@ -195,6 +220,7 @@ function computeAggregateKzgProof(blobs) {
   requireSetup();
   // chain.ts:402 calls this for every produced block, blobless ones included
   if (!blobs.length) return G1_INFINITY48.slice();
+  if (field === "device") return addon.kzgComputeAggregateProof(engine, concatBlobs(blobs));
   const commitments = blobs.map(blobToKzgCommitment);
   const {agg, x} = aggregate(blobs, commitments);
   return commitCoefficients(quotient(evaluationsToCoefficients(agg), x));
@@ -202,6 +228,14 @@ function computeAggregateKzgProof(blobs) {
 function verifyAggregateKzgProof(blobs, expectedKzgCommitments, kzgAggregatedProof) {
   requireSetup();
   if (blobs.length !== expectedKzgCommitments.length) throw Error("blobs / commitments length mismatch");
+  if (field === "device") {
+    const cm = new Uint8Array(48 * expectedKzgCommitments.length);
+    expectedKzgCommitments.forEach((c, i) => {
+      if (c.length !== 48) throw Error("commitment length != 48");
+      cm.set(c, 48 * i);
+    });
+    return addon.kzgVerifyAggregateProof(engine, concatBlobs(blobs), cm, kzgAggregatedProof);
+  }
   if (!blobs.length) {
     // aggregated commitment = infinity, y = 0: true iff the proof is infinity (still decoded)
     const {x} = computeChallenges([], []);

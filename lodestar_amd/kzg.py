@@ -6,10 +6,17 @@ callers chain/validation/blobsSidecar.ts:75-120 and chain/produceBlock/validateB
 following the EIP-4844 polynomial-commitments spec of the reference's pinned consensus-spec
 version (v1.3.0-alpha.2, test/spec/specTestVersioning.ts:18).
 
-Split: the scalar-field work is host code here (the inverse FFT from the blob's evaluations to
-monomial coefficients, Fiat-Shamir challenges, evaluation, quotient); the group work runs on the
-GPU through the C ABI -- 4096-term G1 linear combinations of the resident trusted setup
-(`lb_g1_lincomb`) and the proof check as one two-pair pairing product (`lb_kzg_verify_proof`).
+Split, chosen per `Kzg(engine, field=...)`:
+
+* field="host" (the default): the scalar-field work is host code here (the inverse FFT from the
+  blob's evaluations to monomial coefficients, Fiat-Shamir challenges, evaluation, quotient); the
+  group work runs on the GPU through the C ABI -- 4096-term G1 linear combinations of the resident
+  trusted setup (`lb_g1_lincomb`) and the proof check as one two-pair pairing product
+  (`lb_kzg_verify_proof`).
+* field="device": the blob-level C calls (`lb_kzg_blob_to_commitment`,
+  `lb_kzg_compute_aggregate_proof`, `lb_kzg_verify_aggregate_proof`, `lb_kzg_compute_proof`,
+  `lb_kzg_blob_coefficients`) take the blobs' bytes; the field work runs in the k_fr_* kernels
+  (csrc/lb_kzg_field.h), only the transcript hash stays on the host (in C).  Same bytes out.
 
 The setup is Lodestar's own `trusted_setup.bin` (kzg.ts:36-48: two u32 counts, 4096 compressed
 [tau^i] G1, 65 compressed [tau^i] G2), i.e. MONOMIAL form (setup_G1[0] is the G1 generator).
@@ -176,8 +183,11 @@ class KzgError(Exception):
 class Kzg:
     """ckzg for one engine: `load_trusted_setup` once, then commitments / aggregate proofs."""
 
-    def __init__(self, engine, setup: bytes = None):
+    def __init__(self, engine, setup: bytes = None, field: str = "host"):
         from lodestar_amd import _native as N
+        if field not in ("host", "device"):
+            raise ValueError('field must be "host" or "device"')
+        self.field = field
         self.engine = engine
         self.lib = N.load()
         self._N = N
@@ -219,7 +229,52 @@ class Kzg:
     def commit_coefficients(self, coeffs: Sequence[int]) -> bytes:
         return self.g1_lincomb(coeffs)
 
+    # -- field="device": bytes straight to the blob-level C calls
+    @staticmethod
+    def _blob_bytes(blobs: Sequence[bytes]) -> np.ndarray:
+        for b in blobs:
+            if len(b) != BYTES_PER_BLOB:
+                raise ValueError(f"blob length {len(b)} != {BYTES_PER_BLOB}")
+        return np.frombuffer(b"".join(bytes(b) for b in blobs) or b"\x00", np.uint8)
+
+    def blob_coefficients(self, blob: bytes) -> List[int]:
+        """monomial coefficients of the blob's polynomial, computed on the GPU (`lb_kzg_blob_coefficients`)"""
+        u8 = ctypes.POINTER(ctypes.c_uint8)
+        src = self._blob_bytes([blob])
+        out = np.zeros(BYTES_PER_BLOB, np.uint8)
+        self._check(self.lib.lb_kzg_blob_coefficients(self.engine.h, src.ctypes.data_as(u8), out.ctypes.data_as(u8)),
+                    "blob_coefficients")
+        raw = out.tobytes()
+        return [int.from_bytes(raw[32 * i: 32 * i + 32], "little") for i in range(FIELD_ELEMENTS_PER_BLOB)]
+
+    def compute_kzg_proof(self, blob: bytes, z: int) -> Tuple[bytes, int]:
+        """(proof, y): the proof that the blob's polynomial takes the value y at z, on the GPU
+        (`lb_kzg_compute_proof`); z may lie on the evaluation domain"""
+        u8 = ctypes.POINTER(ctypes.c_uint8)
+        src = self._blob_bytes([blob])
+        zb = (ctypes.c_uint8 * 32).from_buffer_copy(int(z).to_bytes(32, "little"))
+        proof = (ctypes.c_uint8 * 48)()
+        yb = (ctypes.c_uint8 * 32)()
+        self._check(self.lib.lb_kzg_compute_proof(self.engine.h, src.ctypes.data_as(u8), ctypes.cast(zb, u8),
+                                                  ctypes.cast(proof, u8), ctypes.cast(yb, u8)), "compute_kzg_proof")
+        return bytes(proof), int.from_bytes(bytes(yb), "little")
+
+    def _device_commitments(self, blobs: Sequence[bytes]) -> List[bytes]:
+        u8 = ctypes.POINTER(ctypes.c_uint8)
+        n = len(blobs)
+        src = self._blob_bytes(blobs)
+        out = np.zeros(48 * max(n, 1), np.uint8)
+        status = np.zeros(max(n, 1), np.int32)
+        self._check(self.lib.lb_kzg_blob_to_commitment(self.engine.h, n, src.ctypes.data_as(u8), out.ctypes.data_as(u8),
+                                                       status.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))),
+                    "blobToKzgCommitment")
+        for b in range(n):
+            self._check(int(status[b]), f"blobToKzgCommitment: blob {b}")
+        return [out[48 * b: 48 * b + 48].tobytes() for b in range(n)]
+
     def blob_to_kzg_commitment(self, blob: bytes) -> bytes:
+        if self.field == "device":
+            return self._device_commitments([blob])[0]
         return self.commit_coefficients(evaluations_to_coefficients(blob_to_polynomial(blob)))
 
     def _aggregate(self, blobs: Sequence[bytes], commitments: Sequence[bytes]):
@@ -236,6 +291,13 @@ class Kzg:
         """c-kzg compute_aggregate_kzg_proof; called for every produced block (chain.ts:402), blobless
         ones included: zero blobs aggregate to the zero polynomial, whose proof is the point at
         infinity (the spec's compute_kzg_proof of the zero polynomial)."""
+        if self.field == "device":
+            u8 = ctypes.POINTER(ctypes.c_uint8)
+            src = self._blob_bytes(blobs)
+            out = (ctypes.c_uint8 * 48)()
+            self._check(self.lib.lb_kzg_compute_aggregate_proof(self.engine.h, len(blobs), src.ctypes.data_as(u8),
+                                                                ctypes.cast(out, u8)), "computeAggregateKzgProof")
+            return bytes(out)
         if not blobs:
             return G1_INFINITY48
         commitments = [self.blob_to_kzg_commitment(b) for b in blobs]
@@ -262,6 +324,20 @@ class Kzg:
     def verify_aggregate_kzg_proof(self, blobs: Sequence[bytes], commitments: Sequence[bytes], proof: bytes) -> bool:
         if len(blobs) != len(commitments):
             raise KzgError("verifyAggregateKzgProof: blobs / commitments length mismatch")
+        if self.field == "device":
+            if len(proof) != 48 or any(len(c) != 48 for c in commitments):
+                raise KzgError("verifyAggregateKzgProof: 48-byte commitments and proof")
+            u8 = ctypes.POINTER(ctypes.c_uint8)
+            src = self._blob_bytes(blobs)
+            cm = np.frombuffer(b"".join(bytes(c) for c in commitments) or b"\x00", np.uint8)
+            pb = (ctypes.c_uint8 * 48).from_buffer_copy(bytes(proof))
+            ok = ctypes.c_int32(0)
+            self._check(self.lib.lb_kzg_verify_aggregate_proof(self.engine.h, len(blobs), src.ctypes.data_as(u8),
+                                                               cm.ctypes.data_as(u8), ctypes.cast(pb, u8),
+                                                               ctypes.byref(ok)), "verifyAggregateKzgProof")
+            if ok.value < 0:
+                raise KzgError(f"verifyAggregateKzgProof: {self._N.error_name(-ok.value)}")
+            return ok.value == 1
         if not blobs:
             # aggregated commitment = infinity, y = 0: e(pi, [tau - z] G2) == 1 iff pi is infinity
             # (the check still decodes pi: a malformed proof raises)

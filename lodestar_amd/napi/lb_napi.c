@@ -45,6 +45,9 @@
  *   g1Lincomb(engine, scalars32le: Uint8Array, points48?: Uint8Array) -> Uint8Array(48)
  *       (points omitted: the loaded setup's [tau^i] G1)
  *   kzgVerifyProof(engine, commitment48, z32le, y32le, proof48) -> boolean
+ *   kzgBlobToCommitment(engine, blob) / kzgComputeAggregateProof(engine, blobs) -> Uint8Array (48),
+ *   kzgVerifyAggregateProof(engine, blobs, commitments, proof48) -> boolean: the blob-level calls,
+ *   scalar-field work on the GPU as well (blobs: n x 131072 bytes in one Uint8Array)
  *   (the KZG calls are synchronous, as c-kzg's are; lodestar_amd/js/kzg.js builds the ckzg
  *   module surface of util/kzg.ts on them)
  */
@@ -728,6 +731,78 @@ static napi_value kzg_verify_proof(napi_env env, napi_callback_info info) {
   return v;
 }
 
+/* Blob-level KZG with the scalar-field work on the GPU as well (lb_kzg_blob_to_commitment,
+ * lb_kzg_compute_aggregate_proof, lb_kzg_verify_aggregate_proof); blobs = n x 131072 bytes in one
+ * Uint8Array.  Synchronous, like the other KZG calls. */
+#define LB_BLOB_BYTES 131072u
+static napi_value kzg_blob_to_commitment(napi_env env, napi_callback_info info) {
+  size_t argc = 2;
+  napi_value argv[2];
+  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  engine_box* b = NULL;
+  tview bl;
+  if (argc < 2 || napi_get_value_external(env, argv[0], (void**)&b) != napi_ok || !b || !b->e ||
+      !get_view(env, argv[1], &bl) || !bl.present || bl.type != napi_uint8_array || bl.n != LB_BLOB_BYTES) {
+    napi_throw_type_error(env, NULL, "kzgBlobToCommitment(engine, blob: Uint8Array of 131072 bytes)");
+    return NULL;
+  }
+  napi_value ab, out;
+  void* po;
+  int32_t st = LB_OK;
+  NAPI_CALL(env, napi_create_arraybuffer(env, 48, &po, &ab));
+  const int32_t r = lb_kzg_blob_to_commitment(b->e, 1, (const uint8_t*)bl.data, (uint8_t*)po, &st);
+  if (r != LB_OK) return throw_code(env, r);
+  if (st != LB_OK) return throw_code(env, st);
+  NAPI_CALL(env, napi_create_typedarray(env, napi_uint8_array, 48, ab, 0, &out));
+  return out;
+}
+
+static napi_value kzg_compute_aggregate_proof(napi_env env, napi_callback_info info) {
+  size_t argc = 2;
+  napi_value argv[2];
+  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  engine_box* b = NULL;
+  tview bl;
+  if (argc < 2 || napi_get_value_external(env, argv[0], (void**)&b) != napi_ok || !b || !b->e ||
+      !get_view(env, argv[1], &bl) || !bl.present || bl.type != napi_uint8_array || bl.n % LB_BLOB_BYTES) {
+    napi_throw_type_error(env, NULL, "kzgComputeAggregateProof(engine, blobs: Uint8Array of n x 131072 bytes)");
+    return NULL;
+  }
+  napi_value ab, out;
+  void* po;
+  NAPI_CALL(env, napi_create_arraybuffer(env, 48, &po, &ab));
+  const int32_t r = lb_kzg_compute_aggregate_proof(b->e, (uint32_t)(bl.n / LB_BLOB_BYTES), (const uint8_t*)bl.data,
+                                                   (uint8_t*)po);
+  if (r != LB_OK) return throw_code(env, r);
+  NAPI_CALL(env, napi_create_typedarray(env, napi_uint8_array, 48, ab, 0, &out));
+  return out;
+}
+
+static napi_value kzg_verify_aggregate_proof(napi_env env, napi_callback_info info) {
+  size_t argc = 4;
+  napi_value argv[4];
+  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  engine_box* b = NULL;
+  tview bl, cm, pr;
+  if (argc < 4 || napi_get_value_external(env, argv[0], (void**)&b) != napi_ok || !b || !b->e ||
+      !get_view(env, argv[1], &bl) || !bl.present || bl.type != napi_uint8_array || bl.n % LB_BLOB_BYTES ||
+      !get_view(env, argv[2], &cm) || !cm.present || cm.type != napi_uint8_array ||
+      cm.n != bl.n / LB_BLOB_BYTES * 48 || !get_view(env, argv[3], &pr) || !pr.present || pr.n != 48) {
+    napi_throw_type_error(env, NULL,
+                          "kzgVerifyAggregateProof(engine, blobs: Uint8Array of n x 131072 bytes, "
+                          "commitments: Uint8Array of n x 48 bytes, proof48)");
+    return NULL;
+  }
+  int32_t ok = 0;
+  const int32_t r = lb_kzg_verify_aggregate_proof(b->e, (uint32_t)(bl.n / LB_BLOB_BYTES), (const uint8_t*)bl.data,
+                                                  (const uint8_t*)cm.data, (const uint8_t*)pr.data, &ok);
+  if (r != LB_OK) return throw_code(env, r);
+  if (ok < 0) return throw_code(env, -ok);
+  napi_value v;
+  NAPI_CALL(env, napi_get_boolean(env, ok == 1, &v));
+  return v;
+}
+
 static napi_value table_size(napi_env env, napi_callback_info info) {
   size_t argc = 1;
   napi_value argv[1], v;
@@ -773,6 +848,9 @@ static napi_value init(napi_env env, napi_value exports) {
       {"kzgLoadSetup", NULL, kzg_load_setup, NULL, NULL, NULL, napi_default, NULL},
       {"g1Lincomb", NULL, g1_lincomb, NULL, NULL, NULL, napi_default, NULL},
       {"kzgVerifyProof", NULL, kzg_verify_proof, NULL, NULL, NULL, napi_default, NULL},
+      {"kzgBlobToCommitment", NULL, kzg_blob_to_commitment, NULL, NULL, NULL, napi_default, NULL},
+      {"kzgComputeAggregateProof", NULL, kzg_compute_aggregate_proof, NULL, NULL, NULL, napi_default, NULL},
+      {"kzgVerifyAggregateProof", NULL, kzg_verify_aggregate_proof, NULL, NULL, NULL, napi_default, NULL},
   };
   napi_define_properties(env, exports, sizeof(props) / sizeof(props[0]), props);
   return exports;

@@ -18,7 +18,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "lodestar_amd", "csrc")
-FILES = ["lb_kernels.h", "lb_group_exec.h", "lb_kzg.h", "lb_ssz.h", "lb_latency.h"]
+FILES = ["lb_kernels.h", "lb_group_exec.h", "lb_kzg.h", "lb_kzg_field.h", "lb_ssz.h", "lb_latency.h"]
 OUT = os.path.join(CSRC, "lb_kdecl.h")
 
 # kernel -> translation-unit group (balanced by measured compile time; the one-lane per-root and
@@ -45,6 +45,8 @@ GROUPS = {
     12: ["k_hash_finish_row"],
     13: ["k_hash_map_row", "k_decompress_sigs_row", "k_pk_blind_rowp", "k_sig_subgroup_w4", "k_sig_blind_w4"],
     15: ["k_comb_fill", "k_pk_blind_comb"],
+    # KZG scalar field (lb_kzg_field.h), beside the KZG group kernels of group 7
+    16: ["k_fr_blob_load", "k_fr_aggregate", "k_fr_intt4096", "k_fr_eval_quotient"],
 }
 N_GROUPS = len(GROUPS)
 GROUP_OF = {k: g for g, ks in GROUPS.items() for k in ks}
