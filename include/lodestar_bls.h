@@ -263,6 +263,30 @@ int32_t lb_kzg_verify_aggregate_proof(lb_engine* e, uint32_t n_blobs, const uint
 int32_t lb_kzg_blob_coefficients(lb_engine* e, const uint8_t* blob, uint8_t* out_coeffs32le /* 4096 x 32 */);
 
 /*
+ * lb_kzg_verify_aggregate_proof for many sidecars in one pass (a range-sync segment's blocks): every
+ * stage runs once over all of them, with one stream synchronisation, and each sidecar gets its own
+ * exact pairing check.  Sidecar k owns blobs blob_offsets[k] .. blob_offsets[k + 1] - 1 and their
+ * commitments; a sidecar without blobs is allowed anywhere (1 iff its proof is the point at
+ * infinity; the proof is still decoded and subgroup-checked).
+ * out_ok[k] is what lb_kzg_verify_aggregate_proof reports for sidecar k alone: its *ok (1, 0, or
+ * -code for a commitment or proof that fails to decode or lies outside G1), or -LB_BAD_SCALAR where
+ * the single call returns LB_BAD_SCALAR.  Precedence as there: a blob element >= r, the first
+ * failing commitment in order, the proof's decode error, the proof outside G1.  A sidecar that
+ * rejects changes nothing for the others.
+ * Returns LB_OK whenever the call ran (n_sidecars == 0: at once, nothing written); LB_ERR_ARGUMENT
+ * for no 4096-point setup, a needed pointer that is NULL, blob_offsets[0] != 0, decreasing offsets,
+ * more than 1024 sidecars or more than 1024 blobs in all.
+ * lb_kzg_batch_hash_ns: the host time the engine's last batch call spent hashing transcripts.
+ */
+int32_t lb_kzg_verify_aggregate_proof_batch(lb_engine* e, uint32_t n_sidecars,
+                                            const uint32_t* blob_offsets, /* n_sidecars + 1 prefix sums over blobs */
+                                            const uint8_t* blobs,         /* blob_offsets[n] x 131072 B */
+                                            const uint8_t* commitments48, /* blob_offsets[n] x 48 B, same order */
+                                            const uint8_t* proofs48,      /* n_sidecars x 48 B */
+                                            int32_t* out_ok);             /* n_sidecars */
+uint64_t lb_kzg_batch_hash_ns(const lb_engine* e);
+
+/*
  * Synthetic-data helpers for tests and the benchmark (not on the verification path):
  * SecretKey.toPublicKey and SecretKey.sign as used by the reference's own tests
  * (test/e2e/chain/bls/multithread.test.ts:28-31).  Secret keys are 32-byte big-endian < r.

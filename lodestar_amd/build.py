@@ -148,6 +148,24 @@ def build_fr_harness(force=False, verbose=True):
     return FR_HARNESS
 
 
+KZG_BATCH_HARNESS = os.path.join(ROOT, "build", "lb_kzg_batch_harness.so")
+
+
+def build_kzg_batch_harness(force=False, verbose=True):
+    """the segmented aggregation and the evaluation of the batched KZG verification on the CPU
+    (tests/test_kzg_batch_cpu.py)"""
+    src = os.path.join(ROOT, "tests", "harness", "lb_kzg_batch_harness.cpp")
+    os.makedirs(os.path.dirname(KZG_BATCH_HARNESS), exist_ok=True)
+    if not force and not _stale(KZG_BATCH_HARNESS, _deps() + [src]):
+        return KZG_BATCH_HARNESS
+    cmd = ["g++", "-O2", "-shared", "-fPIC", "-I" + INC, "-I" + CSRC, src, "-o", KZG_BATCH_HARNESS + ".tmp"]
+    if verbose:
+        print("[build]", " ".join(cmd), flush=True)
+    subprocess.run(cmd, check=True)
+    os.replace(KZG_BATCH_HARNESS + ".tmp", KZG_BATCH_HARNESS)
+    return KZG_BATCH_HARNESS
+
+
 def build_cpu_pool(force=False, verbose=True):
     src = os.path.join(ROOT, "oracle", "cpu_pool.cpp")
     if not os.path.exists(src):
@@ -208,6 +226,7 @@ def build_all(force=False):
     build_harness(force)
     build_comb_harness(force)
     build_fr_harness(force)
+    build_kzg_batch_harness(force)
     build_cpu_pool(force)
     build_ubench(force)
 

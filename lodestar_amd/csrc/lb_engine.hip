@@ -241,6 +241,7 @@ struct lb_engine {
   // ... and the inverse transform's twiddles for the blob-level calls (lb_fr.h fr_intt_table(12):
   // 2048 powers of the inverse root and 1 / 4096, Montgomery form), built on the host at load
   dbuf kzg_tw;
+  uint64_t kzg_batch_hash_ns = 0;  // host transcript hashing of the last batch verification (lb_kzg_batch_hash_ns)
   // profiling
   bool profiling = false;
   hipEvent_t ev0[kStages] = {}, ev1[kStages] = {};
@@ -2547,9 +2548,11 @@ struct kzg_ws {
   dbuf pw, pw_le;  // r^j, Montgomery and plain LE
   dbuf z;       // evaluation point, Montgomery
   dbuf io, yz;  // k_kzg_check's inputs: C || proof, y || z as LE words
+  dbuf off, ok;  // the batched verification: sidecar offsets in, verdicts out
   std::vector<int32_t> h_status;
   ~kzg_ws() {
-    for (dbuf* b : {&blobs, &polys, &status, &agg, &coef, &le, &terms, &part, &tstatus, &pts, &pw, &pw_le, &z, &io, &yz})
+    for (dbuf* b : {&blobs, &polys, &status, &agg, &coef, &le, &terms, &part, &tstatus, &pts, &pw, &pw_le, &z, &io, &yz,
+                    &off, &ok})
       b->release();
   }
 };
@@ -2796,3 +2799,101 @@ extern "C" int32_t lb_kzg_verify_aggregate_proof(lb_engine* e, uint32_t n_blobs,
   LB_KZG_TRY(hipStreamSynchronize(e->stream));
   return LB_OK;
 }
+
+// Many sidecars in one pass: every stage once over all of them, one synchronisation at the end.
+// Device arrays in k_g1_terms' order: the commitments, then the proofs, then one G1 generator per
+// sidecar; their scalars r_k^j, x_k from the host and y_k written by k_fr_eval_many.
+extern "C" int32_t lb_kzg_verify_aggregate_proof_batch(lb_engine* e, uint32_t n, const uint32_t* blob_offsets,
+                                                       const uint8_t* blobs, const uint8_t* commitments48,
+                                                       const uint8_t* proofs48, int32_t* out_ok) {
+  if (!kzg_ready(e) || n > 1024) return LB_ERR_ARGUMENT;
+  if (!n) return LB_OK;
+  if (!blob_offsets || !proofs48 || !out_ok || blob_offsets[0] != 0) return LB_ERR_ARGUMENT;
+  for (uint32_t k = 0; k < n; k++)
+    if (blob_offsets[k + 1] < blob_offsets[k]) return LB_ERR_ARGUMENT;
+  const uint32_t nb = blob_offsets[n];
+  if (nb > kMaxBlobs || (nb && (!blobs || !commitments48))) return LB_ERR_ARGUMENT;
+  static const uint8_t kG1Gen48[48] = {0x97, 0xf1, 0xd3, 0xa7, 0x31, 0x97, 0xd7, 0x94, 0x26, 0x95, 0x63, 0x8c,
+                                       0x4f, 0xa9, 0xac, 0x0f, 0xc3, 0x68, 0x8c, 0x4f, 0x97, 0x74, 0xb9, 0x05,
+                                       0xa1, 0x4e, 0x3a, 0x3f, 0x17, 0x1b, 0xac, 0x58, 0x6c, 0x55, 0xe8, 0x3f,
+                                       0xf9, 0x7a, 0x1a, 0xef, 0xfb, 0x3a, 0xf0, 0x0a, 0xdb, 0x22, 0xc6, 0xbb};
+  const uint32_t n_pts = nb + 2 * n;
+  std::lock_guard<std::mutex> lk(e->mu);
+  kzg_ws w;
+  LB_KZG_TRY(hipSetDevice(e->device));
+  LB_KZG_TRY(w.blobs.ensure(std::max<size_t>(nb, 1) * kBlobBytes));
+  LB_KZG_TRY(w.polys.ensure(std::max<size_t>(nb, 1) * kBlobBytes));
+  LB_KZG_TRY(w.status.ensure(std::max<size_t>(nb, 1) * 4));
+  LB_KZG_TRY(w.pw.ensure(std::max<size_t>(nb, 1) * sizeof(fr)));
+  LB_KZG_TRY(w.z.ensure((size_t)n * sizeof(fr)));
+  LB_KZG_TRY(w.agg.ensure((size_t)n * kBlobBytes));
+  LB_KZG_TRY(w.coef.ensure((size_t)n * kBlobBytes));
+  LB_KZG_TRY(w.pts.ensure((size_t)n_pts * 48));
+  LB_KZG_TRY(w.le.ensure((size_t)n_pts * 32));
+  LB_KZG_TRY(w.terms.ensure((size_t)n_pts * sizeof(g1j)));
+  LB_KZG_TRY(w.tstatus.ensure((size_t)n_pts * 4));
+  LB_KZG_TRY(w.off.ensure((size_t)(n + 1) * 4));
+  LB_KZG_TRY(w.ok.ensure((size_t)n * 4));
+  // 1. the blobs go up and are decoded while the host hashes
+  LB_KZG_TRY(hipMemcpyAsync(w.off.p, blob_offsets, (size_t)(n + 1) * 4, hipMemcpyHostToDevice, e->stream));
+  if (nb) {
+    LB_KZG_TRY(hipMemcpyAsync(w.blobs.p, blobs, nb * kBlobBytes, hipMemcpyHostToDevice, e->stream));
+    LB_KZG_TRY(hipMemsetAsync(w.status.p, 0, (size_t)nb * 4, e->stream));
+    const uint32_t n_elems = nb * LB_FR_N;
+    hipLaunchKernelGGL(k_fr_blob_load, dim3((n_elems + 255) / 256), dim3(256), 0, e->stream, n_elems,
+                       w.blobs.as<uint8_t>(), w.polys.as<uint32_t>(), w.status.as<int32_t>());
+    LB_KZG_TRY(hipGetLastError());
+  }
+  // 2. challenges per sidecar; the host arrays live until the synchronisation below
+  std::vector<fr> pw(std::max<uint32_t>(nb, 1)), zs(n), sc(nb + n);
+  uint64_t hash_ns = 0;
+  for (uint32_t k = 0; k < n; k++) {
+    const uint32_t lo = blob_offsets[k], cnt = blob_offsets[k + 1] - lo;
+    fr r, x;
+    const auto h0 = std::chrono::steady_clock::now();
+    kzg_challenges(cnt, cnt ? blobs + lo * kBlobBytes : nullptr, cnt ? commitments48 + (size_t)48 * lo : nullptr, r, x);
+    hash_ns += (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - h0).count();
+    fr p = fr_one();
+    for (uint32_t j = 0; j < cnt; j++) {
+      pw[lo + j] = p;
+      fr_to_le_words(sc[lo + j].l, p);
+      p = fr_mul(p, r);
+    }
+    zs[k] = x;
+    fr_to_le_words(sc[nb + k].l, x);
+  }
+  e->kzg_batch_hash_ns = hash_ns;
+  std::vector<uint8_t> pts((size_t)n_pts * 48);
+  if (nb) memcpy(pts.data(), commitments48, (size_t)nb * 48);
+  memcpy(pts.data() + (size_t)nb * 48, proofs48, (size_t)n * 48);
+  for (uint32_t k = 0; k < n; k++) memcpy(pts.data() + (size_t)(nb + n + k) * 48, kG1Gen48, 48);
+  if (nb) LB_KZG_TRY(hipMemcpyAsync(w.pw.p, pw.data(), (size_t)nb * sizeof(fr), hipMemcpyHostToDevice, e->stream));
+  LB_KZG_TRY(hipMemcpyAsync(w.z.p, zs.data(), (size_t)n * sizeof(fr), hipMemcpyHostToDevice, e->stream));
+  LB_KZG_TRY(hipMemcpyAsync(w.le.p, sc.data(), (size_t)(nb + n) * sizeof(fr), hipMemcpyHostToDevice, e->stream));
+  LB_KZG_TRY(hipMemcpyAsync(w.pts.p, pts.data(), pts.size(), hipMemcpyHostToDevice, e->stream));
+  // 3. - 5. aggregates, their coefficients, their values y_k into the generators' scalar slots
+  hipLaunchKernelGGL(k_fr_aggregate_seg, dim3(n * (LB_FR_N / 256)), dim3(256), 0, e->stream, n, w.off.as<uint32_t>(), nb,
+                     w.polys.as<uint32_t>(), w.pw.as<uint32_t>(), w.agg.as<uint32_t>());
+  LB_KZG_TRY(hipGetLastError());
+  const int32_t rc = kzg_intt(e, n, w.agg.as<uint32_t>(), w.coef.as<uint32_t>(), nullptr);
+  if (rc != LB_OK) return rc;
+  hipLaunchKernelGGL(k_fr_eval_many, dim3(n), dim3(LB_FR_WG), LB_FR_EV_LDS, e->stream, w.coef.as<uint32_t>(),
+                     w.z.as<uint32_t>(), w.le.as<uint32_t>() + (size_t)8 * (nb + n));
+  LB_KZG_TRY(hipGetLastError());
+  // 6. every ladder and subgroup check of the segment in one launch
+  hipLaunchKernelGGL(k_g1_terms, dim3(nblk(n_pts)), dim3(LB_TPB), 0, e->stream, n_pts, w.pts.as<uint8_t>(),
+                     e->kzg_g1.as<uint32_t>(), e->kzg_n, w.le.as<uint32_t>(), w.terms.as<uint32_t>(),
+                     w.tstatus.as<int32_t>());
+  LB_KZG_TRY(hipGetLastError());
+  // 7. one wave per sidecar: status, T_k, the two-pair product
+  hipLaunchKernelGGL(k_kzg_check_many, dim3(n), dim3(64), 0, e->stream, n, w.off.as<uint32_t>(), nb,
+                     w.status.as<int32_t>(), w.pts.as<uint8_t>(), w.terms.as<uint32_t>(), w.tstatus.as<int32_t>(),
+                     e->kzg_g2.as<uint32_t>(), w.ok.as<int32_t>());
+  LB_KZG_TRY(hipGetLastError());
+  // 8. the verdicts
+  LB_KZG_TRY(hipMemcpyAsync(out_ok, w.ok.p, (size_t)n * 4, hipMemcpyDeviceToHost, e->stream));
+  LB_KZG_TRY(hipStreamSynchronize(e->stream));
+  return LB_OK;
+}
+
+extern "C" uint64_t lb_kzg_batch_hash_ns(const lb_engine* e) { return e ? e->kzg_batch_hash_ns : 0; }

@@ -279,3 +279,33 @@ LB_HD void fr_eq_finish(const A& a, const fr& z, const fr* T, uint32_t lanes, ui
     LB_UNROLL for (int w = 0; w < 8; w++) q_le[(size_t)8 * (4 * lanes - 1) + w] = 0;
   }
 }
+
+// ------------------------------------------------------------------ segments: many sidecars at once
+// The batched verification (lb_kzg_verify_aggregate_proof_batch) lays the polynomials of all its
+// sidecars side by side; sidecar k owns polynomials off[k] .. off[k + 1] - 1.
+//
+// fr_seg_aggregate: element i of sum_j pw[j] poly_j over the polynomials lo <= j < hi of one
+// sidecar (pw[j] = r_k^(j - lo), Montgomery form).  `poly(j, i)` and `pw(j)` are accessors; an empty
+// range gives 0, the zero polynomial's element.  The caller bounds lo <= hi <= the polynomial count.
+template <class P, class W>
+LB_HD fr fr_seg_aggregate(const P& poly, const W& pw, uint32_t lo, uint32_t hi, uint32_t i) {
+  fr acc = fr_zero();
+  for (uint32_t j = lo; j < hi; j++) acc = fr_add(acc, fr_mul(pw(j), poly(j, i)));
+  return acc;
+}
+
+// Evaluation alone, y = p(z), where the quotient of fr_eq_* is not wanted: lane t of n / 4 takes
+// its four coefficients by Horner (fr_eq_local: L[t] = sum_k a[4 t + k] z^k), then
+// y = sum_t L[t] z^(4 t) folds in halves: for s = log2(n / 4) - 1 down to 0, with h = 2^s, lane
+// t < h does V[t] += z^(4 h) V[t + h] (fr_ev_fold), barrier; V[0] is y.  The live lanes stay
+// contiguous, so whole waves drop out step by step.  V is an accessor with ld / st over n / 4
+// values; fr_ev_weight(z, s) = z^(4 * 2^s) is the weight of the step with h = 2^s.
+LB_HD fr fr_ev_weight(const fr& z, int s) {
+  fr w = fr_eq_weight(z);
+  for (int i = 0; i < s; i++) w = fr_sqr(w);
+  return w;
+}
+template <class V>
+LB_HD void fr_ev_fold(V& v, uint32_t h, const fr& w, uint32_t t) {
+  if (t < h) v.st(t, fr_add(v.ld(t), fr_mul(w, v.ld(t + h))));
+}

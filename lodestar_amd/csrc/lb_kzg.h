@@ -213,3 +213,105 @@ __global__ void __launch_bounds__(64) k_kzg_check(const uint8_t* __restrict__ io
   if (lane == 0) *ok = one ? 1 : 0;
 }
 #endif  // LB_KG
+
+// The same check for many sidecars at once (lb_kzg_verify_aggregate_proof_batch): one wave per
+// sidecar k, which owns blobs off[k] .. off[k + 1] - 1 of n_blobs.  The scalar multiplications and
+// the subgroup checks ran before, in one k_g1_terms launch over n_blobs + 2 n points:
+//   [0, n_blobs)            the commitments C_j, scalars r_k^j
+//   n_blobs + k             the proof pi_k, scalar x_k
+//   n_blobs + n + k         the G1 generator, scalar y_k
+// (pts48, terms as a g1j SoA of that many entries, tstatus).  Here: the sidecar's status by the single
+// call's precedence (a blob element >= r, bstatus; the first failing commitment; the proof), then
+// T_k = sum_j [r_k^j] C_j - [y_k] G1 + [x_k] pi_k and e(T_k, -G2) e(pi_k, [tau] G2) == 1 on the
+// wave engine.  ok[k] = 1 / 0, or -code; a sidecar with a bad status never reaches the pairing.
+// The offsets are clamped to n_blobs and to each other before anything is indexed by them.
+#if LB_KG(5)
+__global__ void __launch_bounds__(64) k_kzg_check_many(uint32_t n, const uint32_t* __restrict__ off, uint32_t n_blobs,
+                                                       const int32_t* __restrict__ bstatus, const uint8_t* __restrict__ pts48,
+                                                       const uint32_t* __restrict__ terms, const int32_t* __restrict__ tstatus,
+                                                       const uint32_t* __restrict__ g2, int32_t* __restrict__ ok) {
+  LBW_SHARED_ML(S);
+  __shared__ int st_sh, qinf_sh, pinf_sh;
+  const int lane = threadIdx.x;
+  const uint32_t k = blockIdx.x;
+  if (k >= n) return;
+  w_init_consts(S, LBW_PROGS_ALL);
+  const uint32_t n_pts = n_blobs + 2 * n, i_pi = n_blobs + k, i_g = n_blobs + n + k;
+  const uint32_t hi = min(off[k + 1], n_blobs), lo = min(off[k], hi);
+  // the sidecar's terms: its commitments, then [x] pi, then [y] G1 (subtracted); 64 at a time
+  const uint32_t m = hi - lo + 2;
+  g1j v = jac_infinity<fp>();
+  for (uint32_t q = lane; q < m; q += 64) {
+    const uint32_t idx = q + 2 < m ? lo + q : (q + 2 == m ? i_pi : i_g);
+    g1j t = soa_ld<g1j>(terms, n_pts, idx);
+    if (q + 1 == m) t = jac_neg(t);
+    v = jac_add_i(v, t);
+  }
+  for (int l = 5; l >= 0; l--) {
+    const unsigned d = 1u << l;
+    const g1j o{fp_shfl_down(v.x, d), fp_shfl_down(v.y, d), fp_shfl_down(v.z, d)};
+    if (threadIdx.x < d) v = jac_add_i(v, o);
+  }
+  g1a pi;
+  if (lane == 0) {
+    int st = LB_OK;
+    for (uint32_t j = lo; j < hi && st == LB_OK; j++)
+      if (bstatus[j] != LB_OK) st = LB_BAD_SCALAR;
+    for (uint32_t j = lo; j < hi && st == LB_OK; j++) st = tstatus[j];
+    if (st == LB_OK) st = tstatus[i_pi];
+    bool pinf = false;
+    bool qfin = false;
+    g1a qa;
+    if (st == LB_OK) {
+      // pi in affine form for its Miller loop (its status is LB_OK: it decodes)
+      uint8_t b[48];
+      ld_bytes<48>(b, pts48 + (size_t)48 * i_pi);
+      st = g1_decompress48(b, pi, pinf);
+      qfin = jac_to_aff(qa, v);
+    }
+    if (st == LB_OK) {
+      w_st(S, LBW_PT + 0, qa.x);
+      w_st(S, LBW_PT + 1, qa.y);
+      const g2a* G = reinterpret_cast<const g2a*>(g2);
+      const g2a g0 = G[0];
+      w_st(S, LBW_PT + 2, g0.x.c0);
+      w_st(S, LBW_PT + 3, g0.x.c1);
+      w_st(S, LBW_PT + 4, fp_neg(g0.y.c0));  // -G2
+      w_st(S, LBW_PT + 5, fp_neg(g0.y.c1));
+    }
+    st_sh = st;
+    qinf_sh = qfin ? 0 : 1;
+    pinf_sh = pinf ? 1 : 0;
+  }
+  __syncthreads();
+  const int st_u = st_sh, qinf = qinf_sh, pinf_u = pinf_sh;
+  __syncthreads();
+  if (st_u != LB_OK) {
+    if (lane == 0) ok[k] = -st_u;
+    return;
+  }
+  if (qinf)
+    w_set_one(S, LBW_A(0));
+  else
+    w_miller(S, LBW_A(0));
+  if (lane == 0) {
+    const g2a* G = reinterpret_cast<const g2a*>(g2);
+    const g2a g1t = G[1];
+    w_st(S, LBW_PT + 0, pi.x);
+    w_st(S, LBW_PT + 1, pi.y);
+    w_st(S, LBW_PT + 2, g1t.x.c0);
+    w_st(S, LBW_PT + 3, g1t.x.c1);
+    w_st(S, LBW_PT + 4, g1t.y.c0);
+    w_st(S, LBW_PT + 5, g1t.y.c1);
+  }
+  __syncthreads();
+  if (pinf_u)
+    w_set_one(S, LBW_A(7));
+  else
+    w_miller(S, LBW_A(7));
+  w_mul(S, LBW_A(0), LBW_A(0), LBW_A(7));
+  w_final_exp(S, LBW_A(0), LBW_A(0));
+  const bool one = w_is_one(S, LBW_A(0));
+  if (lane == 0) ok[k] = one ? 1 : 0;
+}
+#endif  // LB_KG

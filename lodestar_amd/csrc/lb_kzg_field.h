@@ -138,3 +138,68 @@ __global__ void __launch_bounds__(LB_FR_WG) k_fr_eval_quotient(const uint32_t* _
   fr_eq_finish(A, z, src, lanes, t, q_le, y_le);
 }
 #endif  // LB_KG
+
+// ------------------------------------------------------------------ many sidecars in one pass
+// lb_kzg_verify_aggregate_proof_batch: the polynomials of all sidecars stand side by side, sidecar
+// k owning polynomials off[k] .. off[k + 1] - 1 (off: n_sidecars + 1 prefix sums, n_polys in all).
+#define LB_FR_EV_LDS ((LB_FR_N / 4) * 32u + 16u * 32u)  // 1024 lane values + the ten step weights
+
+struct fr_gpolys {
+  const uint32_t* p;
+  __device__ __forceinline__ fr operator()(uint32_t j, uint32_t i) const { return fr_ldg(p + ((size_t)j * LB_FR_N + i) * 8); }
+};
+// n values in LDS, limb-major like fr_lds_poly: word w of value i at w * n + i
+struct fr_lds_vec {
+  uint32_t* w;
+  uint32_t n;
+  __device__ __forceinline__ fr ld(uint32_t i) const {
+    fr v;
+    LB_UNROLL for (int k = 0; k < 8; k++) v.l[k] = w[k * n + i];
+    return v;
+  }
+  __device__ __forceinline__ void st(uint32_t i, const fr& v) {
+    LB_UNROLL for (int k = 0; k < 8; k++) w[k * n + i] = v.l[k];
+  }
+};
+
+// agg[k][i] = sum_j pw[j] polys[j][i] over sidecar k's polynomials (pw[j] = r_k^(j - off[k])), one
+// thread per element of every aggregate; a sidecar without polynomials gets the zero polynomial.
+// The offsets are clamped to n_polys and to each other before anything is indexed by them.
+#if LB_KG(16)
+__global__ void __launch_bounds__(256) k_fr_aggregate_seg(uint32_t n_sidecars, const uint32_t* __restrict__ off, uint32_t n_polys,
+                                                          const uint32_t* __restrict__ polys, const uint32_t* __restrict__ pw,
+                                                          uint32_t* __restrict__ agg) {
+  const uint32_t k = blockIdx.x / (LB_FR_N / 256), i = (blockIdx.x % (LB_FR_N / 256)) * 256 + threadIdx.x;
+  if (k >= n_sidecars) return;
+  const uint32_t hi = min(off[k + 1], n_polys), lo = min(off[k], hi);
+  fr_stg(agg + ((size_t)k * LB_FR_N + i) * 8, fr_seg_aggregate(fr_gpolys{polys}, fr_gtable{pw}, lo, hi, i));
+}
+#endif  // LB_KG
+
+// One workgroup per polynomial: y_k = p_k(z_k) for the 4096 coefficients coef[k] (Montgomery) and
+// the point z[k] (Montgomery), each polynomial at its own point; lb_fr.h fr_eq_local and fr_ev_*.
+// y_k leaves as 8 plain LE words at y_le + 8 k: a scalar of k_g1_terms.  No quotient.
+// LB_FR_EV_LDS bytes of dynamic LDS.
+#if LB_KG(16)
+__global__ void __launch_bounds__(LB_FR_WG) k_fr_eval_many(const uint32_t* __restrict__ coef, const uint32_t* __restrict__ z_mont,
+                                                           uint32_t* __restrict__ y_le) {
+  extern __shared__ uint32_t lb_fr_lds[];
+  const uint32_t lanes = LB_FR_N / 4, t = threadIdx.x, k = blockIdx.x;
+  fr_lds_vec V{lb_fr_lds, lanes};
+  fr_lds_vec W{lb_fr_lds + lanes * 8, 16};
+  const fr_gpoly A{coef + (size_t)k * LB_FR_N * 8};
+  const fr z = fr_ldg(z_mont + (size_t)8 * k);
+  V.st(t, fr_eq_local(A, z, t));
+  if (t < LB_FR_LOGN - 2) W.st(t, fr_ev_weight(z, (int)t));
+  __syncthreads();
+  for (int s = LB_FR_LOGN - 3; s >= 0; s--) {
+    fr_ev_fold(V, 1u << s, W.ld((uint32_t)s), t);
+    __syncthreads();
+  }
+  if (t == 0) {
+    uint32_t w[8];
+    fr_to_le_words(w, V.ld(0));
+    fr_stg(y_le + (size_t)8 * k, fr_from_words(w));
+  }
+}
+#endif  // LB_KG

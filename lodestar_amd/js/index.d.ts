@@ -85,5 +85,11 @@ export interface CKzg {
   blobToKzgCommitment(blob: Uint8Array): Uint8Array;
   computeAggregateKzgProof(blobs: Uint8Array[]): Uint8Array;
   verifyAggregateKzgProof(blobs: Uint8Array[], expectedKzgCommitments: Uint8Array[], kzgAggregatedProof: Uint8Array): boolean;
+  /**
+   * verifyAggregateKzgProof for many sidecars (a range-sync segment's blocks) in one pass over the
+   * GPU, in either field mode: true, false, or the Error the single call would throw, per sidecar.
+   */
+  verifyAggregateKzgProofBatch(sidecars: KzgSidecar[]): (boolean | Error)[];
   readonly G1_INFINITY48: Uint8Array;
 }
+export type KzgSidecar = {blobs: Uint8Array[]; commitments: Uint8Array[]; proof: Uint8Array};

@@ -18,6 +18,9 @@
  * the three calls then hand the blobs' bytes to the addon's blob-level calls (kzgBlobToCommitment /
  * kzgComputeAggregateProof / kzgVerifyAggregateProof -> lb_kzg_blob_to_commitment ...) and no BigInt
  * arithmetic runs.  The default, {field: "host"}, is the BigInt path above; both give the same bytes.
+ *
+ * verifyAggregateKzgProofBatch(sidecars) is not part of c-kzg: many sidecars (a range-sync segment's
+ * blocks) in one pass over the GPU, one verdict per sidecar, in either field mode.
  */
 const crypto = require("crypto");
 const fs = require("fs");
@@ -249,11 +252,41 @@ function verifyAggregateKzgProof(blobs, expectedKzgCommitments, kzgAggregatedPro
   return addon.kzgVerifyProof(engine, c, bigToBytes(x, 32, true), bigToBytes(y, 32, true), kzgAggregatedProof);
 }
 
+// verifyAggregateKzgProof for many sidecars (a range-sync segment's blocks) in one pass over the GPU
+// (kzgVerifyAggregateProofBatch -> lb_kzg_verify_aggregate_proof_batch), in either field mode.
+// sidecars: {blobs, commitments, proof}[].  One entry per sidecar: true, false, or the Error the
+// single call would throw -- returned, not thrown, so one bad sidecar does not hide the others.
+// Malformed input throws before anything is sent.
+function verifyAggregateKzgProofBatch(sidecars) {
+  requireSetup();
+  const offsets = new Uint32Array(sidecars.length + 1);
+  const allBlobs = [];
+  const allComms = [];
+  sidecars.forEach((s, k) => {
+    if (s.blobs.length !== s.commitments.length) throw Error("blobs / commitments length mismatch");
+    s.commitments.forEach((c) => {
+      if (c.length !== 48) throw Error("commitment length != 48");
+      allComms.push(c);
+    });
+    if (s.proof.length !== 48) throw Error("proof length != 48");
+    allBlobs.push(...s.blobs);
+    offsets[k + 1] = allBlobs.length;
+  });
+  if (!sidecars.length) return [];
+  const cm = new Uint8Array(48 * allComms.length);
+  allComms.forEach((c, i) => cm.set(c, 48 * i));
+  const pr = new Uint8Array(48 * sidecars.length);
+  sidecars.forEach((s, k) => pr.set(s.proof, 48 * k));
+  const ok = addon.kzgVerifyAggregateProofBatch(engine, concatBlobs(allBlobs), offsets, cm, pr);
+  return Array.from(ok, (v) => (v < 0 ? Error(addon.errorName(-v)) : v === 1));
+}
+
 module.exports = {
   loadTrustedSetup,
   blobToKzgCommitment,
   computeAggregateKzgProof,
   verifyAggregateKzgProof,
+  verifyAggregateKzgProofBatch,
   G1_INFINITY48,
   // host field work, exported for tests
   _internal: {evaluationsToCoefficients, evaluate, quotient, computeChallenges, ROOTS, BRP, R},

@@ -18,6 +18,9 @@ Split, chosen per `Kzg(engine, field=...)`:
   `lb_kzg_blob_coefficients`) take the blobs' bytes; the field work runs in the k_fr_* kernels
   (csrc/lb_kzg_field.h), only the transcript hash stays on the host (in C).  Same bytes out.
 
+Whatever `field` is, `verify_aggregate_kzg_proof_batch` checks many sidecars (a range-sync segment's
+blocks) in one pass over the GPU (`lb_kzg_verify_aggregate_proof_batch`), one verdict per sidecar.
+
 The setup is Lodestar's own `trusted_setup.bin` (kzg.ts:36-48: two u32 counts, 4096 compressed
 [tau^i] G1, 65 compressed [tau^i] G2), i.e. MONOMIAL form (setup_G1[0] is the G1 generator).
 Committing in monomial form, sum a_j [tau^j] G1 with a = IFFT of the blob's evaluations, gives
@@ -347,7 +350,40 @@ class Kzg:
         y = evaluate_coefficients(evaluations_to_coefficients(agg), x)
         return self.verify_kzg_proof(c, x, y, proof)
 
+    def verify_aggregate_kzg_proof_batch(self, sidecars: Sequence[Tuple[Sequence[bytes], Sequence[bytes], bytes]]) -> list:
+        """verify_aggregate_kzg_proof for many sidecars (a range-sync segment's blocks) in one pass
+        over the GPU (`lb_kzg_verify_aggregate_proof_batch`), whatever `field` is.  `sidecars`:
+        (blobs, commitments, proof) each.  One entry per sidecar: True, False, or the KzgError the
+        single call would raise -- returned, not raised, so one bad sidecar does not hide the others.
+        Malformed input (a blobs / commitments length mismatch, a wrong blob or point length) raises
+        before anything is sent."""
+        what = "verifyAggregateKzgProof"
+        offsets, blobs, comms, proofs = [0], [], [], []
+        for sc_blobs, sc_comms, proof in sidecars:
+            if len(sc_blobs) != len(sc_comms):
+                raise KzgError(f"{what}: blobs / commitments length mismatch")
+            if len(proof) != 48 or any(len(c) != 48 for c in sc_comms):
+                raise KzgError(f"{what}: 48-byte commitments and proof")
+            blobs += list(sc_blobs)
+            comms += [bytes(c) for c in sc_comms]
+            proofs.append(bytes(proof))
+            offsets.append(len(blobs))
+        n = len(proofs)
+        if n == 0:
+            return []
+        u8, i32 = ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_int32)
+        src = self._blob_bytes(blobs)
+        cm = np.frombuffer(b"".join(comms) or b"\x00", np.uint8)
+        pf = np.frombuffer(b"".join(proofs), np.uint8)
+        off = np.asarray(offsets, np.uint32)
+        ok = np.zeros(n, np.int32)
+        self._check(self.lib.lb_kzg_verify_aggregate_proof_batch(
+            self.engine.h, n, off.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), src.ctypes.data_as(u8),
+            cm.ctypes.data_as(u8), pf.ctypes.data_as(u8), ok.ctypes.data_as(i32)), f"{what}Batch")
+        return [KzgError(f"{what}: {self._N.error_name(-int(v))}") if v < 0 else bool(v == 1) for v in ok]
+
     # the ckzg names kzg.ts binds
+    verifyAggregateKzgProofBatch = verify_aggregate_kzg_proof_batch
     blobToKzgCommitment = blob_to_kzg_commitment
     computeAggregateKzgProof = compute_aggregate_kzg_proof
     verifyAggregateKzgProof = verify_aggregate_kzg_proof
