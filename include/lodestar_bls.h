@@ -287,6 +287,39 @@ int32_t lb_kzg_verify_aggregate_proof_batch(lb_engine* e, uint32_t n_sidecars,
 uint64_t lb_kzg_batch_hash_ns(const lb_engine* e);
 
 /*
+ * One proof per blob: the form of EIP-4844 that shipped in Deneb (c-kzg computeBlobKzgProof,
+ * verifyBlobKzgProof, verifyBlobKzgProofBatch).  Both calls need the 4096-point setup and take at
+ * most 1024 blobs (and 1024 groups); LB_ERR_ARGUMENT otherwise, or for a needed pointer that is NULL.
+ * The challenge of blob i is z_i = hash_to_bls_field(FS_DOMAIN || 4096 as 16 bytes BE || blob_i ||
+ * C_i), hashed on up to LB_KZG_HASH_THREADS host threads (environment, default 8, at most 16).
+ * Byte parity with c-kzg is not pinned, as for the calls above.
+ *
+ * lb_kzg_compute_blob_proofs: out_proofs48[b] = commit((p_b - p_b(z_b)) / (X - z_b)) for every blob
+ * and its commitment (which must decode and lie in G1; infinity is allowed).  out_status[b] = LB_OK,
+ * the commitment's decode / group error, or LB_BAD_SCALAR for a blob element >= r; the proof of a
+ * rejected blob is zeroed.  Returns LB_OK whenever the call ran.
+ *
+ * lb_kzg_verify_blob_proof_batch: one group is one verifyBlobKzgProofBatch call (one block's
+ * sidecars).  Group k owns blobs group_offsets[k] .. group_offsets[k + 1] - 1 with their commitments
+ * and proofs, one proof per blob, and gets its own exact check with the spec's combiner
+ *   r = hash_to_bls_field(RC_DOMAIN || 4096, n as 8 bytes BE each || per blob: C_i || z_i || y_i || proof_i):
+ *   e(sum r^i C_i - [sum r^i y_i] G1 + sum [r^i z_i] proof_i, -G2) e(sum r^i proof_i, [tau] G2) == 1.
+ * out_ok[k] = 1, 0, or -code: the lowest blob index with any error wins, and within a blob the
+ * commitment's decode / group error, then -LB_BAD_SCALAR for a blob element >= r, then the proof's
+ * error.  An empty group gives 1; a rejecting group changes nothing for the others; the verdicts
+ * are deterministic (no random combination across groups).  Argument errors as for
+ * lb_kzg_verify_aggregate_proof_batch.  lb_kzg_batch_hash_ns reports this call's hashing time too.
+ */
+int32_t lb_kzg_compute_blob_proofs(lb_engine* e, uint32_t n_blobs, const uint8_t* blobs, /* n_blobs x 131072 B */
+                                   const uint8_t* commitments48, uint8_t* out_proofs48, int32_t* out_status);
+int32_t lb_kzg_verify_blob_proof_batch(lb_engine* e, uint32_t n_groups,
+                                       const uint32_t* group_offsets, /* n_groups + 1 prefix sums over blobs */
+                                       const uint8_t* blobs,          /* group_offsets[n] x 131072 B */
+                                       const uint8_t* commitments48,  /* group_offsets[n] x 48 B */
+                                       const uint8_t* proofs48,       /* group_offsets[n] x 48 B */
+                                       int32_t* out_ok);              /* n_groups */
+
+/*
  * Synthetic-data helpers for tests and the benchmark (not on the verification path):
  * SecretKey.toPublicKey and SecretKey.sign as used by the reference's own tests
  * (test/e2e/chain/bls/multithread.test.ts:28-31).  Secret keys are 32-byte big-endian < r.

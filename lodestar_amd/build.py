@@ -166,6 +166,26 @@ def build_kzg_batch_harness(force=False, verbose=True):
     return KZG_BATCH_HARNESS
 
 
+KZG_BLOB_HARNESS = os.path.join(ROOT, "build", "lb_kzg_blob_harness.so")
+
+
+def build_kzg_blob_harness(force=False, verbose=True):
+    """the transcripts, the many-polynomial quotient scan and the status fold of the per-blob KZG
+    calls on the CPU (tests/test_kzg_blob_cpu.py)"""
+    hdir = os.path.join(ROOT, "tests", "harness")
+    src = os.path.join(hdir, "lb_kzg_blob_harness.cpp")
+    os.makedirs(os.path.dirname(KZG_BLOB_HARNESS), exist_ok=True)
+    if not force and not _stale(KZG_BLOB_HARNESS, _deps() + [src, os.path.join(hdir, "kzg_blob_lanes.h")]):
+        return KZG_BLOB_HARNESS
+    cmd = ["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-pthread", "-I" + INC, "-I" + CSRC, src,
+           "-o", KZG_BLOB_HARNESS + ".tmp"]
+    if verbose:
+        print("[build]", " ".join(cmd), flush=True)
+    subprocess.run(cmd, check=True)
+    os.replace(KZG_BLOB_HARNESS + ".tmp", KZG_BLOB_HARNESS)
+    return KZG_BLOB_HARNESS
+
+
 def build_cpu_pool(force=False, verbose=True):
     src = os.path.join(ROOT, "oracle", "cpu_pool.cpp")
     if not os.path.exists(src):
@@ -227,6 +247,7 @@ def build_all(force=False):
     build_comb_harness(force)
     build_fr_harness(force)
     build_kzg_batch_harness(force)
+    build_kzg_blob_harness(force)
     build_cpu_pool(force)
     build_ubench(force)
 

@@ -24,6 +24,7 @@
 #include "lb_kernels.h"
 #include "lb_kzg.h"
 #include "lb_kzg_field.h"
+#include "lb_kzg_transcript.h"
 #include "lb_kdecl.h"  // kernels of the other translation units (split build)
 
 #define LB_ABI_VERSION 1
@@ -2458,48 +2459,6 @@ extern "C" int32_t lb_kzg_verify_proof(lb_engine* e, const uint8_t* commitment48
 
 // ---------------------------------------------------------------- KZG, blob level (lb_kzg_field.h)
 namespace {
-// SHA-256 of the Fiat-Shamir transcript, streamed through lb_h2c.h's sha256_compress on the host
-struct sha_stream {
-  uint32_t h[8];
-  uint8_t buf[64];
-  size_t fill = 0;
-  uint64_t total = 0;
-  sha_stream() { sha256_init(h); }
-  void block(const uint8_t* b) {
-    uint32_t w[16];
-    for (int i = 0; i < 16; i++)
-      w[i] = ((uint32_t)b[4 * i] << 24) | ((uint32_t)b[4 * i + 1] << 16) | ((uint32_t)b[4 * i + 2] << 8) | b[4 * i + 3];
-    sha256_compress(h, w);
-  }
-  void update(const uint8_t* d, size_t n) {
-    total += n;
-    if (fill) {
-      const size_t k = std::min(n, sizeof(buf) - fill);
-      memcpy(buf + fill, d, k);
-      fill += k;
-      d += k;
-      n -= k;
-      if (fill < sizeof(buf)) return;
-      block(buf);
-      fill = 0;
-    }
-    for (; n >= 64; d += 64, n -= 64) block(d);
-    if (n) memcpy(buf, d, n);
-    fill = n;
-  }
-  void finish(uint8_t out[32]) {
-    const uint64_t bits = total * 8;
-    uint8_t pad[72] = {0x80};
-    const size_t padn = (fill < 56 ? 56 : 120) - fill;
-    uint8_t len[8];
-    for (int i = 0; i < 8; i++) len[i] = (uint8_t)(bits >> (56 - 8 * i));
-    update(pad, padn);
-    update(len, 8);
-    for (int i = 0; i < 8; i++)
-      for (int k = 0; k < 4; k++) out[4 * i + k] = (uint8_t)(h[i] >> (24 - 8 * k));
-  }
-};
-
 // hash_to_bls_field(h || tag): SHA-256, read as a big-endian integer, mod r (Montgomery form)
 fr kzg_hash_to_field(const uint8_t h[32], uint8_t tag) {
   sha_stream s;
@@ -2534,6 +2493,11 @@ void kzg_challenges(uint32_t n, const uint8_t* blobs, const uint8_t* commitments
 
 constexpr size_t kBlobBytes = (size_t)LB_FR_N * 32;
 constexpr uint32_t kMaxBlobs = 1024;  // per call (the spec's MAX_BLOBS_PER_BLOCK is 4)
+// the compressed G1 generator: the point whose scalar is y in the batched checks' k_g1_terms launch
+const uint8_t kG1Gen48[48] = {0x97, 0xf1, 0xd3, 0xa7, 0x31, 0x97, 0xd7, 0x94, 0x26, 0x95, 0x63, 0x8c,
+                              0x4f, 0xa9, 0xac, 0x0f, 0xc3, 0x68, 0x8c, 0x4f, 0x97, 0x74, 0xb9, 0x05,
+                              0xa1, 0x4e, 0x3a, 0x3f, 0x17, 0x1b, 0xac, 0x58, 0x6c, 0x55, 0xe8, 0x3f,
+                              0xf9, 0x7a, 0x1a, 0xef, 0xfb, 0x3a, 0xf0, 0x0a, 0xdb, 0x22, 0xc6, 0xbb};
 
 // device workspace of one blob-level call, freed when it returns.  Field elements: 8 words each.
 struct kzg_ws {
@@ -2813,10 +2777,6 @@ extern "C" int32_t lb_kzg_verify_aggregate_proof_batch(lb_engine* e, uint32_t n,
     if (blob_offsets[k + 1] < blob_offsets[k]) return LB_ERR_ARGUMENT;
   const uint32_t nb = blob_offsets[n];
   if (nb > kMaxBlobs || (nb && (!blobs || !commitments48))) return LB_ERR_ARGUMENT;
-  static const uint8_t kG1Gen48[48] = {0x97, 0xf1, 0xd3, 0xa7, 0x31, 0x97, 0xd7, 0x94, 0x26, 0x95, 0x63, 0x8c,
-                                       0x4f, 0xa9, 0xac, 0x0f, 0xc3, 0x68, 0x8c, 0x4f, 0x97, 0x74, 0xb9, 0x05,
-                                       0xa1, 0x4e, 0x3a, 0x3f, 0x17, 0x1b, 0xac, 0x58, 0x6c, 0x55, 0xe8, 0x3f,
-                                       0xf9, 0x7a, 0x1a, 0xef, 0xfb, 0x3a, 0xf0, 0x0a, 0xdb, 0x22, 0xc6, 0xbb};
   const uint32_t n_pts = nb + 2 * n;
   std::lock_guard<std::mutex> lk(e->mu);
   kzg_ws w;
@@ -2891,6 +2851,189 @@ extern "C" int32_t lb_kzg_verify_aggregate_proof_batch(lb_engine* e, uint32_t n,
                      e->kzg_g2.as<uint32_t>(), w.ok.as<int32_t>());
   LB_KZG_TRY(hipGetLastError());
   // 8. the verdicts
+  LB_KZG_TRY(hipMemcpyAsync(out_ok, w.ok.p, (size_t)n * 4, hipMemcpyDeviceToHost, e->stream));
+  LB_KZG_TRY(hipStreamSynchronize(e->stream));
+  return LB_OK;
+}
+
+// ---------------------------------------------------------------- KZG, one proof per blob (Deneb)
+namespace {
+// host threads that hash the per-blob challenges: LB_KZG_HASH_THREADS, default 8, 1 .. 16
+uint32_t kzg_hash_threads() {
+  const char* s = getenv("LB_KZG_HASH_THREADS");
+  const long v = s && *s ? strtol(s, nullptr, 10) : 8;
+  return (uint32_t)std::min<long>(16, std::max<long>(1, v));
+}
+uint64_t kzg_ns_since(const std::chrono::steady_clock::time_point& t0) {
+  return (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
+}
+}  // namespace
+
+// compute_blob_kzg_proof for n_blobs blobs: every stage once over all of them, the 4096-term
+// commitment to each quotient as in kzg_commit, one synchronisation at the end.
+extern "C" int32_t lb_kzg_compute_blob_proofs(lb_engine* e, uint32_t n_blobs, const uint8_t* blobs,
+                                              const uint8_t* commitments48, uint8_t* out_proofs48, int32_t* out_status) {
+  if (!kzg_ready(e) || n_blobs > kMaxBlobs) return LB_ERR_ARGUMENT;
+  if (!n_blobs) return LB_OK;
+  if (!blobs || !commitments48 || !out_proofs48 || !out_status) return LB_ERR_ARGUMENT;
+  const uint32_t n = n_blobs;
+  std::lock_guard<std::mutex> lk(e->mu);
+  kzg_ws w;
+  LB_KZG_TRY(hipSetDevice(e->device));
+  LB_KZG_TRY(w.blobs.ensure(n * kBlobBytes));
+  LB_KZG_TRY(w.polys.ensure(n * kBlobBytes));
+  LB_KZG_TRY(w.coef.ensure(n * kBlobBytes));
+  LB_KZG_TRY(w.le.ensure(n * kBlobBytes));
+  LB_KZG_TRY(w.status.ensure((size_t)n * 4));
+  LB_KZG_TRY(w.pts.ensure((size_t)n * 48));
+  LB_KZG_TRY(w.pw_le.ensure((size_t)n * sizeof(fr)));
+  LB_KZG_TRY(w.agg.ensure((size_t)n * sizeof(g1j)));  // the validation launch's terms (unused)
+  LB_KZG_TRY(w.ok.ensure((size_t)n * 4));             // ... and its statuses: the commitments'
+  LB_KZG_TRY(w.z.ensure((size_t)n * sizeof(fr)));
+  LB_KZG_TRY(w.yz.ensure((size_t)n * sizeof(fr)));
+  LB_KZG_TRY(w.io.ensure((size_t)n * 48));
+  LB_KZG_TRY(w.terms.ensure((size_t)LB_FR_N * sizeof(g1j)));
+  LB_KZG_TRY(w.part.ensure((size_t)(LB_FR_N / 64) * sizeof(g1j)));
+  LB_KZG_TRY(w.tstatus.ensure((size_t)LB_FR_N * 4));
+  // 1. the blobs go up and are decoded; 2. the commitments are decoded and subgroup-checked (unit
+  // scalars) while the host hashes the challenges
+  LB_KZG_TRY(hipMemcpyAsync(w.blobs.p, blobs, n * kBlobBytes, hipMemcpyHostToDevice, e->stream));
+  LB_KZG_TRY(hipMemsetAsync(w.status.p, 0, (size_t)n * 4, e->stream));
+  const uint32_t n_elems = n * LB_FR_N;
+  hipLaunchKernelGGL(k_fr_blob_load, dim3((n_elems + 255) / 256), dim3(256), 0, e->stream, n_elems, w.blobs.as<uint8_t>(),
+                     w.polys.as<uint32_t>(), w.status.as<int32_t>());
+  LB_KZG_TRY(hipGetLastError());
+  std::vector<fr> ones(n), zs(n);
+  for (uint32_t b = 0; b < n; b++) {
+    ones[b] = fr_zero();
+    ones[b].l[0] = 1;
+  }
+  LB_KZG_TRY(hipMemcpyAsync(w.pts.p, commitments48, (size_t)n * 48, hipMemcpyHostToDevice, e->stream));
+  LB_KZG_TRY(hipMemcpyAsync(w.pw_le.p, ones.data(), (size_t)n * sizeof(fr), hipMemcpyHostToDevice, e->stream));
+  hipLaunchKernelGGL(k_g1_terms, dim3(nblk(n)), dim3(LB_TPB), 0, e->stream, n, w.pts.as<uint8_t>(), e->kzg_g1.as<uint32_t>(),
+                     e->kzg_n, w.pw_le.as<uint32_t>(), w.agg.as<uint32_t>(), w.ok.as<int32_t>());
+  LB_KZG_TRY(hipGetLastError());
+  kzg_blob_challenges(n, blobs, commitments48, zs.data(), kzg_hash_threads());
+  LB_KZG_TRY(hipMemcpyAsync(w.z.p, zs.data(), (size_t)n * sizeof(fr), hipMemcpyHostToDevice, e->stream));
+  // 3. coefficients; 4. y_b and the quotients' scalars; 5. their commitments
+  const int32_t rc = kzg_intt(e, n, w.polys.as<uint32_t>(), w.coef.as<uint32_t>(), nullptr);
+  if (rc != LB_OK) return rc;
+  hipLaunchKernelGGL(k_fr_eval_quotient_many, dim3(n), dim3(LB_FR_WG), LB_FR_EQ_LDS, e->stream, w.coef.as<uint32_t>(),
+                     w.z.as<uint32_t>(), w.le.as<uint32_t>(), w.yz.as<uint32_t>());
+  LB_KZG_TRY(hipGetLastError());
+  for (uint32_t b = 0; b < n; b++)
+    g1_lincomb_launch(e, LB_FR_N, nullptr, w.le.as<uint32_t>() + (size_t)b * LB_FR_N * 8, w.terms.as<uint32_t>(),
+                      w.part.as<uint32_t>(), w.tstatus.as<int32_t>(), w.io.as<uint8_t>() + (size_t)48 * b);
+  LB_KZG_TRY(hipGetLastError());
+  // 6. proofs and statuses
+  std::vector<int32_t> bst(n, LB_OK), cst(n, LB_OK);
+  LB_KZG_TRY(hipMemcpyAsync(out_proofs48, w.io.p, (size_t)n * 48, hipMemcpyDeviceToHost, e->stream));
+  LB_KZG_TRY(hipMemcpyAsync(bst.data(), w.status.p, (size_t)n * 4, hipMemcpyDeviceToHost, e->stream));
+  LB_KZG_TRY(hipMemcpyAsync(cst.data(), w.ok.p, (size_t)n * 4, hipMemcpyDeviceToHost, e->stream));
+  LB_KZG_TRY(hipStreamSynchronize(e->stream));
+  for (uint32_t b = 0; b < n; b++) {
+    out_status[b] = cst[b] != LB_OK ? cst[b] : bst[b];
+    if (out_status[b] != LB_OK) memset(out_proofs48 + (size_t)48 * b, 0, 48);
+  }
+  return LB_OK;
+}
+
+// verify_blob_kzg_proof_batch for many groups in one pass: every stage once over all blobs, two
+// synchronisations (the combiner r_k hashes the y_i, which the device computes).  Device arrays in
+// k_kzg_check_groups' order: the commitments, the proofs twice, one G1 generator per group.
+extern "C" int32_t lb_kzg_verify_blob_proof_batch(lb_engine* e, uint32_t n_groups, const uint32_t* group_offsets,
+                                                  const uint8_t* blobs, const uint8_t* commitments48,
+                                                  const uint8_t* proofs48, int32_t* out_ok) {
+  const uint32_t n = n_groups;
+  if (!kzg_ready(e) || n > 1024) return LB_ERR_ARGUMENT;
+  if (!n) return LB_OK;
+  if (!group_offsets || !out_ok || group_offsets[0] != 0) return LB_ERR_ARGUMENT;
+  for (uint32_t k = 0; k < n; k++)
+    if (group_offsets[k + 1] < group_offsets[k]) return LB_ERR_ARGUMENT;
+  const uint32_t nb = group_offsets[n];
+  if (nb > kMaxBlobs || (nb && (!blobs || !commitments48 || !proofs48))) return LB_ERR_ARGUMENT;
+  const uint32_t n_pts = 3 * nb + n;
+  std::lock_guard<std::mutex> lk(e->mu);
+  kzg_ws w;
+  LB_KZG_TRY(hipSetDevice(e->device));
+  LB_KZG_TRY(w.blobs.ensure(std::max<size_t>(nb, 1) * kBlobBytes));
+  LB_KZG_TRY(w.polys.ensure(std::max<size_t>(nb, 1) * kBlobBytes));
+  LB_KZG_TRY(w.coef.ensure(std::max<size_t>(nb, 1) * kBlobBytes));
+  LB_KZG_TRY(w.status.ensure(std::max<size_t>(nb, 1) * 4));
+  LB_KZG_TRY(w.z.ensure(std::max<size_t>(nb, 1) * sizeof(fr)));
+  LB_KZG_TRY(w.yz.ensure(std::max<size_t>(nb, 1) * sizeof(fr)));
+  LB_KZG_TRY(w.pts.ensure((size_t)n_pts * 48));
+  LB_KZG_TRY(w.le.ensure((size_t)n_pts * 32));
+  LB_KZG_TRY(w.terms.ensure((size_t)n_pts * sizeof(g1j)));
+  LB_KZG_TRY(w.tstatus.ensure((size_t)n_pts * 4));
+  LB_KZG_TRY(w.off.ensure((size_t)(n + 1) * 4));
+  LB_KZG_TRY(w.ok.ensure((size_t)n * 4));
+  LB_KZG_TRY(hipMemcpyAsync(w.off.p, group_offsets, (size_t)(n + 1) * 4, hipMemcpyHostToDevice, e->stream));
+  // the host arrays live until the last synchronisation
+  std::vector<fr> zs(std::max<uint32_t>(nb, 1)), ys(std::max<uint32_t>(nb, 1)), y_le(std::max<uint32_t>(nb, 1)), sc(n_pts);
+  uint64_t hash_ns = 0;
+  if (nb) {
+    // 1. the blobs go up and are decoded while 2. the host threads hash the z_i
+    LB_KZG_TRY(hipMemcpyAsync(w.blobs.p, blobs, nb * kBlobBytes, hipMemcpyHostToDevice, e->stream));
+    LB_KZG_TRY(hipMemsetAsync(w.status.p, 0, (size_t)nb * 4, e->stream));
+    const uint32_t n_elems = nb * LB_FR_N;
+    hipLaunchKernelGGL(k_fr_blob_load, dim3((n_elems + 255) / 256), dim3(256), 0, e->stream, n_elems,
+                       w.blobs.as<uint8_t>(), w.polys.as<uint32_t>(), w.status.as<int32_t>());
+    LB_KZG_TRY(hipGetLastError());
+    const auto h0 = std::chrono::steady_clock::now();
+    kzg_blob_challenges(nb, blobs, commitments48, zs.data(), kzg_hash_threads());
+    hash_ns += kzg_ns_since(h0);
+    // 3. coefficients, y_i = p_i(z_i), back to the host: the first synchronisation
+    LB_KZG_TRY(hipMemcpyAsync(w.z.p, zs.data(), (size_t)nb * sizeof(fr), hipMemcpyHostToDevice, e->stream));
+    const int32_t rc = kzg_intt(e, nb, w.polys.as<uint32_t>(), w.coef.as<uint32_t>(), nullptr);
+    if (rc != LB_OK) return rc;
+    hipLaunchKernelGGL(k_fr_eval_many, dim3(nb), dim3(LB_FR_WG), LB_FR_EV_LDS, e->stream, w.coef.as<uint32_t>(),
+                       w.z.as<uint32_t>(), w.yz.as<uint32_t>());
+    LB_KZG_TRY(hipGetLastError());
+    LB_KZG_TRY(hipMemcpyAsync(y_le.data(), w.yz.p, (size_t)nb * sizeof(fr), hipMemcpyDeviceToHost, e->stream));
+    LB_KZG_TRY(hipStreamSynchronize(e->stream));
+    for (uint32_t j = 0; j < nb; j++) ys[j] = fr_to_mont(y_le[j]);
+  }
+  // 4. r_k per group and the scalars r^i, r^i z_i, sum r^i y_i
+  for (uint32_t k = 0; k < n; k++) {
+    const uint32_t lo = group_offsets[k], cnt = group_offsets[k + 1] - lo;
+    fr r = fr_one();
+    if (cnt > 1) {  // r^0 = 1 alone is used otherwise: verify_blob_kzg_proof
+      const auto h0 = std::chrono::steady_clock::now();
+      r = kzg_batch_r(cnt, commitments48 + (size_t)48 * lo, zs.data() + lo, ys.data() + lo, proofs48 + (size_t)48 * lo);
+      hash_ns += kzg_ns_since(h0);
+    }
+    fr p = fr_one(), ysum = fr_zero();
+    for (uint32_t i = 0; i < cnt; i++) {
+      const uint32_t j = lo + i;
+      fr_to_le_words(sc[j].l, p);
+      fr_to_le_words(sc[nb + j].l, fr_mul(p, zs[j]));
+      sc[2 * nb + j] = sc[j];
+      ysum = fr_add(ysum, fr_mul(p, ys[j]));
+      p = fr_mul(p, r);
+    }
+    fr_to_le_words(sc[3 * nb + k].l, ysum);
+  }
+  e->kzg_batch_hash_ns = hash_ns;
+  std::vector<uint8_t> pts((size_t)n_pts * 48);
+  if (nb) {
+    memcpy(pts.data(), commitments48, (size_t)nb * 48);
+    memcpy(pts.data() + (size_t)nb * 48, proofs48, (size_t)nb * 48);
+    memcpy(pts.data() + (size_t)2 * nb * 48, proofs48, (size_t)nb * 48);
+  }
+  for (uint32_t k = 0; k < n; k++) memcpy(pts.data() + (size_t)(3 * nb + k) * 48, kG1Gen48, 48);
+  LB_KZG_TRY(hipMemcpyAsync(w.le.p, sc.data(), (size_t)n_pts * sizeof(fr), hipMemcpyHostToDevice, e->stream));
+  LB_KZG_TRY(hipMemcpyAsync(w.pts.p, pts.data(), pts.size(), hipMemcpyHostToDevice, e->stream));
+  // 5. every ladder and subgroup check of the call in one launch
+  hipLaunchKernelGGL(k_g1_terms, dim3(nblk(n_pts)), dim3(LB_TPB), 0, e->stream, n_pts, w.pts.as<uint8_t>(),
+                     e->kzg_g1.as<uint32_t>(), e->kzg_n, w.le.as<uint32_t>(), w.terms.as<uint32_t>(),
+                     w.tstatus.as<int32_t>());
+  LB_KZG_TRY(hipGetLastError());
+  // 6. one wave per group: status, T_k and P_k, the two-pair product; the second synchronisation
+  hipLaunchKernelGGL(k_kzg_check_groups, dim3(n), dim3(64), 0, e->stream, n, w.off.as<uint32_t>(), nb,
+                     w.status.as<int32_t>(), w.terms.as<uint32_t>(), w.tstatus.as<int32_t>(), e->kzg_g2.as<uint32_t>(),
+                     w.ok.as<int32_t>());
+  LB_KZG_TRY(hipGetLastError());
   LB_KZG_TRY(hipMemcpyAsync(out_ok, w.ok.p, (size_t)n * 4, hipMemcpyDeviceToHost, e->stream));
   LB_KZG_TRY(hipStreamSynchronize(e->stream));
   return LB_OK;

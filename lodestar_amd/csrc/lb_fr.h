@@ -294,6 +294,20 @@ LB_HD fr fr_seg_aggregate(const P& poly, const W& pw, uint32_t lo, uint32_t hi, 
   return acc;
 }
 
+// kzg_group_status: the status of one group of the per-blob proof form (k_kzg_check_groups,
+// lb_kzg_verify_blob_proof_batch) over its blobs lo <= j < hi of n_blobs, in the order the spec's
+// loop reads them: the lowest blob index with any error wins, and within a blob the commitment
+// (tstatus[j]), then a blob element >= r (bstatus[j]), then the proof (tstatus[2 n_blobs + j]: the
+// term that carries the proof's decode and subgroup result).  LB_OK for an empty group.
+LB_HD int kzg_group_status(const int32_t* bstatus, const int32_t* tstatus, uint32_t n_blobs, uint32_t lo, uint32_t hi) {
+  for (uint32_t j = lo; j < hi; j++) {
+    if (tstatus[j] != LB_OK) return tstatus[j];
+    if (bstatus[j] != LB_OK) return LB_BAD_SCALAR;
+    if (tstatus[2 * n_blobs + j] != LB_OK) return tstatus[2 * n_blobs + j];
+  }
+  return LB_OK;
+}
+
 // Evaluation alone, y = p(z), where the quotient of fr_eq_* is not wanted: lane t of n / 4 takes
 // its four coefficients by Horner (fr_eq_local: L[t] = sum_k a[4 t + k] z^k), then
 // y = sum_t L[t] z^(4 t) folds in halves: for s = log2(n / 4) - 1 down to 0, with h = 2^s, lane

@@ -13,6 +13,7 @@
 // commitment to p(X) = sum a_i X^i is sum a_i [tau^i] G1, the same point as the spec's Lagrange
 // form sum p(w_i) L_i(tau) G1) as a g1a SoA table; [tau^0] G2 and [tau^1] G2 as two g2a.
 #pragma once
+#include "lb_fr.h"  // kzg_group_status
 #include "lb_kernels.h"
 
 // [r] P == O for an affine G1 point (r = the BLS12-381 subgroup order): the G1 subgroup check of
@@ -299,6 +300,110 @@ __global__ void __launch_bounds__(64) k_kzg_check_many(uint32_t n, const uint32_
     const g2a g1t = G[1];
     w_st(S, LBW_PT + 0, pi.x);
     w_st(S, LBW_PT + 1, pi.y);
+    w_st(S, LBW_PT + 2, g1t.x.c0);
+    w_st(S, LBW_PT + 3, g1t.x.c1);
+    w_st(S, LBW_PT + 4, g1t.y.c0);
+    w_st(S, LBW_PT + 5, g1t.y.c1);
+  }
+  __syncthreads();
+  if (pinf_u)
+    w_set_one(S, LBW_A(7));
+  else
+    w_miller(S, LBW_A(7));
+  w_mul(S, LBW_A(0), LBW_A(0), LBW_A(7));
+  w_final_exp(S, LBW_A(0), LBW_A(0));
+  const bool one = w_is_one(S, LBW_A(0));
+  if (lane == 0) ok[k] = one ? 1 : 0;
+}
+#endif  // LB_KG
+
+// The per-blob proof form (Deneb's verify_blob_kzg_proof_batch; lb_kzg_verify_blob_proof_batch): one
+// wave per group k, which owns blobs off[k] .. off[k + 1] - 1 of n_blobs, each with its own
+// commitment C_j and proof pi_j.  With r the group's combiner and i = j - off[k], the ladders ran
+// before, in one k_g1_terms launch over 3 n_blobs + n points:
+//   [0, n_blobs)              C_j,   scalar r^i
+//   n_blobs + j               pi_j,  scalar r^i z_j
+//   2 n_blobs + j             pi_j,  scalar r^i
+//   3 n_blobs + k             the G1 generator, scalar sum_i r^i y_j
+// (terms as a g1j SoA of that many entries, tstatus).  Here: the group's status (lb_fr.h
+// kzg_group_status: lowest blob first; commitment, blob element, proof), then
+//   T = sum [r^i] C_j + sum [r^i z_j] pi_j - [sum r^i y_j] G1,   P = sum [r^i] pi_j
+// and e(T, -G2) e(P, [tau] G2) == 1 on the wave engine; either point may be infinity (constant blobs
+// with infinity proofs make T infinity), an empty group accepts.  ok[k] = 1 / 0, or -code; a group
+// with a bad status never reaches the pairing.  The offsets are clamped to n_blobs and to each
+// other before anything is indexed by them.
+#if LB_KG(5)
+__global__ void __launch_bounds__(64) k_kzg_check_groups(uint32_t n, const uint32_t* __restrict__ off, uint32_t n_blobs,
+                                                         const int32_t* __restrict__ bstatus, const uint32_t* __restrict__ terms,
+                                                         const int32_t* __restrict__ tstatus, const uint32_t* __restrict__ g2,
+                                                         int32_t* __restrict__ ok) {
+  LBW_SHARED_ML(S);
+  __shared__ int st_sh, qinf_sh, pinf_sh;
+  const int lane = threadIdx.x;
+  const uint32_t k = blockIdx.x;
+  if (k >= n) return;
+  w_init_consts(S, LBW_PROGS_ALL);
+  const uint32_t n_pts = 3 * n_blobs + n, i_g = 3 * n_blobs + k;
+  const uint32_t hi = min(off[k + 1], n_blobs), lo = min(off[k], hi);
+  const uint32_t m = hi - lo;
+  // T: the group's C terms, its z pi terms, then the generator term (subtracted); 64 at a time
+  g1j v = jac_infinity<fp>();
+  for (uint32_t q = lane; q < 2 * m + 1; q += 64) {
+    const uint32_t idx = q < m ? lo + q : (q < 2 * m ? n_blobs + lo + (q - m) : i_g);
+    g1j t = soa_ld<g1j>(terms, n_pts, idx);
+    if (q == 2 * m) t = jac_neg(t);
+    v = jac_add_i(v, t);
+  }
+  for (int l = 5; l >= 0; l--) {
+    const unsigned d = 1u << l;
+    const g1j o{fp_shfl_down(v.x, d), fp_shfl_down(v.y, d), fp_shfl_down(v.z, d)};
+    if (threadIdx.x < d) v = jac_add_i(v, o);
+  }
+  // P: the group's pi terms
+  g1j u = jac_infinity<fp>();
+  for (uint32_t q = lane; q < m; q += 64) u = jac_add_i(u, soa_ld<g1j>(terms, n_pts, 2 * n_blobs + lo + q));
+  for (int l = 5; l >= 0; l--) {
+    const unsigned d = 1u << l;
+    const g1j o{fp_shfl_down(u.x, d), fp_shfl_down(u.y, d), fp_shfl_down(u.z, d)};
+    if (threadIdx.x < d) u = jac_add_i(u, o);
+  }
+  g1a pa;
+  if (lane == 0) {
+    const int st = kzg_group_status(bstatus, tstatus, n_blobs, lo, hi);
+    bool qfin = false, pfin = false;
+    if (st == LB_OK) {
+      g1a qa;
+      qfin = jac_to_aff(qa, v);
+      pfin = jac_to_aff(pa, u);
+      w_st(S, LBW_PT + 0, qa.x);
+      w_st(S, LBW_PT + 1, qa.y);
+      const g2a* G = reinterpret_cast<const g2a*>(g2);
+      const g2a g0 = G[0];
+      w_st(S, LBW_PT + 2, g0.x.c0);
+      w_st(S, LBW_PT + 3, g0.x.c1);
+      w_st(S, LBW_PT + 4, fp_neg(g0.y.c0));  // -G2
+      w_st(S, LBW_PT + 5, fp_neg(g0.y.c1));
+    }
+    st_sh = st;
+    qinf_sh = qfin ? 0 : 1;
+    pinf_sh = pfin ? 0 : 1;
+  }
+  __syncthreads();
+  const int st_u = st_sh, qinf = qinf_sh, pinf_u = pinf_sh;
+  __syncthreads();
+  if (st_u != LB_OK) {
+    if (lane == 0) ok[k] = -st_u;
+    return;
+  }
+  if (qinf)
+    w_set_one(S, LBW_A(0));
+  else
+    w_miller(S, LBW_A(0));
+  if (lane == 0) {
+    const g2a* G = reinterpret_cast<const g2a*>(g2);
+    const g2a g1t = G[1];
+    w_st(S, LBW_PT + 0, pa.x);
+    w_st(S, LBW_PT + 1, pa.y);
     w_st(S, LBW_PT + 2, g1t.x.c0);
     w_st(S, LBW_PT + 3, g1t.x.c1);
     w_st(S, LBW_PT + 4, g1t.y.c0);

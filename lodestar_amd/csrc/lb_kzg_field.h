@@ -203,3 +203,33 @@ __global__ void __launch_bounds__(LB_FR_WG) k_fr_eval_many(const uint32_t* __res
   }
 }
 #endif  // LB_KG
+
+// ------------------------------------------------------------------ one proof per blob
+// lb_kzg_compute_blob_proofs: k_fr_eval_quotient for many polynomials, one workgroup each, polynomial
+// k (coef + k * 4096 * 8, Montgomery) at its own point z_mont + 8 k.  The same suffix scan (lb_fr.h
+// fr_eq_*, two LDS buffers ping-ponging, LB_FR_EQ_LDS bytes of dynamic LDS); y_k leaves as 8 plain
+// LE words at y_le + 8 k and the quotient's 4096 scalars at q_le + k * 4096 * 8 (q[4095] = 0).
+// No division: z on the evaluation domain is no special case.
+#if LB_KG(16)
+__global__ void __launch_bounds__(LB_FR_WG) k_fr_eval_quotient_many(const uint32_t* __restrict__ coef, const uint32_t* __restrict__ z_mont,
+                                                                    uint32_t* __restrict__ q_le, uint32_t* __restrict__ y_le) {
+  extern __shared__ uint32_t lb_fr_lds[];
+  const uint32_t lanes = LB_FR_N / 4, t = threadIdx.x, k = blockIdx.x;
+  fr* src = reinterpret_cast<fr*>(lb_fr_lds);
+  fr* dst = src + lanes;
+  const fr_gpoly A{coef + (size_t)k * LB_FR_N * 8};
+  const fr z = fr_ldg(z_mont + (size_t)8 * k);
+  src[t] = fr_eq_local(A, z, t);
+  __syncthreads();
+  fr w = fr_eq_weight(z);
+  for (uint32_t d = 1; d < lanes; d *= 2) {
+    dst[t] = fr_eq_scan(src, lanes, d, w, t);
+    __syncthreads();
+    fr* x = src;
+    src = dst;
+    dst = x;
+    w = fr_sqr(w);
+  }
+  fr_eq_finish(A, z, src, lanes, t, q_le + (size_t)k * LB_FR_N * 8, y_le + (size_t)8 * k);
+}
+#endif  // LB_KG

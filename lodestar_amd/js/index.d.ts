@@ -90,6 +90,19 @@ export interface CKzg {
    * GPU, in either field mode: true, false, or the Error the single call would throw, per sidecar.
    */
   verifyAggregateKzgProofBatch(sidecars: KzgSidecar[]): (boolean | Error)[];
+  /** One proof per blob (Deneb), c-kzg's names and shapes; z and y are 32 big-endian bytes below r. */
+  computeBlobKzgProof(blob: Uint8Array, commitment: Uint8Array): Uint8Array;
+  verifyBlobKzgProof(blob: Uint8Array, commitment: Uint8Array, proof: Uint8Array): boolean;
+  verifyBlobKzgProofBatch(blobs: Uint8Array[], commitments: Uint8Array[], proofs: Uint8Array[]): boolean;
+  computeKzgProof(blob: Uint8Array, zBytes: Uint8Array): [Uint8Array, Uint8Array];
+  verifyKzgProof(commitment: Uint8Array, zBytes: Uint8Array, yBytes: Uint8Array, proof: Uint8Array): boolean;
+  /**
+   * verifyBlobKzgProofBatch for many groups (one group = one block's sidecars) in one pass over the
+   * GPU, in either field mode: true, false, or the Error the single call would throw, per group.
+   */
+  verifyBlobKzgProofBatchMany(groups: KzgBlobGroup[]): (boolean | Error)[];
   readonly G1_INFINITY48: Uint8Array;
 }
 export type KzgSidecar = {blobs: Uint8Array[]; commitments: Uint8Array[]; proof: Uint8Array};
+/** One verifyBlobKzgProofBatch call: one proof per blob. */
+export type KzgBlobGroup = {blobs: Uint8Array[]; commitments: Uint8Array[]; proofs: Uint8Array[]};

@@ -21,6 +21,10 @@
  *
  * verifyAggregateKzgProofBatch(sidecars) is not part of c-kzg: many sidecars (a range-sync segment's
  * blocks) in one pass over the GPU, one verdict per sidecar, in either field mode.
+ *
+ * The per-blob proof form that shipped in Deneb is here too, under c-kzg's names and shapes:
+ * computeBlobKzgProof, verifyBlobKzgProof, verifyBlobKzgProofBatch, computeKzgProof, verifyKzgProof,
+ * and verifyBlobKzgProofBatchMany(groups) for many blocks' sidecars in one pass (see below).
  */
 const crypto = require("crypto");
 const fs = require("fs");
@@ -281,13 +285,128 @@ function verifyAggregateKzgProofBatch(sidecars) {
   return Array.from(ok, (v) => (v < 0 ? Error(addon.errorName(-v)) : v === 1));
 }
 
+// ------------------------------------------------------------------ one proof per blob (Deneb)
+// The c-kzg surface of the shipped form of EIP-4844: computeBlobKzgProof, verifyBlobKzgProof,
+// verifyBlobKzgProofBatch, computeKzgProof, verifyKzgProof.  Every blob has its own transcript,
+//   z = hash_to_bls_field(FS_DOMAIN || 4096 as 16 bytes BE || blob || commitment),
+// and a batch its own combiner r (computeBatchR).  verifyBlobKzgProofBatch always runs on the GPU
+// (kzgVerifyBlobProofBatch -> lb_kzg_verify_blob_proof_batch); computeBlobKzgProof and
+// verifyBlobKzgProof honour the field mode and give the same bytes and verdicts in both.
+const RC_DOMAIN = Buffer.from("RCKZGBATCH___V1_", "ascii");
+
+function check48(p, what) {
+  if (!(p instanceof Uint8Array) || p.length !== 48) throw Error(what + " length != 48");
+}
+function computeChallenge(blob, commitment) {
+  checkBlob(blob);
+  check48(commitment, "commitment");
+  return hashToBlsField(Buffer.concat([DOMAIN, bigToBytes(BigInt(N), 16, false), Buffer.from(blob), Buffer.from(commitment)]));
+}
+function computeBatchR(commitments, zs, ys, proofs) {
+  const parts = [RC_DOMAIN, bigToBytes(BigInt(N), 8, false), bigToBytes(BigInt(commitments.length), 8, false)];
+  commitments.forEach((c, i) => {
+    parts.push(Buffer.from(c), bigToBytes(zs[i], 32, false), bigToBytes(ys[i], 32, false), Buffer.from(proofs[i]));
+  });
+  return hashToBlsField(Buffer.concat(parts));
+}
+function fieldElement(b, what) {
+  if (!(b instanceof Uint8Array) || b.length !== 32) throw Error(what + " length != 32");
+  const v = bytesToBig(b);
+  if (v >= R) throw Error("BLST_BAD_SCALAR");
+  return v;
+}
+// decodes and subgroup-checks a point given by the caller (throws the blst-style name)
+function validateG1(p) {
+  addon.g1Lincomb(engine, scalarsLE([1n]), p);
+}
+
+function computeBlobKzgProof(blob, commitment) {
+  requireSetup();
+  checkBlob(blob);
+  check48(commitment, "commitment");
+  if (field === "device") return addon.kzgComputeBlobProofs(engine, blob, commitment);
+  validateG1(commitment);
+  const coeffs = evaluationsToCoefficients(blobToPolynomial(blob));
+  return commitCoefficients(quotient(coeffs, computeChallenge(blob, commitment)));
+}
+
+// verifyBlobKzgProofBatch for many groups (one group = one block's sidecars) in one pass over the
+// GPU, in either field mode.  groups: {blobs, commitments, proofs}[], one proof per blob.  One entry
+// per group: true, false, or the Error the single call would throw -- returned, not thrown.
+// Malformed input throws before anything is sent.
+function verifyBlobKzgProofBatchMany(groups) {
+  requireSetup();
+  const offsets = new Uint32Array(groups.length + 1);
+  const allBlobs = [];
+  const allComms = [];
+  const allProofs = [];
+  groups.forEach((g, k) => {
+    if (g.blobs.length !== g.commitments.length || g.blobs.length !== g.proofs.length) {
+      throw Error("blobs / commitments / proofs length mismatch");
+    }
+    g.commitments.forEach((c) => check48(c, "commitment"));
+    g.proofs.forEach((p) => check48(p, "proof"));
+    allBlobs.push(...g.blobs);
+    allComms.push(...g.commitments);
+    allProofs.push(...g.proofs);
+    offsets[k + 1] = allBlobs.length;
+  });
+  if (!groups.length) return [];
+  const cm = new Uint8Array(48 * allComms.length);
+  const pr = new Uint8Array(48 * allProofs.length);
+  allComms.forEach((c, i) => cm.set(c, 48 * i));
+  allProofs.forEach((p, i) => pr.set(p, 48 * i));
+  const ok = addon.kzgVerifyBlobProofBatch(engine, concatBlobs(allBlobs), offsets, cm, pr);
+  return Array.from(ok, (v) => (v < 0 ? Error(addon.errorName(-v)) : v === 1));
+}
+function verifyBlobKzgProofBatch(blobs, commitments, proofs) {
+  const res = verifyBlobKzgProofBatchMany([{blobs, commitments, proofs}])[0];
+  if (res instanceof Error) throw res;
+  return res;
+}
+function verifyBlobKzgProof(blob, commitment, proof) {
+  requireSetup();
+  if (field === "device") return verifyBlobKzgProofBatch([blob], [commitment], [proof]);
+  checkBlob(blob);
+  check48(commitment, "commitment");
+  check48(proof, "proof");
+  validateG1(commitment); // the commitment's error comes before the blob's
+  const z = computeChallenge(blob, commitment);
+  const y = evaluate(evaluationsToCoefficients(blobToPolynomial(blob)), z);
+  return addon.kzgVerifyProof(engine, commitment, bigToBytes(z, 32, true), bigToBytes(y, 32, true), proof);
+}
+// computeKzgProof(blob, zBytes) -> [proof, yBytes] and verifyKzgProof(commitment, zBytes, yBytes,
+// proof): z and y as 32 big-endian bytes, each below r.  The field work of computeKzgProof is
+// BigInt in either mode (the addon binds no single-point proof call); the commitment to the
+// quotient and the pairing check run on the GPU.
+function computeKzgProof(blob, zBytes) {
+  requireSetup();
+  const z = fieldElement(zBytes, "z");
+  const coeffs = evaluationsToCoefficients(blobToPolynomial(blob));
+  return [commitCoefficients(quotient(coeffs, z)), new Uint8Array(bigToBytes(evaluate(coeffs, z), 32, false))];
+}
+function verifyKzgProof(commitment, zBytes, yBytes, proof) {
+  requireSetup();
+  check48(commitment, "commitment");
+  check48(proof, "proof");
+  const z = fieldElement(zBytes, "z");
+  const y = fieldElement(yBytes, "y");
+  return addon.kzgVerifyProof(engine, commitment, bigToBytes(z, 32, true), bigToBytes(y, 32, true), proof);
+}
+
 module.exports = {
   loadTrustedSetup,
   blobToKzgCommitment,
   computeAggregateKzgProof,
   verifyAggregateKzgProof,
   verifyAggregateKzgProofBatch,
+  computeBlobKzgProof,
+  verifyBlobKzgProof,
+  verifyBlobKzgProofBatch,
+  verifyBlobKzgProofBatchMany,
+  computeKzgProof,
+  verifyKzgProof,
   G1_INFINITY48,
   // host field work, exported for tests
-  _internal: {evaluationsToCoefficients, evaluate, quotient, computeChallenges, ROOTS, BRP, R},
+  _internal: {evaluationsToCoefficients, evaluate, quotient, computeChallenges, computeChallenge, computeBatchR, ROOTS, BRP, R},
 };

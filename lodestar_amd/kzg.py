@@ -21,6 +21,13 @@ Split, chosen per `Kzg(engine, field=...)`:
 Whatever `field` is, `verify_aggregate_kzg_proof_batch` checks many sidecars (a range-sync segment's
 blocks) in one pass over the GPU (`lb_kzg_verify_aggregate_proof_batch`), one verdict per sidecar.
 
+The per-blob proof form that shipped in Deneb (c-kzg `computeBlobKzgProof`, `verifyBlobKzgProof`,
+`verifyBlobKzgProofBatch`, `computeKzgProof`, `verifyKzgProof`) is here too: `compute_challenge` and
+`compute_batch_r` restate its two transcripts, `Kzg.compute_blob_kzg_proof` and
+`Kzg.verify_blob_kzg_proof` honour `field` (same bytes either way), and the batch calls
+(`verify_blob_kzg_proof_batch`, `verify_blob_kzg_proof_batch_many` for many blocks' sidecars in one
+pass) always run on the GPU (`lb_kzg_verify_blob_proof_batch`).
+
 The setup is Lodestar's own `trusted_setup.bin` (kzg.ts:36-48: two u32 counts, 4096 compressed
 [tau^i] G1, 65 compressed [tau^i] G2), i.e. MONOMIAL form (setup_G1[0] is the G1 generator).
 Committing in monomial form, sum a_j [tau^j] G1 with a = IFFT of the blob's evaluations, gives
@@ -166,6 +173,31 @@ def compute_challenges(polys: Sequence[Sequence[int]], commitments: Sequence[byt
         powers.append(x)
         x = x * r % BLS_MODULUS
     return powers, hash_to_bls_field(h + b"\x01")
+
+
+# -- one proof per blob (Deneb): each blob has its own transcript, and a batch its own combiner
+RANDOM_CHALLENGE_KZG_BATCH_DOMAIN = b"RCKZGBATCH___V1_"
+
+
+def compute_challenge(blob: bytes, commitment: bytes) -> int:
+    """z = hash_to_bls_field(domain || 4096 as 16 bytes || blob || commitment); no tag byte"""
+    if len(blob) != BYTES_PER_BLOB or len(commitment) != 48:
+        raise ValueError("compute_challenge: a 131072-byte blob and a 48-byte commitment")
+    return hash_to_bls_field(FIAT_SHAMIR_PROTOCOL_DOMAIN + FIELD_ELEMENTS_PER_BLOB.to_bytes(16, ENDIANNESS)
+                             + bytes(blob) + bytes(commitment))
+
+
+def compute_batch_r(commitments: Sequence[bytes], zs: Sequence[int], ys: Sequence[int], proofs: Sequence[bytes]) -> int:
+    """the combiner of verify_blob_kzg_proof_batch: domain || 4096 and n as 8 bytes each || per blob
+    commitment (48) || z (32) || y (32) || proof (48)"""
+    n = len(commitments)
+    if not (len(zs) == len(ys) == len(proofs) == n):
+        raise ValueError("compute_batch_r: one z, y and proof per commitment")
+    data = bytearray(RANDOM_CHALLENGE_KZG_BATCH_DOMAIN)
+    data += FIELD_ELEMENTS_PER_BLOB.to_bytes(8, ENDIANNESS) + n.to_bytes(8, ENDIANNESS)
+    for c, z, y, p in zip(commitments, zs, ys, proofs):
+        data += bytes(c) + int(z).to_bytes(32, ENDIANNESS) + int(y).to_bytes(32, ENDIANNESS) + bytes(p)
+    return hash_to_bls_field(bytes(data))
 
 
 def _scalars_le(vals: Sequence[int]) -> np.ndarray:
@@ -382,7 +414,109 @@ class Kzg:
             cm.ctypes.data_as(u8), pf.ctypes.data_as(u8), ok.ctypes.data_as(i32)), f"{what}Batch")
         return [KzgError(f"{what}: {self._N.error_name(-int(v))}") if v < 0 else bool(v == 1) for v in ok]
 
+    # -- one proof per blob (Deneb): computeBlobKzgProof, verifyBlobKzgProof(Batch), computeKzgProof, verifyKzgProof
+    @staticmethod
+    def _points48(what: str, *groups: Sequence[bytes]) -> None:
+        if any(len(p) != 48 for g in groups for p in g):
+            raise KzgError(f"{what}: 48-byte commitments and proofs")
+
+    def compute_blob_kzg_proof(self, blob: bytes, commitment: bytes) -> bytes:
+        """the proof that the blob's polynomial takes the value p(z) at z = compute_challenge(blob,
+        commitment); the commitment must decode and lie in G1 (infinity allowed)"""
+        what = "computeBlobKzgProof"
+        self._points48(what, [commitment])
+        if self.field == "device":
+            u8, i32 = ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_int32)
+            src = self._blob_bytes([blob])
+            cm = np.frombuffer(bytes(commitment), np.uint8)
+            out = np.zeros(48, np.uint8)
+            status = np.zeros(1, np.int32)
+            self._check(self.lib.lb_kzg_compute_blob_proofs(self.engine.h, 1, src.ctypes.data_as(u8), cm.ctypes.data_as(u8),
+                                                            out.ctypes.data_as(u8), status.ctypes.data_as(i32)), what)
+            self._check(int(status[0]), what)
+            return out.tobytes()
+        self.g1_lincomb([1], [commitment])  # decodes and subgroup-checks the commitment
+        coeffs = evaluations_to_coefficients(blob_to_polynomial(blob))
+        return self.commit_coefficients(quotient_coefficients(coeffs, compute_challenge(blob, commitment)))
+
+    def verify_blob_kzg_proof_batch_many(self, groups: Sequence[Tuple[Sequence[bytes], Sequence[bytes], Sequence[bytes]]]) -> list:
+        """verify_blob_kzg_proof_batch for many groups (one group = one block's sidecars: blobs,
+        commitments, proofs, one proof per blob) in one pass over the GPU
+        (`lb_kzg_verify_blob_proof_batch`), whatever `field` is.  One entry per group: True, False,
+        or the KzgError the single call would raise -- returned, not raised.  Malformed input (length
+        mismatches, a wrong blob or point length) raises before anything is sent."""
+        what = "verifyBlobKzgProofBatch"
+        offsets, blobs, comms, proofs = [0], [], [], []
+        for g_blobs, g_comms, g_proofs in groups:
+            if not (len(g_blobs) == len(g_comms) == len(g_proofs)):
+                raise KzgError(f"{what}: blobs / commitments / proofs length mismatch")
+            self._points48(what, g_comms, g_proofs)
+            blobs += list(g_blobs)
+            comms += [bytes(c) for c in g_comms]
+            proofs += [bytes(p) for p in g_proofs]
+            offsets.append(len(blobs))
+        n = len(offsets) - 1
+        if n == 0:
+            return []
+        u8, i32 = ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_int32)
+        src = self._blob_bytes(blobs)
+        cm = np.frombuffer(b"".join(comms) or b"\x00", np.uint8)
+        pf = np.frombuffer(b"".join(proofs) or b"\x00", np.uint8)
+        off = np.asarray(offsets, np.uint32)
+        ok = np.zeros(n, np.int32)
+        self._check(self.lib.lb_kzg_verify_blob_proof_batch(
+            self.engine.h, n, off.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), src.ctypes.data_as(u8),
+            cm.ctypes.data_as(u8), pf.ctypes.data_as(u8), ok.ctypes.data_as(i32)), f"{what}Many")
+        return [KzgError(f"{what}: {self._N.error_name(-int(v))}") if v < 0 else bool(v == 1) for v in ok]
+
+    def verify_blob_kzg_proof_batch(self, blobs: Sequence[bytes], commitments: Sequence[bytes], proofs: Sequence[bytes]) -> bool:
+        """c-kzg verifyBlobKzgProofBatch: one group, always through the device call"""
+        res = self.verify_blob_kzg_proof_batch_many([(blobs, commitments, proofs)])[0]
+        if isinstance(res, KzgError):
+            raise res
+        return res
+
+    def verify_blob_kzg_proof(self, blob: bytes, commitment: bytes, proof: bytes) -> bool:
+        """c-kzg verifyBlobKzgProof: the batch of one blob (r^0 = 1)"""
+        if self.field == "device":
+            return self.verify_blob_kzg_proof_batch([blob], [commitment], [proof])
+        self._points48("verifyBlobKzgProof", [commitment], [proof])
+        self.g1_lincomb([1], [commitment])  # the commitment's error comes before the blob's
+        z = compute_challenge(blob, commitment)
+        y = evaluate_coefficients(evaluations_to_coefficients(blob_to_polynomial(blob)), z)
+        return self.verify_kzg_proof(commitment, z, y, proof)
+
+    @staticmethod
+    def _field_element(what: str, b: bytes) -> int:
+        if len(b) != 32:
+            raise KzgError(f"{what}: 32-byte field elements")
+        v = int.from_bytes(bytes(b), ENDIANNESS)
+        if v >= BLS_MODULUS:
+            raise KzgError(f"{what}: BLST_BAD_SCALAR")
+        return v
+
+    def compute_kzg_proof_bytes(self, blob: bytes, z32: bytes) -> Tuple[bytes, bytes]:
+        """c-kzg computeKzgProof: (proof, y) with z and y as 32 big-endian bytes"""
+        z = self._field_element("computeKzgProof", z32)
+        if self.field == "device":
+            proof, y = self.compute_kzg_proof(blob, z)
+        else:
+            proof, y = self.compute_kzg_proof_coefficients(evaluations_to_coefficients(blob_to_polynomial(blob)), z)
+        return proof, y.to_bytes(32, ENDIANNESS)
+
+    def verify_kzg_proof_bytes(self, commitment: bytes, z32: bytes, y32: bytes, proof: bytes) -> bool:
+        """c-kzg verifyKzgProof: z and y as 32 big-endian bytes, each below r"""
+        z = self._field_element("verifyKzgProof", z32)
+        y = self._field_element("verifyKzgProof", y32)
+        return self.verify_kzg_proof(commitment, z, y, proof)
+
     # the ckzg names kzg.ts binds
+    computeBlobKzgProof = compute_blob_kzg_proof
+    verifyBlobKzgProof = verify_blob_kzg_proof
+    verifyBlobKzgProofBatch = verify_blob_kzg_proof_batch
+    verifyBlobKzgProofBatchMany = verify_blob_kzg_proof_batch_many
+    computeKzgProof = compute_kzg_proof_bytes
+    verifyKzgProof = verify_kzg_proof_bytes
     verifyAggregateKzgProofBatch = verify_aggregate_kzg_proof_batch
     blobToKzgCommitment = blob_to_kzg_commitment
     computeAggregateKzgProof = compute_aggregate_kzg_proof

@@ -50,6 +50,10 @@
  *   scalar-field work on the GPU as well (blobs: n x 131072 bytes in one Uint8Array)
  *   kzgVerifyAggregateProofBatch(engine, blobs, blobOffsets: Uint32Array, commitments, proofs)
  *     -> Int32Array: many sidecars in one pass, 1 / 0 / -code per sidecar
+ *   kzgComputeBlobProofs(engine, blobs, commitments) -> Uint8Array (48 B per blob): one proof per
+ *     blob (Deneb), throws the first rejected blob's code
+ *   kzgVerifyBlobProofBatch(engine, blobs, groupOffsets: Uint32Array, commitments, proofs)
+ *     -> Int32Array: many verifyBlobKzgProofBatch groups in one pass, 1 / 0 / -code per group
  *   (the KZG calls are synchronous, as c-kzg's are; lodestar_amd/js/kzg.js builds the ckzg
  *   module surface of util/kzg.ts on them)
  */
@@ -838,6 +842,72 @@ static napi_value kzg_verify_aggregate_proof_batch(napi_env env, napi_callback_i
   return out;
 }
 
+/* One proof per blob (Deneb; lb_kzg_compute_blob_proofs): the proofs of n blobs against their
+ * commitments as one Uint8Array of n x 48 bytes.  The first rejected blob's code is thrown (a
+ * commitment that fails to decode or lies outside G1, a blob element >= r). */
+static napi_value kzg_compute_blob_proofs(napi_env env, napi_callback_info info) {
+  size_t argc = 3;
+  napi_value argv[3];
+  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  engine_box* b = NULL;
+  tview bl, cm;
+  if (argc < 3 || napi_get_value_external(env, argv[0], (void**)&b) != napi_ok || !b || !b->e ||
+      !get_view(env, argv[1], &bl) || !bl.present || bl.type != napi_uint8_array || bl.n % LB_BLOB_BYTES ||
+      !get_view(env, argv[2], &cm) || !cm.present || cm.type != napi_uint8_array ||
+      cm.n != bl.n / LB_BLOB_BYTES * 48) {
+    napi_throw_type_error(env, NULL,
+                          "kzgComputeBlobProofs(engine, blobs: Uint8Array of n x 131072 bytes, "
+                          "commitments: Uint8Array of n x 48 bytes)");
+    return NULL;
+  }
+  const uint32_t n = (uint32_t)(bl.n / LB_BLOB_BYTES);
+  napi_value ab, out;
+  void* po;
+  NAPI_CALL(env, napi_create_arraybuffer(env, (size_t)n * 48, &po, &ab));
+  int32_t* st = (int32_t*)calloc(n ? n : 1, sizeof(int32_t));
+  if (!st) return throw_code(env, LB_ERR_DEVICE);
+  const int32_t r = lb_kzg_compute_blob_proofs(b->e, n, (const uint8_t*)bl.data, (const uint8_t*)cm.data, (uint8_t*)po, st);
+  int32_t bad = r;
+  for (uint32_t i = 0; i < n && bad == LB_OK; i++) bad = st[i];
+  free(st);
+  if (bad != LB_OK) return throw_code(env, bad);
+  NAPI_CALL(env, napi_create_typedarray(env, napi_uint8_array, (size_t)n * 48, ab, 0, &out));
+  return out;
+}
+
+/* Many groups in one pass (lb_kzg_verify_blob_proof_batch): group k owns blobs groupOffsets[k] ..
+ * groupOffsets[k + 1] - 1 with their commitments and proofs, one proof per blob.  One int32 per
+ * group: 1, 0, or -code, as the C call gives them; nothing is thrown for a group that rejects. */
+static napi_value kzg_verify_blob_proof_batch(napi_env env, napi_callback_info info) {
+  size_t argc = 5;
+  napi_value argv[5];
+  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  engine_box* b = NULL;
+  tview bl, of, cm, pr;
+  if (argc < 5 || napi_get_value_external(env, argv[0], (void**)&b) != napi_ok || !b || !b->e ||
+      !get_view(env, argv[1], &bl) || !bl.present || bl.type != napi_uint8_array || bl.n % LB_BLOB_BYTES ||
+      !get_view(env, argv[2], &of) || !of.present || of.type != napi_uint32_array || of.n < 1 ||
+      !get_view(env, argv[3], &cm) || !cm.present || cm.type != napi_uint8_array ||
+      cm.n != bl.n / LB_BLOB_BYTES * 48 || !get_view(env, argv[4], &pr) || !pr.present ||
+      pr.type != napi_uint8_array || pr.n != cm.n ||
+      ((const uint32_t*)of.data)[of.n - 1] != bl.n / LB_BLOB_BYTES) {
+    napi_throw_type_error(env, NULL,
+                          "kzgVerifyBlobProofBatch(engine, blobs: Uint8Array of b x 131072 bytes, "
+                          "groupOffsets: Uint32Array of n + 1 prefix sums ending in b, "
+                          "commitments: Uint8Array of b x 48 bytes, proofs: Uint8Array of b x 48 bytes)");
+    return NULL;
+  }
+  const uint32_t n = (uint32_t)(of.n - 1);
+  napi_value ab, out;
+  void* po;
+  NAPI_CALL(env, napi_create_arraybuffer(env, (size_t)n * 4, &po, &ab));
+  const int32_t r = lb_kzg_verify_blob_proof_batch(b->e, n, (const uint32_t*)of.data, (const uint8_t*)bl.data,
+                                                   (const uint8_t*)cm.data, (const uint8_t*)pr.data, (int32_t*)po);
+  if (r != LB_OK) return throw_code(env, r);
+  NAPI_CALL(env, napi_create_typedarray(env, napi_int32_array, n, ab, 0, &out));
+  return out;
+}
+
 static napi_value table_size(napi_env env, napi_callback_info info) {
   size_t argc = 1;
   napi_value argv[1], v;
@@ -887,6 +957,8 @@ static napi_value init(napi_env env, napi_value exports) {
       {"kzgComputeAggregateProof", NULL, kzg_compute_aggregate_proof, NULL, NULL, NULL, napi_default, NULL},
       {"kzgVerifyAggregateProof", NULL, kzg_verify_aggregate_proof, NULL, NULL, NULL, napi_default, NULL},
       {"kzgVerifyAggregateProofBatch", NULL, kzg_verify_aggregate_proof_batch, NULL, NULL, NULL, napi_default, NULL},
+      {"kzgComputeBlobProofs", NULL, kzg_compute_blob_proofs, NULL, NULL, NULL, napi_default, NULL},
+      {"kzgVerifyBlobProofBatch", NULL, kzg_verify_blob_proof_batch, NULL, NULL, NULL, napi_default, NULL},
   };
   napi_define_properties(env, exports, sizeof(props) / sizeof(props[0]), props);
   return exports;

@@ -33,7 +33,8 @@ GROUPS = {
     4: ["k_miller_lane", "k_pk_chunks", "k_pk_chunks_idx", "k_pk_blind", "k_gsum_chunks", "k_gsum_final"],
     14: ["k_gsum_wave", "k_pk_out96"],
     5: ["k_miller_wave", "k_tree_up_U", "k_ml_S", "k_root_check", "k_root_partial", "k_partials_check", "k_search_ml",
-        "k_search_fe", "k_search_match", "k_miller_g8", "k_kzg_check", "k_kzg_check_many"],
+        "k_search_fe", "k_search_match", "k_miller_g8", "k_kzg_check", "k_kzg_check_many",
+        "k_kzg_check_groups"],
     6: ["k_msm_count", "k_msm_scatter", "k_msm_chunks", "k_msm_buckets", "k_msm_reduce"],
     7: ["k_smsm_count", "k_smsm_scatter", "k_smsm_terms_g8", "k_smsm_terms_lane", "k_seg_sum64", "k_seg_final",
         "k_rsm_terms", "k_range_pk", "k_test_pk", "k_g1_terms", "k_g1_sum64", "k_g1_out48",
@@ -47,7 +48,7 @@ GROUPS = {
     15: ["k_comb_fill", "k_pk_blind_comb"],
     # KZG scalar field (lb_kzg_field.h), beside the KZG group kernels of group 7
     16: ["k_fr_blob_load", "k_fr_aggregate", "k_fr_intt4096", "k_fr_eval_quotient", "k_fr_aggregate_seg",
-         "k_fr_eval_many"],
+         "k_fr_eval_many", "k_fr_eval_quotient_many"],
 }
 N_GROUPS = len(GROUPS)
 GROUP_OF = {k: g for g, ks in GROUPS.items() for k in ks}
