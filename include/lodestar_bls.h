@@ -209,9 +209,11 @@ int32_t lb_merkleize(lb_engine* e, uint32_t n_trees, const uint32_t* chunk_offse
  *
  * lb_kzg_load_setup (ckzg.loadTrustedSetup, kzg.ts:54-67): the monomial-form setup as Lodestar's
  * trusted_setup.bin holds it -- n_g1 compressed [tau^i] G1 (48 B each) and at least two compressed
- * [tau^i] G2 (96 B each; [tau^0] G2 and [tau^1] G2 are kept).  Every point is decoded and checked
- * (curve, subgroup); out_status[i] per G1 point, and LB_POINT_NOT_IN_GROUP is returned for a bad
- * G2 point.  Replaces any previously loaded setup of this engine.
+ * [tau^i] G2 (96 B each; [tau^0] G2 and [tau^1] G2 are kept, and with n_g2 >= 65 also [tau^64] G2,
+ * which the cell calls below pair against; with fewer, everything but lb_kzg_verify_cell_proof_batch
+ * works).  Every point is decoded and checked (curve, subgroup); out_status[i] per G1 point, and
+ * LB_POINT_NOT_IN_GROUP is returned for a bad G2 point.  Replaces any previously loaded setup of
+ * this engine.
  */
 int32_t lb_kzg_load_setup(lb_engine* e, const uint8_t* g1_48, uint32_t n_g1, const uint8_t* g2_96, uint32_t n_g2,
                           int32_t* out_status);
@@ -317,6 +319,54 @@ int32_t lb_kzg_verify_blob_proof_batch(lb_engine* e, uint32_t n_groups,
                                        const uint8_t* blobs,          /* group_offsets[n] x 131072 B */
                                        const uint8_t* commitments48,  /* group_offsets[n] x 48 B */
                                        const uint8_t* proofs48,       /* group_offsets[n] x 48 B */
+                                       int32_t* out_ok);              /* n_groups */
+
+/*
+ * Cells (EIP-7594 data-availability sampling; c-kzg computeCells, verifyCellKzgProofBatch).  The
+ * blob's polynomial is evaluated over the 8192-point domain of w = 7^((r - 1) / 8192), in 128 cells of
+ * 64 field elements (2048 bytes, 32 big-endian bytes each): cell i holds the values at the bit-reversed
+ * roots 64 i .. 64 i + 63, the coset h_i <w^128> with h_i = w^brp7(i).  Cells 0 .. 63 are the blob.
+ * Every call needs the 4096-point setup; byte parity with c-kzg is not pinned, as above.
+ *
+ * lb_kzg_compute_cells (ckzg.computeCells) for n_blobs <= 1024 blobs: out_cells[b] = the 128 cells of
+ * blob b; out_status[b] = LB_OK or LB_BAD_SCALAR for a blob element >= r (its cells are then zeroed).
+ * Returns LB_OK whenever the call ran.
+ *
+ * lb_kzg_compute_cell_proofs: the proofs of n_cells <= 128 chosen cells of ONE blob by the spec's
+ * direct route, proof_i = commit((p - I_i) / (X^64 - h_i^64)): the quotient on the device, then one
+ * 4096-term multi-scalar multiplication PER CELL.  This is not computeCellsAndKzgProofs (which needs
+ * FK20 to be affordable for all 128 cells); it gives a producer, and the tests, a device route to a
+ * few cells.  *out_status = LB_OK or LB_BAD_SCALAR (the proofs are then zeroed); a cell index >= 128
+ * is LB_ERR_ARGUMENT.
+ *
+ * lb_kzg_verify_cell_proof_batch: one group is one verifyCellKzgProofBatch call (a data-column
+ * sidecar).  Group g owns cells cell_offsets[g] .. cell_offsets[g + 1] - 1 of the flat per-cell arrays
+ * and gets its own exact check with the spec's combiner: the group's commitments are deduplicated in
+ * order of first appearance, r = hash_to_bls_field(CELL_DOMAIN || 4096 || 64 || #distinct || n || the
+ * distinct commitments || per cell: commitment index || cell index || cell || proof), integers as 8
+ * bytes BE, and with I_k the interpolation polynomial of cell k over its coset
+ *   e(sum r^k proof_k, [tau^64] G2) e(sum r^k C_k - commit(sum r^k I_k) + sum [r^k h_k^64] proof_k, -G2) == 1.
+ * r hashes nothing the device computes, so the whole pass has ONE stream synchronisation.
+ * out_ok[g] = 1, 0, or -code in the spec's reading order: the first commitment (by position) that
+ * fails to decode or lies outside G1, then -LB_BAD_SCALAR for the first cell with an element >= r,
+ * then the first bad proof.  Infinity is a legal commitment and proof; an empty group gives 1; a
+ * rejecting group changes nothing for the others.  Returns LB_OK whenever the call ran (n_groups == 0:
+ * at once); LB_ERR_ARGUMENT for no 4096-point setup or one loaded with n_g2 < 65, a needed pointer that
+ * is NULL, cell_offsets[0] != 0, decreasing offsets, a cell index >= 128, more than 1024 groups or
+ * more than 16384 cells in all.  lb_kzg_batch_hash_ns reports this call's hashing time too.
+ */
+int32_t lb_kzg_compute_cells(lb_engine* e, uint32_t n_blobs, const uint8_t* blobs, /* n_blobs x 131072 B */
+                             uint8_t* out_cells,                                  /* n_blobs x 128 x 2048 B */
+                             int32_t* out_status);                                /* n_blobs */
+int32_t lb_kzg_compute_cell_proofs(lb_engine* e, const uint8_t* blob, uint32_t n_cells, const uint32_t* cell_indices,
+                                   uint8_t* out_proofs48, /* n_cells x 48 B */
+                                   int32_t* out_status);  /* one: the blob's */
+int32_t lb_kzg_verify_cell_proof_batch(lb_engine* e, uint32_t n_groups,
+                                       const uint32_t* cell_offsets,  /* n_groups + 1 prefix sums over cells */
+                                       const uint8_t* commitments48,  /* one per cell: cell_offsets[n] x 48 B */
+                                       const uint32_t* cell_indices,  /* one per cell, < 128 */
+                                       const uint8_t* cells,          /* cell_offsets[n] x 2048 B */
+                                       const uint8_t* proofs48,       /* cell_offsets[n] x 48 B */
                                        int32_t* out_ok);              /* n_groups */
 
 /*

@@ -186,6 +186,26 @@ def build_kzg_blob_harness(force=False, verbose=True):
     return KZG_BLOB_HARNESS
 
 
+KZG_CELLS_HARNESS = os.path.join(ROOT, "build", "lb_kzg_cells_harness.so")
+
+
+def build_kzg_cells_harness(force=False, verbose=True):
+    """the combiner, the coset transform, the cell interpolation and quotient lanes and the status fold
+    of the cell calls on the CPU (tests/test_kzg_cells_cpu.py)"""
+    hdir = os.path.join(ROOT, "tests", "harness")
+    src = os.path.join(hdir, "lb_kzg_cells_harness.cpp")
+    os.makedirs(os.path.dirname(KZG_CELLS_HARNESS), exist_ok=True)
+    if not force and not _stale(KZG_CELLS_HARNESS, _deps() + [src, os.path.join(hdir, "kzg_cells_lanes.h")]):
+        return KZG_CELLS_HARNESS
+    cmd = ["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-pthread", "-I" + INC, "-I" + CSRC, src,
+           "-o", KZG_CELLS_HARNESS + ".tmp"]
+    if verbose:
+        print("[build]", " ".join(cmd), flush=True)
+    subprocess.run(cmd, check=True)
+    os.replace(KZG_CELLS_HARNESS + ".tmp", KZG_CELLS_HARNESS)
+    return KZG_CELLS_HARNESS
+
+
 def build_cpu_pool(force=False, verbose=True):
     src = os.path.join(ROOT, "oracle", "cpu_pool.cpp")
     if not os.path.exists(src):
@@ -248,6 +268,7 @@ def build_all(force=False):
     build_fr_harness(force)
     build_kzg_batch_harness(force)
     build_kzg_blob_harness(force)
+    build_kzg_cells_harness(force)
     build_cpu_pool(force)
     build_ubench(force)
 

@@ -242,6 +242,11 @@ struct lb_engine {
   // ... and the inverse transform's twiddles for the blob-level calls (lb_fr.h fr_intt_table(12):
   // 2048 powers of the inverse root and 1 / 4096, Montgomery form), built on the host at load
   dbuf kzg_tw;
+  // ... and, when the setup holds [tau^64] G2 (a third g2a in kzg_g2), the cell calls' table (lb_fr.h
+  // fr_cell_tables) with the 128 coset factors h_i^64 kept on the host (Montgomery form, by cell index)
+  dbuf kzg_cell_tab;
+  bool kzg_cells = false;
+  std::vector<fr> kzg_h64;
   uint64_t kzg_batch_hash_ns = 0;  // host transcript hashing of the last batch verification (lb_kzg_batch_hash_ns)
   // profiling
   bool profiling = false;
@@ -591,7 +596,7 @@ void lb_engine_destroy(lb_engine* e) {
                   &e->gch, &e->chunk_beg, &e->chunk_end, &e->members, &e->set_live, &e->gacc, &e->gp_aff,
                   &e->gp_inf, &e->chunk_root, &e->sig_aos, &e->bcnt, &e->bcursor, &e->boff, &e->bch, &e->bchunk_beg,
                   &e->bchunk_end, &e->bmembers, &e->bacc, &e->bsum, &e->wsum, &e->park, &e->pk_aff, &e->y_root, &e->kzg_g1,
-                  &e->kzg_g2, &e->kzg_tw, &e->s_terms, &e->s_part, &e->s_root, &e->rs_idx, &e->s_set};
+                  &e->kzg_g2, &e->kzg_tw, &e->kzg_cell_tab, &e->s_terms, &e->s_part, &e->s_root, &e->rs_idx, &e->s_set};
   for (dbuf* b : bufs) b->release();
   for (dbuf& b : e->sx) b.release();
   for (int i = 0; i < kStages; i++) {
@@ -2352,27 +2357,33 @@ extern "C" int32_t lb_sign(lb_engine* e, uint32_t n, const uint8_t* sks32, const
 extern "C" int32_t lb_kzg_load_setup(lb_engine* e, const uint8_t* g1_48, uint32_t n_g1, const uint8_t* g2_96,
                                      uint32_t n_g2, int32_t* out_status) {
   if (!e || !n_g1 || !g1_48 || !g2_96 || n_g2 < 2 || !out_status) return LB_ERR_ARGUMENT;
-  std::vector<int32_t> st2(2, LB_OK);
+  // [tau^0] G2, [tau^1] G2 and, where the setup reaches it, [tau^64] G2 (the cell calls), side by side
+  const uint32_t n2 = n_g2 >= 65 ? 3 : 2;
+  std::vector<uint8_t> g2in((size_t)n2 * 96);
+  memcpy(g2in.data(), g2_96, 2 * 96);
+  if (n2 == 3) memcpy(g2in.data() + 2 * 96, g2_96 + (size_t)64 * 96, 96);
+  std::vector<int32_t> st2(3, LB_OK);
   int32_t r;
+  e->kzg_cells = false;
   {
     std::lock_guard<std::mutex> lk(e->mu);
     LB_HIP(hipSetDevice(e->device));
     LB_HIP(e->kzg_g1.ensure((size_t)n_g1 * sizeof(g1a)));
-    LB_HIP(e->kzg_g2.ensure(2 * sizeof(g2a)));
+    LB_HIP(e->kzg_g2.ensure(3 * sizeof(g2a)));
   }
   lb_engine* ee = e;
   r = run_simple(e, {{g1_48, (size_t)n_g1 * 48, false, nullptr}, {nullptr, (size_t)n_g1 * 4, true, out_status},
-                     {g2_96, 2 * 96, false, nullptr}, {nullptr, 2 * 4, true, st2.data()}},
+                     {g2in.data(), g2in.size(), false, nullptr}, {nullptr, (size_t)n2 * 4, true, st2.data()}},
                  [&](std::vector<void*>& p) {
                    hipLaunchKernelGGL(k_kzg_setup_g1, dim3(nblk(n_g1)), dim3(LB_TPB), 0, ee->stream, n_g1,
                                       (const uint8_t*)p[0], ee->kzg_g1.as<uint32_t>(), n_g1, (int32_t*)p[1]);
-                   hipLaunchKernelGGL(k_kzg_setup_g2, dim3(1), dim3(64), 0, ee->stream, (const uint8_t*)p[2],
+                   hipLaunchKernelGGL(k_kzg_setup_g2, dim3(1), dim3(64), 0, ee->stream, n2, (const uint8_t*)p[2],
                                       ee->kzg_g2.as<uint32_t>(), (int32_t*)p[3]);
                  });
   if (r != LB_OK) return r;
-  if (st2[0] != LB_OK || st2[1] != LB_OK) {
+  if (st2[0] != LB_OK || st2[1] != LB_OK || st2[2] != LB_OK) {
     e->kzg_n = 0;
-    return st2[0] != LB_OK ? st2[0] : st2[1];
+    return st2[0] != LB_OK ? st2[0] : (st2[1] != LB_OK ? st2[1] : st2[2]);
   }
   for (uint32_t i = 0; i < n_g1; i++)
     if (out_status[i] != LB_OK) {
@@ -2387,9 +2398,17 @@ extern "C" int32_t lb_kzg_load_setup(lb_engine* e, const uint8_t* g1_48, uint32_
     LB_HIP(hipSetDevice(e->device));
     LB_HIP(e->kzg_tw.ensure(tw.size() * sizeof(fr)));
     LB_HIP(hipMemcpyAsync(e->kzg_tw.p, tw.data(), tw.size() * sizeof(fr), hipMemcpyHostToDevice, e->stream));
+    // the cell calls' tables beside it: forward twiddles, w^j, w^-m, the 64-point inverse table
+    std::vector<fr> ct(LB_FR_CELL_TAB_LEN);
+    fr_cell_tables(ct.data());
+    e->kzg_h64.resize(LB_FR_CELLS);
+    for (uint32_t i = 0; i < LB_FR_CELLS; i++) e->kzg_h64[i] = ct[LB_FR_CELL_TAB_WINV + fr_cell_h64_index(i)];
+    LB_HIP(e->kzg_cell_tab.ensure(ct.size() * sizeof(fr)));
+    LB_HIP(hipMemcpyAsync(e->kzg_cell_tab.p, ct.data(), ct.size() * sizeof(fr), hipMemcpyHostToDevice, e->stream));
     LB_HIP(hipStreamSynchronize(e->stream));
   }
   e->kzg_n = n_g1;
+  e->kzg_cells = n2 == 3;
   return LB_OK;
 }
 
@@ -2513,10 +2532,12 @@ struct kzg_ws {
   dbuf z;       // evaluation point, Montgomery
   dbuf io, yz;  // k_kzg_check's inputs: C || proof, y || z as LE words
   dbuf off, ok;  // the batched verification: sidecar offsets in, verdicts out
+  dbuf cidx, doff;           // the cell calls: cell indices; distinct-commitment offsets per group
+  dbuf tsc;                  // ... the table part's scalars (k_fr_cell_sum -> k_g1_cell_terms)
   std::vector<int32_t> h_status;
   ~kzg_ws() {
     for (dbuf* b : {&blobs, &polys, &status, &agg, &coef, &le, &terms, &part, &tstatus, &pts, &pw, &pw_le, &z, &io, &yz,
-                    &off, &ok})
+                    &off, &ok, &cidx, &doff, &tsc})
       b->release();
   }
 };
@@ -3040,3 +3061,181 @@ extern "C" int32_t lb_kzg_verify_blob_proof_batch(lb_engine* e, uint32_t n_group
 }
 
 extern "C" uint64_t lb_kzg_batch_hash_ns(const lb_engine* e) { return e ? e->kzg_batch_hash_ns : 0; }
+
+// ---------------------------------------------------------------- KZG cells (EIP-7594, PeerDAS)
+// compute_cells for n_blobs blobs: decode, coefficients (k_fr_intt4096), then one workgroup per blob
+// writes its 128 cells (k_fr_coset_ntt4096).
+extern "C" int32_t lb_kzg_compute_cells(lb_engine* e, uint32_t n_blobs, const uint8_t* blobs, uint8_t* out_cells,
+                                        int32_t* out_status) {
+  if (!kzg_ready(e) || n_blobs > kMaxBlobs) return LB_ERR_ARGUMENT;
+  if (!n_blobs) return LB_OK;
+  if (!blobs || !out_cells || !out_status) return LB_ERR_ARGUMENT;
+  const uint32_t n = n_blobs;
+  std::lock_guard<std::mutex> lk(e->mu);
+  kzg_ws w;
+  int32_t rc = kzg_load_blobs(e, w, n, blobs);
+  if (rc != LB_OK) return rc;
+  LB_KZG_TRY(w.coef.ensure(n * kBlobBytes));
+  LB_KZG_TRY(w.le.ensure(n * LB_FR_EXT_BYTES));
+  rc = kzg_intt(e, n, w.polys.as<uint32_t>(), w.coef.as<uint32_t>(), nullptr);
+  if (rc != LB_OK) return rc;
+  LB_KZG_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_fr_coset_ntt4096),
+                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)LB_FR_INTT_LDS));
+  hipLaunchKernelGGL(k_fr_coset_ntt4096, dim3(n), dim3(LB_FR_WG), LB_FR_INTT_LDS, e->stream, w.coef.as<uint32_t>(),
+                     w.blobs.as<uint8_t>(), e->kzg_cell_tab.as<uint32_t>(), w.le.as<uint8_t>());
+  LB_KZG_TRY(hipGetLastError());
+  LB_KZG_TRY(hipMemcpyAsync(out_cells, w.le.p, n * LB_FR_EXT_BYTES, hipMemcpyDeviceToHost, e->stream));
+  LB_KZG_TRY(hipStreamSynchronize(e->stream));
+  for (uint32_t b = 0; b < n; b++) {
+    out_status[b] = w.h_status[b];
+    if (out_status[b] != LB_OK) memset(out_cells + b * LB_FR_EXT_BYTES, 0, LB_FR_EXT_BYTES);
+  }
+  return LB_OK;
+}
+
+// The direct (non-FK20) proofs of chosen cells of one blob: the quotient by X^64 - h^64 per cell on
+// the device (k_fr_cell_quotient), then one 4096-term linear combination of the setup per cell.
+extern "C" int32_t lb_kzg_compute_cell_proofs(lb_engine* e, const uint8_t* blob, uint32_t n_cells, const uint32_t* cell_indices,
+                                              uint8_t* out_proofs48, int32_t* out_status) {
+  if (!kzg_ready(e) || !blob || !out_status || n_cells > LB_FR_CELLS) return LB_ERR_ARGUMENT;
+  if (n_cells && (!cell_indices || !out_proofs48)) return LB_ERR_ARGUMENT;
+  for (uint32_t c = 0; c < n_cells; c++)
+    if (cell_indices[c] >= LB_FR_CELLS) return LB_ERR_ARGUMENT;
+  std::lock_guard<std::mutex> lk(e->mu);
+  kzg_ws w;
+  int32_t rc = kzg_load_blobs(e, w, 1, blob);
+  if (rc != LB_OK) return rc;
+  *out_status = w.h_status[0];
+  if (!n_cells) return LB_OK;
+  if (*out_status != LB_OK) {
+    memset(out_proofs48, 0, (size_t)n_cells * 48);
+    return LB_OK;
+  }
+  LB_KZG_TRY(w.coef.ensure(kBlobBytes));
+  LB_KZG_TRY(w.le.ensure(n_cells * kBlobBytes));
+  LB_KZG_TRY(w.cidx.ensure((size_t)n_cells * 4));
+  LB_KZG_TRY(w.io.ensure((size_t)n_cells * 48));
+  LB_KZG_TRY(hipMemcpyAsync(w.cidx.p, cell_indices, (size_t)n_cells * 4, hipMemcpyHostToDevice, e->stream));
+  rc = kzg_intt(e, 1, w.polys.as<uint32_t>(), w.coef.as<uint32_t>(), nullptr);
+  if (rc != LB_OK) return rc;
+  hipLaunchKernelGGL(k_fr_cell_quotient, dim3(n_cells), dim3(64), 0, e->stream, n_cells, w.coef.as<uint32_t>(),
+                     w.cidx.as<uint32_t>(), e->kzg_cell_tab.as<uint32_t>(), w.le.as<uint32_t>());
+  LB_KZG_TRY(hipGetLastError());
+  for (uint32_t c = 0; c < n_cells; c++)
+    g1_lincomb_launch(e, LB_FR_N, nullptr, w.le.as<uint32_t>() + (size_t)c * LB_FR_N * 8, w.terms.as<uint32_t>(),
+                      w.part.as<uint32_t>(), w.tstatus.as<int32_t>(), w.io.as<uint8_t>() + (size_t)48 * c);
+  LB_KZG_TRY(hipGetLastError());
+  LB_KZG_TRY(hipMemcpyAsync(out_proofs48, w.io.p, (size_t)n_cells * 48, hipMemcpyDeviceToHost, e->stream));
+  LB_KZG_TRY(hipStreamSynchronize(e->stream));
+  return LB_OK;
+}
+
+// verify_cell_kzg_proof_batch for many groups in one pass with ONE synchronisation: the combiner
+// hashes only the caller's bytes, so every scalar of the given-point ladders is known on the host
+// before anything comes back, and the interpolation coefficients never leave the device.
+extern "C" int32_t lb_kzg_verify_cell_proof_batch(lb_engine* e, uint32_t n_groups, const uint32_t* cell_offsets,
+                                                  const uint8_t* commitments48, const uint32_t* cell_indices,
+                                                  const uint8_t* cells, const uint8_t* proofs48, int32_t* out_ok) {
+  const uint32_t n = n_groups;
+  if (!kzg_ready(e) || !e->kzg_cells || n > 1024) return LB_ERR_ARGUMENT;
+  if (!n) return LB_OK;
+  if (!cell_offsets || !out_ok || cell_offsets[0] != 0) return LB_ERR_ARGUMENT;
+  for (uint32_t g = 0; g < n; g++)
+    if (cell_offsets[g + 1] < cell_offsets[g]) return LB_ERR_ARGUMENT;
+  const uint32_t nc = cell_offsets[n];
+  if (nc > 16384 || (nc && (!commitments48 || !cell_indices || !cells || !proofs48))) return LB_ERR_ARGUMENT;
+  for (uint32_t k = 0; k < nc; k++)
+    if (cell_indices[k] >= LB_FR_CELLS) return LB_ERR_ARGUMENT;
+  std::lock_guard<std::mutex> lk(e->mu);
+  kzg_ws w;
+  const size_t nc1 = std::max<size_t>(nc, 1);
+  LB_KZG_TRY(hipSetDevice(e->device));
+  LB_KZG_TRY(w.blobs.ensure(nc1 * LB_FR_CELL_BYTES));
+  LB_KZG_TRY(w.polys.ensure(nc1 * LB_FR_CELL_BYTES));
+  LB_KZG_TRY(w.status.ensure(nc1 * 4));
+  LB_KZG_TRY(w.cidx.ensure(nc1 * 4));
+  LB_KZG_TRY(w.pw.ensure(nc1 * sizeof(fr)));
+  LB_KZG_TRY(w.off.ensure((size_t)(n + 1) * 4));
+  LB_KZG_TRY(w.doff.ensure((size_t)(n + 1) * 4));
+  LB_KZG_TRY(w.tsc.ensure((size_t)n * 64 * sizeof(fr)));
+  LB_KZG_TRY(w.ok.ensure((size_t)n * 4));
+  // 1. the cells go up and are decoded while 2. the host deduplicates and hashes
+  LB_KZG_TRY(hipMemcpyAsync(w.off.p, cell_offsets, (size_t)(n + 1) * 4, hipMemcpyHostToDevice, e->stream));
+  if (nc) {
+    LB_KZG_TRY(hipMemcpyAsync(w.blobs.p, cells, (size_t)nc * LB_FR_CELL_BYTES, hipMemcpyHostToDevice, e->stream));
+    LB_KZG_TRY(hipMemcpyAsync(w.cidx.p, cell_indices, (size_t)nc * 4, hipMemcpyHostToDevice, e->stream));
+    LB_KZG_TRY(hipMemsetAsync(w.status.p, 0, (size_t)nc * 4, e->stream));
+    const uint32_t n_elems = nc * LB_FR_CELL;
+    hipLaunchKernelGGL(k_fr_cell_load, dim3((n_elems + 255) / 256), dim3(256), 0, e->stream, n_elems, w.blobs.as<uint8_t>(),
+                       w.polys.as<uint32_t>(), w.status.as<int32_t>());
+    LB_KZG_TRY(hipGetLastError());
+  }
+  // the host arrays live until the synchronisation
+  std::vector<uint32_t> ci(nc1), first, doff(n + 1, 0);
+  std::vector<fr> rs(n), wt(nc1);
+  const auto h0 = std::chrono::steady_clock::now();
+  for (uint32_t g = 0; g < n; g++) {
+    const uint32_t lo = cell_offsets[g];
+    doff[g + 1] = doff[g] + kzg_cell_dedup(cell_offsets[g + 1] - lo, commitments48 + (size_t)48 * lo, ci.data() + lo, first);
+  }
+  kzg_cell_batch_rs(n, cell_offsets, doff.data(), commitments48, ci.data(), first.data(), cell_indices, cells, proofs48,
+                    rs.data(), kzg_hash_threads());
+  e->kzg_batch_hash_ns = kzg_ns_since(h0);
+  // 3. the scalars: r^i per proof, r^i h^64 per proof, the summed r^i per distinct commitment
+  const uint32_t nd = doff[n], n_pts = 2 * nc + nd;
+  const size_t np1 = std::max<size_t>(n_pts, 1);
+  std::vector<fr> sc(np1);
+  std::vector<uint8_t> pts(np1 * 48);
+  for (uint32_t g = 0; g < n; g++) {
+    const uint32_t lo = cell_offsets[g], cnt = cell_offsets[g + 1] - lo, dcnt = doff[g + 1] - doff[g];
+    std::vector<fr> wsum(dcnt, fr_zero());
+    fr p = fr_one();
+    for (uint32_t i = 0; i < cnt; i++) {
+      const uint32_t k = lo + i;
+      wt[k] = p;
+      fr_to_le_words(sc[k].l, p);
+      fr_to_le_words(sc[nc + k].l, fr_mul(p, e->kzg_h64[cell_indices[k]]));
+      wsum[ci[k]] = fr_add(wsum[ci[k]], p);
+      p = fr_mul(p, rs[g]);
+    }
+    for (uint32_t d = 0; d < dcnt; d++) {
+      fr_to_le_words(sc[2 * nc + doff[g] + d].l, wsum[d]);
+      memcpy(pts.data() + (size_t)(2 * nc + doff[g] + d) * 48, commitments48 + (size_t)48 * (lo + first[doff[g] + d]), 48);
+    }
+  }
+  if (nc) {
+    memcpy(pts.data(), proofs48, (size_t)nc * 48);
+    memcpy(pts.data() + (size_t)nc * 48, proofs48, (size_t)nc * 48);
+  }
+  LB_KZG_TRY(w.pts.ensure(np1 * 48));
+  LB_KZG_TRY(w.le.ensure(np1 * 32));
+  const uint32_t n_tab = n * LB_FR_CELL, n_terms = n_pts + n_tab;
+  LB_KZG_TRY(w.terms.ensure((size_t)n_terms * sizeof(g1j)));
+  LB_KZG_TRY(w.tstatus.ensure((size_t)n_terms * 4));
+  LB_KZG_TRY(hipMemcpyAsync(w.doff.p, doff.data(), (size_t)(n + 1) * 4, hipMemcpyHostToDevice, e->stream));
+  if (nc) {
+    LB_KZG_TRY(hipMemcpyAsync(w.pw.p, wt.data(), (size_t)nc * sizeof(fr), hipMemcpyHostToDevice, e->stream));
+    LB_KZG_TRY(hipMemcpyAsync(w.le.p, sc.data(), (size_t)n_pts * sizeof(fr), hipMemcpyHostToDevice, e->stream));
+    LB_KZG_TRY(hipMemcpyAsync(w.pts.p, pts.data(), (size_t)n_pts * 48, hipMemcpyHostToDevice, e->stream));
+    // 4. one wave per cell: r^i I_k, in place; then 5. the per-group sums, negated, as scalars
+    hipLaunchKernelGGL(k_fr_cell_interp, dim3(nc), dim3(64), 0, e->stream, nc, w.polys.as<uint32_t>(), w.cidx.as<uint32_t>(),
+                       w.pw.as<uint32_t>(), e->kzg_cell_tab.as<uint32_t>());
+    LB_KZG_TRY(hipGetLastError());
+  }
+  hipLaunchKernelGGL(k_fr_cell_sum, dim3(n), dim3(64), 0, e->stream, n, w.off.as<uint32_t>(), nc, w.polys.as<uint32_t>(),
+                     w.tsc.as<uint32_t>());
+  LB_KZG_TRY(hipGetLastError());
+  // 6. every ladder of the call in one launch: the given points and the 64 setup points per group
+  hipLaunchKernelGGL(k_g1_cell_terms, dim3(nblk(n_terms)), dim3(LB_TPB), 0, e->stream, n_pts, w.pts.as<uint8_t>(),
+                     w.le.as<uint32_t>(), n_tab, e->kzg_g1.as<uint32_t>(), e->kzg_n, (uint32_t)LB_FR_CELL, w.tsc.as<uint32_t>(),
+                     w.terms.as<uint32_t>(), w.tstatus.as<int32_t>());
+  LB_KZG_TRY(hipGetLastError());
+  // 7. one wave per group: status, LL and RL, the two-pair product; the synchronisation
+  hipLaunchKernelGGL(k_kzg_check_cells, dim3(n), dim3(64), 0, e->stream, n, w.off.as<uint32_t>(), nc, w.doff.as<uint32_t>(), nd,
+                     w.status.as<int32_t>(), w.terms.as<uint32_t>(), w.tstatus.as<int32_t>(), e->kzg_g2.as<uint32_t>(),
+                     w.ok.as<int32_t>());
+  LB_KZG_TRY(hipGetLastError());
+  LB_KZG_TRY(hipMemcpyAsync(out_ok, w.ok.p, (size_t)n * 4, hipMemcpyDeviceToHost, e->stream));
+  LB_KZG_TRY(hipStreamSynchronize(e->stream));
+  return LB_OK;
+}

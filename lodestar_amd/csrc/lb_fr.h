@@ -308,6 +308,113 @@ LB_HD int kzg_group_status(const int32_t* bstatus, const int32_t* tstatus, uint3
   return LB_OK;
 }
 
+// ------------------------------------------------------------------ cells (EIP-7594, PeerDAS)
+// The blob's polynomial over the 8192-point domain of w = 7^((r - 1) / 8192), in 128 cells of 64
+// values: cell i holds the values at roots_brp_8192[64 i .. 64 i + 63], i.e. element t stands at
+// h_i w64^brp6(t) with h_i = w^brp7(i) and w64 = w^128.  Cells 0 .. 63 are the blob itself; cells
+// 64 .. 127 are p(w X) at the blob's own bit-reversed roots.
+#define LB_FR_CELL 64u     // FIELD_ELEMENTS_PER_CELL
+#define LB_FR_CELL_LOG 6
+#define LB_FR_CELLS 128u   // CELLS_PER_EXT_BLOB
+#define LB_FR_EXT 8192u    // FIELD_ELEMENTS_PER_EXT_BLOB
+// the resident table of the cell calls (fr_cell_tables), in entries of one fr
+#define LB_FR_CELL_TAB_FWD 0u        // w^(2 k), k < 2048: the forward 4096-point twiddles
+#define LB_FR_CELL_TAB_SCALE 2048u   // w^j, j < 4096: coefficient j of p(w X)
+#define LB_FR_CELL_TAB_WINV 6144u    // w^-m, m < 8192: h^-j and h^64 are entries of it
+#define LB_FR_CELL_TAB_ITW 14336u    // fr_intt_table(6): the 64-point inverse transform
+#define LB_FR_CELL_TAB_LEN (14336u + LB_FR_INTT_TABLE_LEN(LB_FR_CELL_LOG))
+
+// w = 7^((r - 1) / 8192) (Montgomery form); its square is LB_FR_ROOT4096_WORDS
+LB_HD fr fr_root8192() {
+  const uint32_t m[8] = LB_FR_MOD_WORDS;
+  uint32_t t[8], e[8];
+  LB_UNROLL for (int i = 0; i < 8; i++) t[i] = m[i];
+  t[0] -= 1u;  // r is odd: no borrow
+  LB_UNROLL for (int i = 0; i < 8; i++) e[i] = (t[i] >> 13) | (i < 7 ? t[i + 1] << 19 : 0u);
+  return fr_pow(fr_from_u32(7), e);
+}
+// the table above (host code: lb_kzg_load_setup, the CPU harness)
+LB_HD void fr_cell_tables(fr* tab) {
+  const fr w = fr_root8192(), w2 = fr_sqr(w), wi = fr_inv(w);
+  tab[LB_FR_CELL_TAB_FWD] = tab[LB_FR_CELL_TAB_SCALE] = tab[LB_FR_CELL_TAB_WINV] = fr_one();
+  for (uint32_t k = 1; k < 2048; k++) tab[LB_FR_CELL_TAB_FWD + k] = fr_mul(tab[LB_FR_CELL_TAB_FWD + k - 1], w2);
+  for (uint32_t k = 1; k < 4096; k++) tab[LB_FR_CELL_TAB_SCALE + k] = fr_mul(tab[LB_FR_CELL_TAB_SCALE + k - 1], w);
+  for (uint32_t k = 1; k < LB_FR_EXT; k++) tab[LB_FR_CELL_TAB_WINV + k] = fr_mul(tab[LB_FR_CELL_TAB_WINV + k - 1], wi);
+  fr_intt_table(tab + LB_FR_CELL_TAB_ITW, LB_FR_CELL_LOG);
+}
+// the index into the w^-m table of h_i^64 = w^(64 brp7(i)), a 128th root of unity
+LB_HD uint32_t fr_cell_h64_index(uint32_t cell_index) {
+  return (LB_FR_EXT - 64u * fr_bitrev(cell_index, 7)) & (LB_FR_EXT - 1u);
+}
+// the plain value as 8 words whose little-endian storage is the 32 big-endian bytes
+LB_HD void fr_to_be_words(uint32_t out[8], const fr& a) {
+  const fr p = fr_from_mont(a);
+  LB_UNROLL for (int i = 0; i < 8; i++) {
+    const uint32_t v = p.l[7 - i];
+    out[i] = (v >> 24) | ((v >> 8) & 0xff00u) | ((v << 8) & 0xff0000u) | (v << 24);
+  }
+}
+
+// Cells 64 .. 127 of a blob (k_fr_coset_ntt4096): from the 4096 monomial coefficients, coefficient
+// j times w^j goes to slot brp12(j) (fr_coset_load: the transform's input reversal done by the
+// load), twelve forward fr_ntt_stage with tw(k) = w^(2 k), and value k' of the upper half is slot
+// brp12(k') (fr_coset_value: p(w X) at the blob's k'-th bit-reversed root).  Barriers between the
+// phases are the caller's.
+template <class A, class C, class T>
+LB_HD void fr_coset_load(A& a, const C& coef, const T& scale, uint32_t tid, uint32_t nthr) {
+  for (uint32_t j = tid; j < 4096u; j += nthr) a.st(fr_bitrev(j, 12), fr_mul(coef.ld(j), scale(j)));
+}
+template <class A>
+LB_HD fr fr_coset_value(const A& a, uint32_t k) {
+  return a.ld(fr_bitrev(k, 12));
+}
+
+// One cell's interpolation polynomial (k_fr_cell_interp): the 64 values stand at a bit-reversed
+// coset, so six fr_ntt_stage over them as they stand with itw = fr_intt_table(6) give g(Y) = I(h Y)
+// in natural order (unscaled); lane j then takes
+//   weight * I_j = weight * g_j / 64 * h^-j,   h^-j = w^-(brp7(cell_index) j)   (winv: the w^-m table)
+template <class T>
+LB_HD fr fr_cell_descale(const fr& g, const fr& inv_n, const T& winv, uint32_t cell_index, uint32_t j, const fr& weight) {
+  const uint32_t m = (fr_bitrev(cell_index, 7) * j) & (LB_FR_EXT - 1u);
+  return fr_mul(fr_mul(g, inv_n), fr_mul(winv(m), weight));
+}
+// coefficient j of sum_k weight_k I_k over the cells lo <= k < hi of one group, always in this
+// order: c(k, j) is cell k's weighted coefficient j.  An empty group gives 0.
+template <class C>
+LB_HD fr fr_cell_group_sum(const C& c, uint32_t lo, uint32_t hi, uint32_t j) {
+  fr acc = fr_zero();
+  for (uint32_t k = lo; k < hi; k++) acc = fr_add(acc, c(k, j));
+  return acc;
+}
+
+// One cell's quotient (k_fr_cell_quotient): p(X) - I(X) = Q(X) (X^64 - h64) with deg I < 64, so
+// q[j] = a[j + 64] + h64 q[j + 64] with q[j] = 0 for j >= n - 64: 64 independent chains, lane l
+// walking j = l mod 64 from the top.  q_le: n scalars as plain LE words, the top 64 zero.
+template <class A>
+LB_HD void fr_cell_quotient_lane(const A& a, uint32_t n, const fr& h64, uint32_t l, uint32_t* q_le) {
+  LB_UNROLL for (int w = 0; w < 8; w++) q_le[(size_t)8 * (n - 64u + l) + w] = 0;
+  fr q = fr_zero();
+  for (uint32_t j = n - 64u + l; j >= 64u; j -= 64u) {
+    q = fr_add(a.ld(j), fr_mul(h64, q));
+    fr_to_le_words(q_le + (size_t)8 * (j - 64u), q);
+  }
+}
+
+// kzg_cell_group_status: the status of one verify_cell_kzg_proof_batch group in the order the spec
+// reads its input: every commitment (dstatus[dlo .. dhi): the group's distinct commitments in order
+// of first appearance, so the first failing position is the first failing entry), then every cell
+// (cstatus[lo .. hi): an element >= r), then every proof (pstatus[lo .. hi)).  LB_OK for an empty group.
+LB_HD int kzg_cell_group_status(const int32_t* dstatus, uint32_t dlo, uint32_t dhi, const int32_t* cstatus,
+                                const int32_t* pstatus, uint32_t lo, uint32_t hi) {
+  for (uint32_t d = dlo; d < dhi; d++)
+    if (dstatus[d] != LB_OK) return dstatus[d];
+  for (uint32_t j = lo; j < hi; j++)
+    if (cstatus[j] != LB_OK) return LB_BAD_SCALAR;
+  for (uint32_t j = lo; j < hi; j++)
+    if (pstatus[j] != LB_OK) return pstatus[j];
+  return LB_OK;
+}
+
 // Evaluation alone, y = p(z), where the quotient of fr_eq_* is not wanted: lane t of n / 4 takes
 // its four coefficients by Horner (fr_eq_local: L[t] = sum_k a[4 t + k] z^k), then
 // y = sum_t L[t] z^(4 t) folds in halves: for s = log2(n / 4) - 1 down to 0, with h = 2^s, lane

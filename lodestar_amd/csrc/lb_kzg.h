@@ -11,7 +11,8 @@
 //
 // Setup layout: the monomial-form points [tau^i] G1 (what Lodestar's trusted_setup.bin holds; a
 // commitment to p(X) = sum a_i X^i is sum a_i [tau^i] G1, the same point as the spec's Lagrange
-// form sum p(w_i) L_i(tau) G1) as a g1a SoA table; [tau^0] G2 and [tau^1] G2 as two g2a.
+// form sum p(w_i) L_i(tau) G1) as a g1a SoA table; [tau^0] G2 and [tau^1] G2 as two g2a, and where
+// the setup file has it [tau^64] G2 as a third (the cell proofs of EIP-7594 pair against it).
 #pragma once
 #include "lb_fr.h"  // kzg_group_status
 #include "lb_kernels.h"
@@ -109,10 +110,10 @@ __global__ void __launch_bounds__(LB_TPB, LB_MINW) k_kzg_setup_g1(uint32_t n, co
 }
 #endif  // LB_KG
 #if LB_KG(7)
-__global__ void __launch_bounds__(64) k_kzg_setup_g2(const uint8_t* __restrict__ in96, uint32_t* __restrict__ g2,
+__global__ void __launch_bounds__(64) k_kzg_setup_g2(uint32_t n, const uint8_t* __restrict__ in96, uint32_t* __restrict__ g2,
                                                      int32_t* __restrict__ status) {
   const uint32_t i = threadIdx.x;
-  if (i >= 2) return;
+  if (i >= n || i >= 3) return;  // [tau^0] G2, [tau^1] G2 and, for the cell calls, [tau^64] G2
   uint8_t b[96];
   ld_bytes<96>(b, in96 + (size_t)96 * i);
   g2a a;
@@ -408,6 +409,148 @@ __global__ void __launch_bounds__(64) k_kzg_check_groups(uint32_t n, const uint3
     w_st(S, LBW_PT + 3, g1t.x.c1);
     w_st(S, LBW_PT + 4, g1t.y.c0);
     w_st(S, LBW_PT + 5, g1t.y.c1);
+  }
+  __syncthreads();
+  if (pinf_u)
+    w_set_one(S, LBW_A(7));
+  else
+    w_miller(S, LBW_A(7));
+  w_mul(S, LBW_A(0), LBW_A(0), LBW_A(7));
+  w_final_exp(S, LBW_A(0), LBW_A(0));
+  const bool one = w_is_one(S, LBW_A(0));
+  if (lane == 0) ok[k] = one ? 1 : 0;
+}
+#endif  // LB_KG
+
+// ------------------------------------------------------------------ cell proofs (EIP-7594)
+// k_g1_terms for the cell batch, both kinds of point in ONE launch (two launches of these
+// latency-bound ladders would run one after the other): thread i < n_pts takes given point i (48
+// compressed bytes, curve- and subgroup-checked) times scalars[i]; thread n_pts + t takes table entry
+// t mod period times tscalars[t] (lb_kzg_verify_cell_proof_batch: period 64, group g's negated
+// interpolation coefficients at 64 g .. 64 g + 63 against [tau^0 .. tau^63] G1).  Scalars: 8 LE words,
+// < r.  terms: a g1j SoA of n_pts + n_tab entries, status alike (LB_OK for setup points, which were
+// checked on load).  period <= table_cap (checked by the host).
+#if LB_KG(7)
+__global__ void __launch_bounds__(LB_TPB, LB_MINW) k_g1_cell_terms(uint32_t n_pts, const uint8_t* __restrict__ pts48,
+                                                          const uint32_t* __restrict__ scalars, uint32_t n_tab,
+                                                          const uint32_t* __restrict__ table, uint32_t table_cap, uint32_t period,
+                                                          const uint32_t* __restrict__ tscalars, uint32_t* __restrict__ terms,
+                                                          int32_t* __restrict__ status) {
+  const uint32_t i = lb_tid(), n = n_pts + n_tab;
+  if (i >= n) return;
+  g1a p;
+  bool inf = false;
+  int st = LB_OK;
+  const uint32_t* sc;
+  if (i < n_pts) {
+    uint8_t b[48];
+    ld_bytes<48>(b, pts48 + (size_t)48 * i);
+    st = g1_decompress48(b, p, inf);
+    if (st == LB_OK && !inf && !g1_in_subgroup_r(p)) st = LB_POINT_NOT_IN_GROUP;
+    sc = scalars + (size_t)8 * i;
+  } else {
+    p = soa_ld<g1a>(table, table_cap, (i - n_pts) % period);
+    sc = tscalars + (size_t)8 * (i - n_pts);
+  }
+  uint32_t k[8];
+  LB_UNROLL for (int w = 0; w < 8; w++) k[w] = sc[w];
+  g1j t = jac_infinity<fp>();
+  if (st == LB_OK && !inf) t = jac_mul_u256(p, k);
+  soa_st(terms, n, i, t);
+  status[i] = st;
+}
+#endif  // LB_KG
+
+// verify_cell_kzg_proof_batch (lb_kzg_verify_cell_proof_batch): one wave per group k, which owns cells
+// off[k] .. off[k + 1] - 1 of n_cells and the distinct commitments doff[k] .. doff[k + 1] - 1 of
+// n_comms.  With r the group's combiner, i the cell's place in its group and h its coset shift, the
+// ladders ran before, in one k_g1_cell_terms launch over 2 n_cells + n_comms given points and 64 n
+// table entries (terms as a g1j SoA of that many entries, tstatus):
+//   [0, n_cells)                  pi_j,  scalar r^i
+//   n_cells + j                   pi_j,  scalar r^i h^64
+//   2 n_cells + d                 distinct commitment d, scalar the sum of its cells' r^i
+//   2 n_cells + n_comms + 64 k + t   [tau^t] G1, scalar the NEGATED summed interpolation coefficient t
+// Here: the group's status
+// (lb_fr.h kzg_cell_group_status: commitments, cells, proofs), then
+//   LL = sum [r^i] pi_j,   RL = sum of the commitment terms + sum [r^i h^64] pi_j + the 64 table terms
+// and e(RL, -G2) e(LL, [tau^64] G2) == 1 on the wave engine; either point may be infinity, an empty
+// group accepts.  g2 = [tau^0] G2, [tau^1] G2, [tau^64] G2.  ok[k] = 1 / 0, or -code; a group with a bad
+// status never reaches the pairing.  All offsets are clamped before anything is indexed by them.
+#if LB_KG(5)
+__global__ void __launch_bounds__(64) k_kzg_check_cells(uint32_t n, const uint32_t* __restrict__ off, uint32_t n_cells,
+                                                        const uint32_t* __restrict__ doff, uint32_t n_comms,
+                                                        const int32_t* __restrict__ cstatus, const uint32_t* __restrict__ terms,
+                                                        const int32_t* __restrict__ tstatus, const uint32_t* __restrict__ g2,
+                                                        int32_t* __restrict__ ok) {
+  LBW_SHARED_ML(S);
+  __shared__ int st_sh, qinf_sh, pinf_sh;
+  const int lane = threadIdx.x;
+  const uint32_t k = blockIdx.x;
+  if (k >= n) return;
+  w_init_consts(S, LBW_PROGS_ALL);
+  const uint32_t n_given = 2 * n_cells + n_comms, n_pts = n_given + 64 * n;
+  const uint32_t hi = min(off[k + 1], n_cells), lo = min(off[k], hi), m = hi - lo;
+  const uint32_t dhi = min(doff[k + 1], n_comms), dlo = min(doff[k], dhi), d = dhi - dlo;
+  // RL: the commitment terms, the h^64 pi terms, the 64 table terms; 64 at a time
+  g1j v = jac_infinity<fp>();
+  for (uint32_t q = lane; q < d + m + 64; q += 64) {
+    const uint32_t idx = q < d ? 2 * n_cells + dlo + q : (q < d + m ? n_cells + lo + (q - d) : n_given + 64 * k + (q - d - m));
+    v = jac_add_i(v, soa_ld<g1j>(terms, n_pts, idx));
+  }
+  for (int l = 5; l >= 0; l--) {
+    const unsigned s = 1u << l;
+    const g1j o{fp_shfl_down(v.x, s), fp_shfl_down(v.y, s), fp_shfl_down(v.z, s)};
+    if (threadIdx.x < s) v = jac_add_i(v, o);
+  }
+  // LL: the pi terms
+  g1j u = jac_infinity<fp>();
+  for (uint32_t q = lane; q < m; q += 64) u = jac_add_i(u, soa_ld<g1j>(terms, n_pts, lo + q));
+  for (int l = 5; l >= 0; l--) {
+    const unsigned s = 1u << l;
+    const g1j o{fp_shfl_down(u.x, s), fp_shfl_down(u.y, s), fp_shfl_down(u.z, s)};
+    if (threadIdx.x < s) u = jac_add_i(u, o);
+  }
+  g1a pa;
+  if (lane == 0) {
+    const int st = kzg_cell_group_status(tstatus + 2 * n_cells, dlo, dhi, cstatus, tstatus, lo, hi);
+    bool qfin = false, pfin = false;
+    if (st == LB_OK) {
+      g1a qa;
+      qfin = jac_to_aff(qa, v);
+      pfin = jac_to_aff(pa, u);
+      w_st(S, LBW_PT + 0, qa.x);
+      w_st(S, LBW_PT + 1, qa.y);
+      const g2a* G = reinterpret_cast<const g2a*>(g2);
+      const g2a g0 = G[0];
+      w_st(S, LBW_PT + 2, g0.x.c0);
+      w_st(S, LBW_PT + 3, g0.x.c1);
+      w_st(S, LBW_PT + 4, fp_neg(g0.y.c0));  // -G2
+      w_st(S, LBW_PT + 5, fp_neg(g0.y.c1));
+    }
+    st_sh = st;
+    qinf_sh = qfin ? 0 : 1;
+    pinf_sh = pfin ? 0 : 1;
+  }
+  __syncthreads();
+  const int st_u = st_sh, qinf = qinf_sh, pinf_u = pinf_sh;
+  __syncthreads();
+  if (st_u != LB_OK) {
+    if (lane == 0) ok[k] = -st_u;
+    return;
+  }
+  if (qinf)
+    w_set_one(S, LBW_A(0));
+  else
+    w_miller(S, LBW_A(0));
+  if (lane == 0) {
+    const g2a* G = reinterpret_cast<const g2a*>(g2);
+    const g2a g64 = G[2];
+    w_st(S, LBW_PT + 0, pa.x);
+    w_st(S, LBW_PT + 1, pa.y);
+    w_st(S, LBW_PT + 2, g64.x.c0);
+    w_st(S, LBW_PT + 3, g64.x.c1);
+    w_st(S, LBW_PT + 4, g64.y.c0);
+    w_st(S, LBW_PT + 5, g64.y.c1);
   }
   __syncthreads();
   if (pinf_u)

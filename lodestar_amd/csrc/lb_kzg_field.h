@@ -233,3 +233,112 @@ __global__ void __launch_bounds__(LB_FR_WG) k_fr_eval_quotient_many(const uint32
   fr_eq_finish(A, z, src, lanes, t, q_le + (size_t)k * LB_FR_N * 8, y_le + (size_t)8 * k);
 }
 #endif  // LB_KG
+
+// ------------------------------------------------------------------ cells (EIP-7594; lb_fr.h)
+// lb_kzg_compute_cells, lb_kzg_compute_cell_proofs, lb_kzg_verify_cell_proof_batch.  `tab` is the
+// resident table of fr_cell_tables (lb_kzg_load_setup).
+#define LB_FR_CELL_BYTES (LB_FR_CELL * 32u)                 // BYTES_PER_CELL
+#define LB_FR_EXT_BYTES ((size_t)LB_FR_CELLS * LB_FR_CELL_BYTES)  // one blob's 128 cells
+
+// cells (n_cells x 64 x 32 bytes, big endian) -> Montgomery Fr; status[c] = LB_BAD_SCALAR if cell c
+// holds an element >= r (status zeroed by the caller, plain stores of one code as in k_fr_blob_load)
+#if LB_KG(16)
+__global__ void __launch_bounds__(256) k_fr_cell_load(uint32_t n_elems, const uint8_t* __restrict__ cells,
+                                                      uint32_t* __restrict__ out, int32_t* __restrict__ status) {
+  const uint32_t i = lb_tid();
+  if (i >= n_elems) return;
+  uint8_t b[32];
+  ld_bytes<32>(b, cells + (size_t)32 * i);
+  fr v;
+  const bool ok = fr_from_be32(v, b);
+  fr_stg(out + (size_t)8 * i, v);
+  if (!ok) status[i / LB_FR_CELL] = LB_BAD_SCALAR;
+}
+#endif  // LB_KG
+
+// One workgroup per blob, the shape of k_fr_intt4096 (1024 lanes, LB_FR_INTT_LDS bytes of dynamic
+// LDS): the blob's 4096 monomial coefficients (coef, Montgomery) -> its 128 cells.  Coefficient j
+// times w^j, twelve forward stages, and the values leave as big-endian bytes in bit-reversed order
+// into cells 64 .. 127 (lb_fr.h fr_coset_*); cells 0 .. 63 are the blob's own bytes, copied.
+#if LB_KG(16)
+__global__ void __launch_bounds__(LB_FR_WG) k_fr_coset_ntt4096(const uint32_t* __restrict__ coef, const uint8_t* __restrict__ blobs,
+                                                               const uint32_t* __restrict__ tab, uint8_t* __restrict__ out_cells) {
+  extern __shared__ uint32_t lb_fr_lds[];
+  fr_lds_poly A{lb_fr_lds};
+  const fr_gpoly C{coef + (size_t)blockIdx.x * LB_FR_N * 8};
+  const fr_gtable SC{tab + (size_t)8 * LB_FR_CELL_TAB_SCALE}, T{tab + (size_t)8 * LB_FR_CELL_TAB_FWD};
+  uint8_t* out = out_cells + (size_t)blockIdx.x * LB_FR_EXT_BYTES;
+  const uint4* src = reinterpret_cast<const uint4*>(blobs + (size_t)blockIdx.x * LB_FR_N * 32);
+  uint4* lower = reinterpret_cast<uint4*>(out);
+  for (uint32_t i = threadIdx.x; i < LB_FR_N * 2; i += LB_FR_WG) lower[i] = src[i];
+  fr_coset_load(A, C, SC, threadIdx.x, LB_FR_WG);
+  __syncthreads();
+  for (int s = 0; s < LB_FR_LOGN; s++) {
+    fr_ntt_stage(A, LB_FR_LOGN, s, T, threadIdx.x, LB_FR_WG);
+    __syncthreads();
+  }
+  uint32_t* upper = reinterpret_cast<uint32_t*>(out + (size_t)LB_FR_N * 32);
+  for (uint32_t k = threadIdx.x; k < LB_FR_N; k += LB_FR_WG) {
+    uint32_t w[8];
+    fr_to_be_words(w, fr_coset_value(A, k));
+    fr_stg(upper + (size_t)8 * k, fr_from_words(w));
+  }
+}
+#endif  // LB_KG
+
+// One wave per cell, in place over the cell's 64 Montgomery values: the 64-point inverse transform
+// (six stages in LDS, one element per lane), then lane j holds weight_c I_j (fr_cell_descale;
+// weight: one Montgomery value per cell, r^k of its group).  cell_index[c] < 128 (checked by the host).
+#if LB_KG(16)
+__global__ void __launch_bounds__(64) k_fr_cell_interp(uint32_t n_cells, uint32_t* __restrict__ cells, const uint32_t* __restrict__ cell_index,
+                                                       const uint32_t* __restrict__ weight, const uint32_t* __restrict__ tab) {
+  __shared__ uint32_t lds[LB_FR_CELL * 8];
+  const uint32_t c = blockIdx.x, t = threadIdx.x;
+  if (c >= n_cells) return;
+  fr_lds_vec V{lds, LB_FR_CELL};
+  const fr_gtable T{tab + (size_t)8 * LB_FR_CELL_TAB_ITW}, W{tab + (size_t)8 * LB_FR_CELL_TAB_WINV};
+  uint32_t* mine = cells + ((size_t)c * LB_FR_CELL + t) * 8;
+  V.st(t, fr_ldg(mine));
+  __syncthreads();
+  for (int s = 0; s < LB_FR_CELL_LOG; s++) {
+    fr_ntt_stage(V, LB_FR_CELL_LOG, s, T, t, LB_FR_CELL);
+    __syncthreads();
+  }
+  fr_stg(mine, fr_cell_descale(V.ld(t), T(LB_FR_CELL / 2), W, cell_index[c] & (LB_FR_CELLS - 1u), t, fr_ldg(weight + (size_t)8 * c)));
+}
+#endif  // LB_KG
+
+// The per-group sum of k_fr_cell_interp's output, one thread per (group, coefficient): the cells
+// off[g] .. off[g + 1] - 1 added in index order (no atomics, no floating order; lb_fr.h
+// fr_cell_group_sum), NEGATED, as plain LE words at out_le + (64 g + j) * 8: the scalars of
+// -RLI = -sum_j c_j [tau^j] G1 for k_g1_cell_terms.  A group may be empty (zeros) or long.
+// The offsets are clamped to n_cells and to each other before anything is indexed by them.
+struct fr_gcells {
+  const uint32_t* p;
+  __device__ __forceinline__ fr operator()(uint32_t k, uint32_t j) const { return fr_ldg(p + ((size_t)k * LB_FR_CELL + j) * 8); }
+};
+#if LB_KG(16)
+__global__ void __launch_bounds__(64) k_fr_cell_sum(uint32_t n_groups, const uint32_t* __restrict__ off, uint32_t n_cells,
+                                                    const uint32_t* __restrict__ cells, uint32_t* __restrict__ out_le) {
+  const uint32_t g = blockIdx.x, j = threadIdx.x;
+  if (g >= n_groups) return;
+  const uint32_t hi = min(off[g + 1], n_cells), lo = min(off[g], hi);
+  uint32_t w[8];
+  fr_to_le_words(w, fr_neg(fr_cell_group_sum(fr_gcells{cells}, lo, hi, j)));
+  fr_stg(out_le + ((size_t)g * LB_FR_CELL + j) * 8, fr_from_words(w));
+}
+#endif  // LB_KG
+
+// One wave per chosen cell of one blob: the quotient of p by X^64 - h^64 (lb_fr.h
+// fr_cell_quotient_lane) from the blob's coefficients (coef, Montgomery), 4096 plain LE scalars at
+// q_le + c * 4096 * 8 with the top 64 zero.  cell_index[c] < 128 (checked by the host).
+#if LB_KG(16)
+__global__ void __launch_bounds__(64) k_fr_cell_quotient(uint32_t n_cells, const uint32_t* __restrict__ coef, const uint32_t* __restrict__ cell_index,
+                                                         const uint32_t* __restrict__ tab, uint32_t* __restrict__ q_le) {
+  const uint32_t c = blockIdx.x;
+  if (c >= n_cells) return;
+  const fr_gtable W{tab + (size_t)8 * LB_FR_CELL_TAB_WINV};
+  fr_cell_quotient_lane(fr_gpoly{coef}, LB_FR_N, W(fr_cell_h64_index(cell_index[c] & (LB_FR_CELLS - 1u))), threadIdx.x,
+                        q_le + (size_t)c * LB_FR_N * 8);
+}
+#endif  // LB_KG

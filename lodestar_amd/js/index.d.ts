@@ -101,8 +101,21 @@ export interface CKzg {
    * GPU, in either field mode: true, false, or the Error the single call would throw, per group.
    */
   verifyBlobKzgProofBatchMany(groups: KzgBlobGroup[]): (boolean | Error)[];
+  /** c-kzg computeCells (EIP-7594): the blob's 128 cells of 2048 bytes, computed on the GPU. */
+  computeCells(blob: Uint8Array): Uint8Array[];
+  /** c-kzg verifyCellKzgProofBatch: one commitment, cell index, cell and proof per cell; on the GPU. */
+  verifyCellKzgProofBatch(commitments: Uint8Array[], cellIndices: number[], cells: Uint8Array[], proofs: Uint8Array[]): boolean;
+  /**
+   * verifyCellKzgProofBatch for many groups (data-column sidecars) in one pass over the GPU: true,
+   * false, or the Error the single call would throw, per group.
+   */
+  verifyCellKzgProofBatchMany(groups: KzgCellGroup[]): (boolean | Error)[];
+  readonly BYTES_PER_CELL: 2048;
+  readonly CELLS_PER_EXT_BLOB: 128;
   readonly G1_INFINITY48: Uint8Array;
 }
+/** One verifyCellKzgProofBatch call: one entry of each array per cell. */
+export type KzgCellGroup = {commitments: Uint8Array[]; cellIndices: number[]; cells: Uint8Array[]; proofs: Uint8Array[]};
 export type KzgSidecar = {blobs: Uint8Array[]; commitments: Uint8Array[]; proof: Uint8Array};
 /** One verifyBlobKzgProofBatch call: one proof per blob. */
 export type KzgBlobGroup = {blobs: Uint8Array[]; commitments: Uint8Array[]; proofs: Uint8Array[]};

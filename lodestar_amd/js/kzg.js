@@ -394,8 +394,93 @@ function verifyKzgProof(commitment, zBytes, yBytes, proof) {
   return addon.kzgVerifyProof(engine, commitment, bigToBytes(z, 32, true), bigToBytes(y, 32, true), proof);
 }
 
+// ------------------------------------------------------------------ cells (EIP-7594, PeerDAS)
+// c-kzg computeCells and verifyCellKzgProofBatch(commitments, cellIndices, cells, proofs), always on
+// the GPU (kzgComputeCells -> lb_kzg_compute_cells, kzgVerifyCellProofBatch ->
+// lb_kzg_verify_cell_proof_batch), in either field mode.  The batch's combiner (computeCellBatchR:
+// the commitments deduplicated in order of first appearance) hashes only the caller's bytes; like
+// the other transcripts its byte parity with c-kzg is unpinned, and no verdict depends on it.
+// computeCellsAndKzgProofs (FK20) and recoverCellsAndKzgProofs are not here.
+const BYTES_PER_CELL = 2048;
+const CELLS_PER_EXT_BLOB = 128;
+const CELL_DOMAIN = Buffer.from("RCKZGCBATCH__V1_", "ascii");
+
+function checkCell(c) {
+  if (!(c instanceof Uint8Array) || c.length !== BYTES_PER_CELL) throw Error("cell length != 2048");
+}
+function checkCellIndex(i) {
+  if (!Number.isInteger(i) || i < 0 || i >= CELLS_PER_EXT_BLOB) throw Error("cell index not below 128");
+}
+function computeCellBatchR(commitments, cellIndices, cells, proofs) {
+  const distinct = [];
+  const indexOf = new Map();
+  const ci = commitments.map((c) => {
+    const key = Buffer.from(c).toString("hex");
+    if (!indexOf.has(key)) {
+      indexOf.set(key, distinct.length);
+      distinct.push(Buffer.from(c));
+    }
+    return indexOf.get(key);
+  });
+  const u64 = (v) => bigToBytes(BigInt(v), 8, false);
+  const parts = [CELL_DOMAIN, u64(N), u64(64), u64(distinct.length), u64(cells.length), ...distinct];
+  cells.forEach((cell, k) => parts.push(u64(ci[k]), u64(cellIndices[k]), Buffer.from(cell), Buffer.from(proofs[k])));
+  return hashToBlsField(Buffer.concat(parts));
+}
+function computeCells(blob) {
+  requireSetup();
+  checkBlob(blob);
+  const all = addon.kzgComputeCells(engine, blob);
+  return Array.from({length: CELLS_PER_EXT_BLOB}, (_, i) => all.slice(BYTES_PER_CELL * i, BYTES_PER_CELL * (i + 1)));
+}
+// groups: {commitments, cellIndices, cells, proofs}[], one of each per cell.  One entry per group:
+// true, false, or the Error the single call would throw -- returned, not thrown.  Malformed input
+// throws before anything is sent.
+function verifyCellKzgProofBatchMany(groups) {
+  requireSetup();
+  const offsets = new Uint32Array(groups.length + 1);
+  const comms = [];
+  const idx = [];
+  const cells = [];
+  const proofs = [];
+  groups.forEach((g, k) => {
+    const n = g.cells.length;
+    if (g.commitments.length !== n || g.cellIndices.length !== n || g.proofs.length !== n) {
+      throw Error("commitments / cellIndices / cells / proofs length mismatch");
+    }
+    g.commitments.forEach((c) => check48(c, "commitment"));
+    g.proofs.forEach((p) => check48(p, "proof"));
+    g.cells.forEach(checkCell);
+    g.cellIndices.forEach(checkCellIndex);
+    comms.push(...g.commitments);
+    idx.push(...g.cellIndices);
+    cells.push(...g.cells);
+    proofs.push(...g.proofs);
+    offsets[k + 1] = cells.length;
+  });
+  if (!groups.length) return [];
+  const cm = new Uint8Array(48 * comms.length);
+  const pr = new Uint8Array(48 * proofs.length);
+  const ce = new Uint8Array(BYTES_PER_CELL * cells.length);
+  comms.forEach((c, i) => cm.set(c, 48 * i));
+  proofs.forEach((p, i) => pr.set(p, 48 * i));
+  cells.forEach((c, i) => ce.set(c, BYTES_PER_CELL * i));
+  const ok = addon.kzgVerifyCellProofBatch(engine, offsets, cm, Uint32Array.from(idx), ce, pr);
+  return Array.from(ok, (v) => (v < 0 ? Error(addon.errorName(-v)) : v === 1));
+}
+function verifyCellKzgProofBatch(commitments, cellIndices, cells, proofs) {
+  const res = verifyCellKzgProofBatchMany([{commitments, cellIndices, cells, proofs}])[0];
+  if (res instanceof Error) throw res;
+  return res;
+}
+
 module.exports = {
   loadTrustedSetup,
+  computeCells,
+  verifyCellKzgProofBatch,
+  verifyCellKzgProofBatchMany,
+  BYTES_PER_CELL,
+  CELLS_PER_EXT_BLOB,
   blobToKzgCommitment,
   computeAggregateKzgProof,
   verifyAggregateKzgProof,
@@ -408,5 +493,5 @@ module.exports = {
   verifyKzgProof,
   G1_INFINITY48,
   // host field work, exported for tests
-  _internal: {evaluationsToCoefficients, evaluate, quotient, computeChallenges, computeChallenge, computeBatchR, ROOTS, BRP, R},
+  _internal: {evaluationsToCoefficients, evaluate, quotient, computeChallenges, computeChallenge, computeBatchR, computeCellBatchR, ROOTS, BRP, R},
 };

@@ -28,6 +28,16 @@ The per-blob proof form that shipped in Deneb (c-kzg `computeBlobKzgProof`, `ver
 (`verify_blob_kzg_proof_batch`, `verify_blob_kzg_proof_batch_many` for many blocks' sidecars in one
 pass) always run on the GPU (`lb_kzg_verify_blob_proof_batch`).
 
+Cells (EIP-7594, "PeerDAS", the Fulu fork; c-kzg `computeCells`, `verifyCellKzgProofBatch`): the
+blob's polynomial over the 8192-point domain in 128 cells of 64 values, each cell with its own proof.
+`Kzg.compute_cells`, `Kzg.compute_cell_kzg_proofs` (the direct per-cell route, one multi-scalar
+multiplication per cell -- NOT `computeCellsAndKzgProofs`, which needs FK20) and
+`Kzg.verify_cell_kzg_proof_batch(_many)` always run on the GPU (`lb_kzg_compute_cells`,
+`lb_kzg_compute_cell_proofs`, `lb_kzg_verify_cell_proof_batch`), whatever `field` is.
+`compute_cell_batch_r` restates the batch's combiner; like the other transcripts its byte parity
+with c-kzg is UNPINNED, and the verdicts do not depend on its exact bytes: a valid batch passes for
+any r, an invalid one fails except with negligible probability.
+
 The setup is Lodestar's own `trusted_setup.bin` (kzg.ts:36-48: two u32 counts, 4096 compressed
 [tau^i] G1, 65 compressed [tau^i] G2), i.e. MONOMIAL form (setup_G1[0] is the G1 generator).
 Committing in monomial form, sum a_j [tau^j] G1 with a = IFFT of the blob's evaluations, gives
@@ -197,6 +207,45 @@ def compute_batch_r(commitments: Sequence[bytes], zs: Sequence[int], ys: Sequenc
     data += FIELD_ELEMENTS_PER_BLOB.to_bytes(8, ENDIANNESS) + n.to_bytes(8, ENDIANNESS)
     for c, z, y, p in zip(commitments, zs, ys, proofs):
         data += bytes(c) + int(z).to_bytes(32, ENDIANNESS) + int(y).to_bytes(32, ENDIANNESS) + bytes(p)
+    return hash_to_bls_field(bytes(data))
+
+
+# -- cells (EIP-7594): the extended domain, the cosets, the batch combiner
+FIELD_ELEMENTS_PER_EXT_BLOB = 8192
+FIELD_ELEMENTS_PER_CELL = 64
+BYTES_PER_CELL = FIELD_ELEMENTS_PER_CELL * BYTES_PER_FIELD_ELEMENT
+CELLS_PER_EXT_BLOB = FIELD_ELEMENTS_PER_EXT_BLOB // FIELD_ELEMENTS_PER_CELL
+RANDOM_CHALLENGE_KZG_CELL_BATCH_DOMAIN = b"RCKZGCBATCH__V1_"
+ROOT_OF_UNITY_EXT = pow(PRIMITIVE_ROOT_OF_UNITY, (BLS_MODULUS - 1) // FIELD_ELEMENTS_PER_EXT_BLOB, BLS_MODULUS)
+
+
+def coset_shift(cell_index: int) -> int:
+    """h_i = w^brp7(i): element t of cell i stands at h_i * w64^brp6(t), w64 = w^128"""
+    if not 0 <= cell_index < CELLS_PER_EXT_BLOB:
+        raise ValueError(f"cell index {cell_index} not below {CELLS_PER_EXT_BLOB}")
+    return pow(ROOT_OF_UNITY_EXT, int(format(cell_index, "07b")[::-1], 2), BLS_MODULUS)
+
+
+def compute_cell_batch_r(commitments: Sequence[bytes], cell_indices: Sequence[int], cells: Sequence[bytes],
+                         proofs: Sequence[bytes]) -> int:
+    """the combiner of verify_cell_kzg_proof_batch over one commitment, cell index, cell and proof per
+    cell: the commitments deduplicated in order of first appearance, then domain || 4096 || 64 ||
+    #distinct || n || the distinct commitments || per cell: commitment index || cell index || cell
+    (2048) || proof (48); every integer 8 bytes big-endian"""
+    n = len(cells)
+    if not (len(commitments) == len(cell_indices) == len(proofs) == n):
+        raise ValueError("compute_cell_batch_r: one commitment, cell index and proof per cell")
+    distinct, index_of = [], {}
+    for c in commitments:
+        if bytes(c) not in index_of:
+            index_of[bytes(c)] = len(distinct)
+            distinct.append(bytes(c))
+    data = bytearray(RANDOM_CHALLENGE_KZG_CELL_BATCH_DOMAIN)
+    for v in (FIELD_ELEMENTS_PER_BLOB, FIELD_ELEMENTS_PER_CELL, len(distinct), n):
+        data += v.to_bytes(8, ENDIANNESS)
+    data += b"".join(distinct)
+    for c, i, cell, p in zip(commitments, cell_indices, cells, proofs):
+        data += index_of[bytes(c)].to_bytes(8, ENDIANNESS) + int(i).to_bytes(8, ENDIANNESS) + bytes(cell) + bytes(p)
     return hash_to_bls_field(bytes(data))
 
 
@@ -510,7 +559,86 @@ class Kzg:
         y = self._field_element("verifyKzgProof", y32)
         return self.verify_kzg_proof(commitment, z, y, proof)
 
+    # -- cells (EIP-7594): computeCells, verifyCellKzgProofBatch; always on the device
+    def compute_cells(self, blob: bytes) -> List[bytes]:
+        """c-kzg computeCells: the blob's 128 cells of 2048 bytes (`lb_kzg_compute_cells`)"""
+        u8, i32 = ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_int32)
+        src = self._blob_bytes([blob])
+        out = np.zeros(CELLS_PER_EXT_BLOB * BYTES_PER_CELL, np.uint8)
+        status = np.zeros(1, np.int32)
+        self._check(self.lib.lb_kzg_compute_cells(self.engine.h, 1, src.ctypes.data_as(u8), out.ctypes.data_as(u8),
+                                                  status.ctypes.data_as(i32)), "computeCells")
+        self._check(int(status[0]), "computeCells")
+        raw = out.tobytes()
+        return [raw[BYTES_PER_CELL * i: BYTES_PER_CELL * (i + 1)] for i in range(CELLS_PER_EXT_BLOB)]
+
+    def compute_cell_kzg_proofs(self, blob: bytes, cell_indices: Sequence[int]) -> List[bytes]:
+        """the proofs of the chosen cells of one blob by the direct route (`lb_kzg_compute_cell_proofs`):
+        one 4096-term multi-scalar multiplication per cell, so for a few cells -- this is not
+        computeCellsAndKzgProofs"""
+        what = "computeCellKzgProofs"
+        idx = [int(i) for i in cell_indices]
+        if any(not 0 <= i < CELLS_PER_EXT_BLOB for i in idx):
+            raise KzgError(f"{what}: cell indices below {CELLS_PER_EXT_BLOB}")
+        u8, i32 = ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_int32)
+        src = self._blob_bytes([blob])
+        ci = np.asarray(idx or [0], np.uint32)
+        out = np.zeros(48 * max(len(idx), 1), np.uint8)
+        status = np.zeros(1, np.int32)
+        self._check(self.lib.lb_kzg_compute_cell_proofs(self.engine.h, src.ctypes.data_as(u8), len(idx),
+                                                        ci.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)),
+                                                        out.ctypes.data_as(u8), status.ctypes.data_as(i32)), what)
+        self._check(int(status[0]), what)
+        return [out[48 * c: 48 * c + 48].tobytes() for c in range(len(idx))]
+
+    def verify_cell_kzg_proof_batch_many(self, groups: Sequence[Tuple[Sequence[bytes], Sequence[int], Sequence[bytes], Sequence[bytes]]]) -> list:
+        """verify_cell_kzg_proof_batch for many groups (one group = one call's commitments, cell
+        indices, cells, proofs, one of each per cell) in one pass over the GPU
+        (`lb_kzg_verify_cell_proof_batch`), whatever `field` is.  One entry per group: True, False, or
+        the KzgError the single call would raise -- returned, not raised.  Malformed input (length
+        mismatches, a wrong cell or point length, a cell index >= 128) raises before anything is sent."""
+        what = "verifyCellKzgProofBatch"
+        offsets, comms, idx, cells, proofs = [0], [], [], [], []
+        for g_comms, g_idx, g_cells, g_proofs in groups:
+            if not (len(g_comms) == len(g_idx) == len(g_cells) == len(g_proofs)):
+                raise KzgError(f"{what}: commitments / cell indices / cells / proofs length mismatch")
+            self._points48(what, g_comms, g_proofs)
+            if any(len(c) != BYTES_PER_CELL for c in g_cells):
+                raise KzgError(f"{what}: {BYTES_PER_CELL}-byte cells")
+            if any(not 0 <= int(i) < CELLS_PER_EXT_BLOB for i in g_idx):
+                raise KzgError(f"{what}: cell indices below {CELLS_PER_EXT_BLOB}")
+            comms += [bytes(c) for c in g_comms]
+            idx += [int(i) for i in g_idx]
+            cells += [bytes(c) for c in g_cells]
+            proofs += [bytes(p) for p in g_proofs]
+            offsets.append(len(cells))
+        n = len(offsets) - 1
+        if n == 0:
+            return []
+        u8, u32, i32 = ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_int32)
+        cm = np.frombuffer(b"".join(comms) or b"\x00", np.uint8)
+        ce = np.frombuffer(b"".join(cells) or b"\x00", np.uint8)
+        pf = np.frombuffer(b"".join(proofs) or b"\x00", np.uint8)
+        ci = np.asarray(idx or [0], np.uint32)
+        off = np.asarray(offsets, np.uint32)
+        ok = np.zeros(n, np.int32)
+        self._check(self.lib.lb_kzg_verify_cell_proof_batch(
+            self.engine.h, n, off.ctypes.data_as(u32), cm.ctypes.data_as(u8), ci.ctypes.data_as(u32), ce.ctypes.data_as(u8),
+            pf.ctypes.data_as(u8), ok.ctypes.data_as(i32)), f"{what}Many")
+        return [KzgError(f"{what}: {self._N.error_name(-int(v))}") if v < 0 else bool(v == 1) for v in ok]
+
+    def verify_cell_kzg_proof_batch(self, commitments: Sequence[bytes], cell_indices: Sequence[int], cells: Sequence[bytes],
+                                    proofs: Sequence[bytes]) -> bool:
+        """c-kzg verifyCellKzgProofBatch: one group"""
+        res = self.verify_cell_kzg_proof_batch_many([(commitments, cell_indices, cells, proofs)])[0]
+        if isinstance(res, KzgError):
+            raise res
+        return res
+
     # the ckzg names kzg.ts binds
+    computeCells = compute_cells
+    verifyCellKzgProofBatch = verify_cell_kzg_proof_batch
+    verifyCellKzgProofBatchMany = verify_cell_kzg_proof_batch_many
     computeBlobKzgProof = compute_blob_kzg_proof
     verifyBlobKzgProof = verify_blob_kzg_proof
     verifyBlobKzgProofBatch = verify_blob_kzg_proof_batch

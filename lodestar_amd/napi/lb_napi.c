@@ -54,6 +54,9 @@
  *     blob (Deneb), throws the first rejected blob's code
  *   kzgVerifyBlobProofBatch(engine, blobs, groupOffsets: Uint32Array, commitments, proofs)
  *     -> Int32Array: many verifyBlobKzgProofBatch groups in one pass, 1 / 0 / -code per group
+ *   kzgComputeCells(engine, blob) -> Uint8Array (128 x 2048 B): the blob's cells (EIP-7594)
+ *   kzgVerifyCellProofBatch(engine, cellOffsets: Uint32Array, commitments, cellIndices: Uint32Array,
+ *     cells, proofs) -> Int32Array: many verifyCellKzgProofBatch groups in one pass, 1 / 0 / -code
  *   (the KZG calls are synchronous, as c-kzg's are; lodestar_amd/js/kzg.js builds the ckzg
  *   module surface of util/kzg.ts on them)
  */
@@ -908,6 +911,64 @@ static napi_value kzg_verify_blob_proof_batch(napi_env env, napi_callback_info i
   return out;
 }
 
+/* Cells (EIP-7594; lb_kzg_compute_cells): the 128 cells of one blob as one Uint8Array of 128 x 2048
+ * bytes.  A blob element >= r is thrown. */
+#define LB_CELL_BYTES 2048u
+static napi_value kzg_compute_cells(napi_env env, napi_callback_info info) {
+  size_t argc = 2;
+  napi_value argv[2];
+  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  engine_box* b = NULL;
+  tview bl;
+  if (argc < 2 || napi_get_value_external(env, argv[0], (void**)&b) != napi_ok || !b || !b->e ||
+      !get_view(env, argv[1], &bl) || !bl.present || bl.type != napi_uint8_array || bl.n != LB_BLOB_BYTES) {
+    napi_throw_type_error(env, NULL, "kzgComputeCells(engine, blob: Uint8Array of 131072 bytes)");
+    return NULL;
+  }
+  napi_value ab, out;
+  void* po;
+  NAPI_CALL(env, napi_create_arraybuffer(env, (size_t)128 * LB_CELL_BYTES, &po, &ab));
+  int32_t st = LB_OK;
+  const int32_t r = lb_kzg_compute_cells(b->e, 1, (const uint8_t*)bl.data, (uint8_t*)po, &st);
+  if (r != LB_OK || st != LB_OK) return throw_code(env, r != LB_OK ? r : st);
+  NAPI_CALL(env, napi_create_typedarray(env, napi_uint8_array, (size_t)128 * LB_CELL_BYTES, ab, 0, &out));
+  return out;
+}
+
+/* Many verifyCellKzgProofBatch groups in one pass (lb_kzg_verify_cell_proof_batch): group k owns
+ * cells cellOffsets[k] .. cellOffsets[k + 1] - 1 of the flat per-cell arrays.  One int32 per group:
+ * 1, 0, or -code, as the C call gives them; nothing is thrown for a group that rejects. */
+static napi_value kzg_verify_cell_proof_batch(napi_env env, napi_callback_info info) {
+  size_t argc = 6;
+  napi_value argv[6];
+  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  engine_box* b = NULL;
+  tview of, cm, ix, ce, pr;
+  if (argc < 6 || napi_get_value_external(env, argv[0], (void**)&b) != napi_ok || !b || !b->e ||
+      !get_view(env, argv[1], &of) || !of.present || of.type != napi_uint32_array || of.n < 1 ||
+      !get_view(env, argv[2], &cm) || !cm.present || cm.type != napi_uint8_array || cm.n % 48 ||
+      !get_view(env, argv[3], &ix) || !ix.present || ix.type != napi_uint32_array || ix.n != cm.n / 48 ||
+      !get_view(env, argv[4], &ce) || !ce.present || ce.type != napi_uint8_array || ce.n != ix.n * LB_CELL_BYTES ||
+      !get_view(env, argv[5], &pr) || !pr.present || pr.type != napi_uint8_array || pr.n != cm.n ||
+      ((const uint32_t*)of.data)[of.n - 1] != ix.n) {
+    napi_throw_type_error(env, NULL,
+                          "kzgVerifyCellProofBatch(engine, cellOffsets: Uint32Array of n + 1 prefix sums ending in c, "
+                          "commitments: Uint8Array of c x 48 bytes, cellIndices: Uint32Array of c, "
+                          "cells: Uint8Array of c x 2048 bytes, proofs: Uint8Array of c x 48 bytes)");
+    return NULL;
+  }
+  const uint32_t n = (uint32_t)(of.n - 1);
+  napi_value ab, out;
+  void* po;
+  NAPI_CALL(env, napi_create_arraybuffer(env, (size_t)n * 4, &po, &ab));
+  const int32_t r = lb_kzg_verify_cell_proof_batch(b->e, n, (const uint32_t*)of.data, (const uint8_t*)cm.data,
+                                                   (const uint32_t*)ix.data, (const uint8_t*)ce.data,
+                                                   (const uint8_t*)pr.data, (int32_t*)po);
+  if (r != LB_OK) return throw_code(env, r);
+  NAPI_CALL(env, napi_create_typedarray(env, napi_int32_array, n, ab, 0, &out));
+  return out;
+}
+
 static napi_value table_size(napi_env env, napi_callback_info info) {
   size_t argc = 1;
   napi_value argv[1], v;
@@ -959,6 +1020,8 @@ static napi_value init(napi_env env, napi_value exports) {
       {"kzgVerifyAggregateProofBatch", NULL, kzg_verify_aggregate_proof_batch, NULL, NULL, NULL, napi_default, NULL},
       {"kzgComputeBlobProofs", NULL, kzg_compute_blob_proofs, NULL, NULL, NULL, napi_default, NULL},
       {"kzgVerifyBlobProofBatch", NULL, kzg_verify_blob_proof_batch, NULL, NULL, NULL, napi_default, NULL},
+      {"kzgComputeCells", NULL, kzg_compute_cells, NULL, NULL, NULL, napi_default, NULL},
+      {"kzgVerifyCellProofBatch", NULL, kzg_verify_cell_proof_batch, NULL, NULL, NULL, napi_default, NULL},
   };
   napi_define_properties(env, exports, sizeof(props) / sizeof(props[0]), props);
   return exports;

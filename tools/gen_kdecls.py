@@ -34,11 +34,11 @@ GROUPS = {
     14: ["k_gsum_wave", "k_pk_out96"],
     5: ["k_miller_wave", "k_tree_up_U", "k_ml_S", "k_root_check", "k_root_partial", "k_partials_check", "k_search_ml",
         "k_search_fe", "k_search_match", "k_miller_g8", "k_kzg_check", "k_kzg_check_many",
-        "k_kzg_check_groups"],
+        "k_kzg_check_groups", "k_kzg_check_cells"],
     6: ["k_msm_count", "k_msm_scatter", "k_msm_chunks", "k_msm_buckets", "k_msm_reduce"],
     7: ["k_smsm_count", "k_smsm_scatter", "k_smsm_terms_g8", "k_smsm_terms_lane", "k_seg_sum64", "k_seg_final",
         "k_rsm_terms", "k_range_pk", "k_test_pk", "k_g1_terms", "k_g1_sum64", "k_g1_out48",
-        "k_kzg_setup_g1", "k_kzg_setup_g2"],
+        "k_kzg_setup_g1", "k_kzg_setup_g2", "k_g1_cell_terms"],
     8: ["k_hash_finish_g8"],
     9: ["k_msm_buckets_g8", "k_msm_window_g8", "k_msm_horner_g8", "k_sig_blind_g8", "k_sig_blind", "k_g2_sum64", "k_sig_unblinded", "k_g2_sum_g8"],
     10: ["k_miller_row", "k_tree_up_row"],
@@ -48,7 +48,8 @@ GROUPS = {
     15: ["k_comb_fill", "k_pk_blind_comb"],
     # KZG scalar field (lb_kzg_field.h), beside the KZG group kernels of group 7
     16: ["k_fr_blob_load", "k_fr_aggregate", "k_fr_intt4096", "k_fr_eval_quotient", "k_fr_aggregate_seg",
-         "k_fr_eval_many", "k_fr_eval_quotient_many"],
+         "k_fr_eval_many", "k_fr_eval_quotient_many", "k_fr_cell_load", "k_fr_coset_ntt4096", "k_fr_cell_interp",
+         "k_fr_cell_sum", "k_fr_cell_quotient"],
 }
 N_GROUPS = len(GROUPS)
 GROUP_OF = {k: g for g, ks in GROUPS.items() for k in ks}
