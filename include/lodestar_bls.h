@@ -334,9 +334,9 @@ int32_t lb_kzg_verify_blob_proof_batch(lb_engine* e, uint32_t n_groups,
  *
  * lb_kzg_compute_cell_proofs: the proofs of n_cells <= 128 chosen cells of ONE blob by the spec's
  * direct route, proof_i = commit((p - I_i) / (X^64 - h_i^64)): the quotient on the device, then one
- * 4096-term multi-scalar multiplication PER CELL.  This is not computeCellsAndKzgProofs (which needs
- * FK20 to be affordable for all 128 cells); it gives a producer, and the tests, a device route to a
- * few cells.  *out_status = LB_OK or LB_BAD_SCALAR (the proofs are then zeroed); a cell index >= 128
+ * 4096-term multi-scalar multiplication PER CELL: the route to a few cells.  For all 128 proofs of
+ * whole blobs use lb_kzg_compute_cells_and_proofs below, which gives the same bytes by FK20 at about
+ * the price of a dozen such multiplications.  *out_status = LB_OK or LB_BAD_SCALAR (the proofs are then zeroed); a cell index >= 128
  * is LB_ERR_ARGUMENT.
  *
  * lb_kzg_verify_cell_proof_batch: one group is one verifyCellKzgProofBatch call (a data-column
@@ -354,6 +354,17 @@ int32_t lb_kzg_verify_blob_proof_batch(lb_engine* e, uint32_t n_groups,
  * at once); LB_ERR_ARGUMENT for no 4096-point setup or one loaded with n_g2 < 65, a needed pointer that
  * is NULL, cell_offsets[0] != 0, decreasing offsets, a cell index >= 128, more than 1024 groups or
  * more than 16384 cells in all.  lb_kzg_batch_hash_ns reports this call's hashing time too.
+ *
+ * lb_kzg_compute_cells_and_proofs (ckzg.computeCellsAndKzgProofs) for n_blobs <= 128 blobs: out_cells[b]
+ * = the 128 cells of blob b, exactly lb_kzg_compute_cells' bytes, and out_proofs48[b] = its 128 cell
+ * proofs, proof i = commit((p - I_i) / (X^64 - h_i^64)): the bytes lb_kzg_compute_cell_proofs gives for
+ * cell i (a compressed point is canonical), computed by FK20: one ladder pass over a resident 8192-point
+ * transform of the setup, two 128-point transforms in G1 per blob.  That table is built on the first
+ * call after lb_kzg_load_setup (once per setup; the call that builds it takes that much longer).
+ * out_status[b] = LB_OK, or LB_BAD_SCALAR for a blob element >= r: that blob's cells and proofs are
+ * zeroed, the other blobs are unaffected.  Returns LB_OK whenever the call ran (n_blobs == 0: at once,
+ * nothing read); LB_ERR_ARGUMENT for no 4096-point setup, a needed pointer that is NULL or
+ * n_blobs > 128.  It pairs against nothing: a setup loaded with two G2 points will do.
  */
 int32_t lb_kzg_compute_cells(lb_engine* e, uint32_t n_blobs, const uint8_t* blobs, /* n_blobs x 131072 B */
                              uint8_t* out_cells,                                  /* n_blobs x 128 x 2048 B */
@@ -368,6 +379,10 @@ int32_t lb_kzg_verify_cell_proof_batch(lb_engine* e, uint32_t n_groups,
                                        const uint8_t* cells,          /* cell_offsets[n] x 2048 B */
                                        const uint8_t* proofs48,       /* cell_offsets[n] x 48 B */
                                        int32_t* out_ok);              /* n_groups */
+int32_t lb_kzg_compute_cells_and_proofs(lb_engine* e, uint32_t n_blobs, const uint8_t* blobs, /* n x 131072 B */
+                                        uint8_t* out_cells,    /* n x 128 x 2048 B */
+                                        uint8_t* out_proofs48, /* n x 128 x 48 B   */
+                                        int32_t* out_status);  /* n */
 
 /*
  * Synthetic-data helpers for tests and the benchmark (not on the verification path):

@@ -206,6 +206,25 @@ def build_kzg_cells_harness(force=False, verbose=True):
     return KZG_CELLS_HARNESS
 
 
+KZG_FK20_HARNESS = os.path.join(ROOT, "build", "lb_kzg_fk20_harness.so")
+
+
+def build_kzg_fk20_harness(force=False, verbose=True):
+    """the column transforms and the 128-point transform's schedule, over the scalar field and over G1
+    points, of the FK20 call on the CPU (tests/test_kzg_fk20_cpu.py)"""
+    hdir = os.path.join(ROOT, "tests", "harness")
+    src = os.path.join(hdir, "lb_kzg_fk20_harness.cpp")
+    os.makedirs(os.path.dirname(KZG_FK20_HARNESS), exist_ok=True)
+    if not force and not _stale(KZG_FK20_HARNESS, _deps() + [src, os.path.join(hdir, "kzg_fk20_lanes.h")]):
+        return KZG_FK20_HARNESS
+    cmd = ["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-I" + INC, "-I" + CSRC, src, "-o", KZG_FK20_HARNESS + ".tmp"]
+    if verbose:
+        print("[build]", " ".join(cmd), flush=True)
+    subprocess.run(cmd, check=True)
+    os.replace(KZG_FK20_HARNESS + ".tmp", KZG_FK20_HARNESS)
+    return KZG_FK20_HARNESS
+
+
 def build_cpu_pool(force=False, verbose=True):
     src = os.path.join(ROOT, "oracle", "cpu_pool.cpp")
     if not os.path.exists(src):
@@ -269,6 +288,7 @@ def build_all(force=False):
     build_kzg_batch_harness(force)
     build_kzg_blob_harness(force)
     build_kzg_cells_harness(force)
+    build_kzg_fk20_harness(force)
     build_cpu_pool(force)
     build_ubench(force)
 

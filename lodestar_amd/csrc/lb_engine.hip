@@ -24,6 +24,7 @@
 #include "lb_kernels.h"
 #include "lb_kzg.h"
 #include "lb_kzg_field.h"
+#include "lb_kzg_fk20.h"
 #include "lb_kzg_transcript.h"
 #include "lb_kdecl.h"  // kernels of the other translation units (split build)
 
@@ -247,6 +248,11 @@ struct lb_engine {
   dbuf kzg_cell_tab;
   bool kzg_cells = false;
   std::vector<fr> kzg_h64;
+  // FK20 (lb_kzg_compute_cells_and_proofs; lb_fk20.h): the twiddle table of fk_tables and the extended
+  // setup X_i[r] (8192 g1j SoA, entry 64 r + i, Jacobian so that O is z = 0), built on the first call
+  // under `mu` and dropped by lb_kzg_load_setup
+  dbuf kzg_fk_tw, kzg_fk_x;
+  bool kzg_fk_ready = false;
   uint64_t kzg_batch_hash_ns = 0;  // host transcript hashing of the last batch verification (lb_kzg_batch_hash_ns)
   // profiling
   bool profiling = false;
@@ -596,7 +602,8 @@ void lb_engine_destroy(lb_engine* e) {
                   &e->gch, &e->chunk_beg, &e->chunk_end, &e->members, &e->set_live, &e->gacc, &e->gp_aff,
                   &e->gp_inf, &e->chunk_root, &e->sig_aos, &e->bcnt, &e->bcursor, &e->boff, &e->bch, &e->bchunk_beg,
                   &e->bchunk_end, &e->bmembers, &e->bacc, &e->bsum, &e->wsum, &e->park, &e->pk_aff, &e->y_root, &e->kzg_g1,
-                  &e->kzg_g2, &e->kzg_tw, &e->kzg_cell_tab, &e->s_terms, &e->s_part, &e->s_root, &e->rs_idx, &e->s_set};
+                  &e->kzg_g2, &e->kzg_tw, &e->kzg_cell_tab, &e->kzg_fk_tw, &e->kzg_fk_x, &e->s_terms, &e->s_part, &e->s_root,
+                  &e->rs_idx, &e->s_set};
   for (dbuf* b : bufs) b->release();
   for (dbuf& b : e->sx) b.release();
   for (int i = 0; i < kStages; i++) {
@@ -2368,6 +2375,8 @@ extern "C" int32_t lb_kzg_load_setup(lb_engine* e, const uint8_t* g1_48, uint32_
   {
     std::lock_guard<std::mutex> lk(e->mu);
     LB_HIP(hipSetDevice(e->device));
+    e->kzg_fk_ready = false;  // the FK20 table belongs to the setup it was built from
+    e->kzg_fk_x.release();
     LB_HIP(e->kzg_g1.ensure((size_t)n_g1 * sizeof(g1a)));
     LB_HIP(e->kzg_g2.ensure(3 * sizeof(g2a)));
   }
@@ -2406,6 +2415,7 @@ extern "C" int32_t lb_kzg_load_setup(lb_engine* e, const uint8_t* g1_48, uint32_
     LB_HIP(e->kzg_cell_tab.ensure(ct.size() * sizeof(fr)));
     LB_HIP(hipMemcpyAsync(e->kzg_cell_tab.p, ct.data(), ct.size() * sizeof(fr), hipMemcpyHostToDevice, e->stream));
     LB_HIP(hipStreamSynchronize(e->stream));
+    e->kzg_fk_ready = false;  // ... also one that a call built while this load was under way
   }
   e->kzg_n = n_g1;
   e->kzg_cells = n2 == 3;
@@ -3237,5 +3247,103 @@ extern "C" int32_t lb_kzg_verify_cell_proof_batch(lb_engine* e, uint32_t n_group
   LB_KZG_TRY(hipGetLastError());
   LB_KZG_TRY(hipMemcpyAsync(out_ok, w.ok.p, (size_t)n * 4, hipMemcpyDeviceToHost, e->stream));
   LB_KZG_TRY(hipStreamSynchronize(e->stream));
+  return LB_OK;
+}
+
+// ---------------------------------------------------------------- KZG cells and all their proofs (FK20; lb_fk20.h)
+namespace {
+constexpr uint32_t kMaxFkBlobs = 128;  // per call: 8192 ladders and 1.2 MB of terms per blob
+
+// n_tr transforms of 128 points between g1j SoA buffers (k_g1_fft128); tw_entry: LB_FK_TAB_FWD / _INV
+void kzg_fk_fft(lb_engine* e, uint32_t n_tr, const uint32_t* in, uint32_t in_cap, uint32_t in_st, uint32_t in_sj, uint32_t n_live,
+                uint32_t tw_entry, uint32_t* out, uint32_t out_cap, uint32_t out_st, uint32_t out_sm) {
+  hipLaunchKernelGGL(k_g1_fft128, dim3(n_tr), dim3(64), 0, e->stream, n_tr, in, in_cap, in_st, in_sj, n_live,
+                     e->kzg_fk_tw.as<uint32_t>() + (size_t)8 * tw_entry, (const uint32_t*)nullptr, out, out_cap, out_st, out_sm);
+}
+
+// The extended setup X_i[r] = DFT128(x_i)[r] at entry 64 r + i, once per loaded setup: the 64 strided,
+// padded columns of the setup (k_g1_fk_gather), one transform each.  Caller holds e->mu.
+int32_t kzg_fk_table(lb_engine* e) {
+  if (e->kzg_fk_ready) return LB_OK;
+  std::vector<fr> tab(LB_FK_TAB_LEN);
+  fk_tables(tab.data());
+  kzg_ws w;  // w.terms: the gathered columns, freed on every way out
+  LB_KZG_TRY(e->kzg_fk_tw.ensure(tab.size() * sizeof(fr)));
+  LB_KZG_TRY(e->kzg_fk_x.ensure((size_t)LB_FK_POINTS * sizeof(g1j)));
+  LB_KZG_TRY(w.terms.ensure((size_t)LB_FK_POINTS * sizeof(g1j)));
+  LB_KZG_TRY(hipMemcpyAsync(e->kzg_fk_tw.p, tab.data(), tab.size() * sizeof(fr), hipMemcpyHostToDevice, e->stream));
+  hipLaunchKernelGGL(k_g1_fk_gather, dim3(nblk(LB_FK_POINTS)), dim3(LB_TPB), 0, e->stream, e->kzg_g1.as<uint32_t>(), e->kzg_n,
+                     w.terms.as<uint32_t>());
+  kzg_fk_fft(e, LB_FK_COLS, w.terms.as<uint32_t>(), LB_FK_POINTS, LB_FK_N, 1, LB_FK_N, LB_FK_TAB_FWD, e->kzg_fk_x.as<uint32_t>(),
+             LB_FK_POINTS, 1, LB_FK_COLS);
+  LB_KZG_TRY(hipGetLastError());
+  LB_KZG_TRY(hipStreamSynchronize(e->stream));
+  e->kzg_fk_ready = true;
+  return LB_OK;
+}
+}  // namespace
+
+// compute_cells_and_kzg_proofs for n_blobs blobs with ONE synchronisation (after the table's first
+// build): a blob with an element >= r still runs, on the reduced element, and is zeroed afterwards.
+extern "C" int32_t lb_kzg_compute_cells_and_proofs(lb_engine* e, uint32_t n_blobs, const uint8_t* blobs, uint8_t* out_cells,
+                                                   uint8_t* out_proofs48, int32_t* out_status) {
+  if (!kzg_ready(e) || n_blobs > kMaxFkBlobs) return LB_ERR_ARGUMENT;
+  if (!n_blobs) return LB_OK;
+  if (!blobs || !out_cells || !out_proofs48 || !out_status) return LB_ERR_ARGUMENT;
+  const uint32_t n = n_blobs, np = n * LB_FK_N, nt = n * LB_FK_POINTS;
+  const size_t proof_bytes = (size_t)LB_FK_N * 48;
+  std::lock_guard<std::mutex> lk(e->mu);
+  kzg_ws w;
+  LB_KZG_TRY(hipSetDevice(e->device));
+  int32_t rc = kzg_fk_table(e);
+  if (rc != LB_OK) return rc;
+  LB_KZG_TRY(w.blobs.ensure(n * kBlobBytes));
+  LB_KZG_TRY(w.polys.ensure(n * kBlobBytes));
+  LB_KZG_TRY(w.status.ensure((size_t)n * 4));
+  LB_KZG_TRY(w.coef.ensure(n * kBlobBytes));
+  LB_KZG_TRY(w.le.ensure(n * LB_FR_EXT_BYTES));
+  LB_KZG_TRY(w.tsc.ensure((size_t)nt * sizeof(fr)));
+  LB_KZG_TRY(w.terms.ensure((size_t)nt * sizeof(g1j)));
+  LB_KZG_TRY(w.part.ensure((size_t)np * sizeof(g1j)));
+  LB_KZG_TRY(w.agg.ensure((size_t)np * sizeof(g1j)));
+  LB_KZG_TRY(w.io.ensure(n * proof_bytes));
+  // 1. decode, coefficients, and the cells by the path of lb_kzg_compute_cells
+  LB_KZG_TRY(hipMemcpyAsync(w.blobs.p, blobs, n * kBlobBytes, hipMemcpyHostToDevice, e->stream));
+  LB_KZG_TRY(hipMemsetAsync(w.status.p, 0, (size_t)n * 4, e->stream));
+  hipLaunchKernelGGL(k_fr_blob_load, dim3((n * LB_FR_N + 255) / 256), dim3(256), 0, e->stream, n * LB_FR_N, w.blobs.as<uint8_t>(),
+                     w.polys.as<uint32_t>(), w.status.as<int32_t>());
+  LB_KZG_TRY(hipGetLastError());
+  rc = kzg_intt(e, n, w.polys.as<uint32_t>(), w.coef.as<uint32_t>(), nullptr);
+  if (rc != LB_OK) return rc;
+  LB_KZG_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_fr_coset_ntt4096),
+                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)LB_FR_INTT_LDS));
+  hipLaunchKernelGGL(k_fr_coset_ntt4096, dim3(n), dim3(LB_FR_WG), LB_FR_INTT_LDS, e->stream, w.coef.as<uint32_t>(),
+                     w.blobs.as<uint8_t>(), e->kzg_cell_tab.as<uint32_t>(), w.le.as<uint8_t>());
+  LB_KZG_TRY(hipGetLastError());
+  // 2. the 64 column transforms per blob -> the scalars C_i[r] / 128 in the table's order
+  hipLaunchKernelGGL(k_fr_fk_cols, dim3(n * LB_FK_COLS), dim3(64), 0, e->stream, n, w.coef.as<uint32_t>(), e->kzg_fk_tw.as<uint32_t>(),
+                     w.tsc.as<uint32_t>());
+  // 3. every ladder of the call in one launch, then E[r]: entry 128 b + r of w.part
+  hipLaunchKernelGGL(k_g1_jac_terms, dim3(nblk(nt)), dim3(LB_TPB), 0, e->stream, nt, e->kzg_fk_x.as<uint32_t>(), LB_FK_POINTS,
+                     w.tsc.as<uint32_t>(), w.terms.as<uint32_t>());
+  hipLaunchKernelGGL(k_g1_sum64, dim3(np), dim3(64), 0, e->stream, nt, w.terms.as<uint32_t>(), np, w.part.as<uint32_t>());
+  LB_KZG_TRY(hipGetLastError());
+  // 4. h = IDFT(E) (scaled already); the proofs = DFT(h[0 .. 63], O ...): h[64 .. 127] are dropped by the load
+  kzg_fk_fft(e, n, w.part.as<uint32_t>(), np, LB_FK_N, 1, LB_FK_N, LB_FK_TAB_INV, w.agg.as<uint32_t>(), np, LB_FK_N, 1);
+  kzg_fk_fft(e, n, w.agg.as<uint32_t>(), np, LB_FK_N, 1, LB_FK_LIVE, LB_FK_TAB_FWD, w.part.as<uint32_t>(), np, LB_FK_N, 1);
+  hipLaunchKernelGGL(k_g1_fk_out48, dim3(np / 64), dim3(64), 0, e->stream, np, w.part.as<uint32_t>(), w.io.as<uint8_t>());
+  LB_KZG_TRY(hipGetLastError());
+  w.h_status.assign(n, LB_OK);
+  LB_KZG_TRY(hipMemcpyAsync(out_cells, w.le.p, n * LB_FR_EXT_BYTES, hipMemcpyDeviceToHost, e->stream));
+  LB_KZG_TRY(hipMemcpyAsync(out_proofs48, w.io.p, n * proof_bytes, hipMemcpyDeviceToHost, e->stream));
+  LB_KZG_TRY(hipMemcpyAsync(w.h_status.data(), w.status.p, (size_t)n * 4, hipMemcpyDeviceToHost, e->stream));
+  LB_KZG_TRY(hipStreamSynchronize(e->stream));
+  for (uint32_t b = 0; b < n; b++) {
+    out_status[b] = w.h_status[b];
+    if (out_status[b] != LB_OK) {
+      memset(out_cells + b * LB_FR_EXT_BYTES, 0, LB_FR_EXT_BYTES);
+      memset(out_proofs48 + b * proof_bytes, 0, proof_bytes);
+    }
+  }
   return LB_OK;
 }

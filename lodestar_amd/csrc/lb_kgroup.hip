@@ -4,4 +4,5 @@
 #include "lb_kernels.h"
 #include "lb_kzg.h"
 #include "lb_kzg_field.h"
+#include "lb_kzg_fk20.h"
 #include "lb_kdecl.h"

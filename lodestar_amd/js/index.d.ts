@@ -103,6 +103,16 @@ export interface CKzg {
   verifyBlobKzgProofBatchMany(groups: KzgBlobGroup[]): (boolean | Error)[];
   /** c-kzg computeCells (EIP-7594): the blob's 128 cells of 2048 bytes, computed on the GPU. */
   computeCells(blob: Uint8Array): Uint8Array[];
+  /**
+   * c-kzg computeCellsAndKzgProofs: [the blob's 128 cells, their 128 proofs of 48 bytes], all proofs in
+   * one FK20 pass over the GPU.
+   */
+  computeCellsAndKzgProofs(blob: Uint8Array): [Uint8Array[], Uint8Array[]];
+  /**
+   * computeCellsAndKzgProofs for many blobs in one pass: [cells, proofs], or the Error the single call
+   * would throw, per blob.
+   */
+  computeCellsAndKzgProofsMany(blobs: Uint8Array[]): ([Uint8Array[], Uint8Array[]] | Error)[];
   /** c-kzg verifyCellKzgProofBatch: one commitment, cell index, cell and proof per cell; on the GPU. */
   verifyCellKzgProofBatch(commitments: Uint8Array[], cellIndices: number[], cells: Uint8Array[], proofs: Uint8Array[]): boolean;
   /**

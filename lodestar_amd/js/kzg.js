@@ -395,12 +395,13 @@ function verifyKzgProof(commitment, zBytes, yBytes, proof) {
 }
 
 // ------------------------------------------------------------------ cells (EIP-7594, PeerDAS)
-// c-kzg computeCells and verifyCellKzgProofBatch(commitments, cellIndices, cells, proofs), always on
-// the GPU (kzgComputeCells -> lb_kzg_compute_cells, kzgVerifyCellProofBatch ->
-// lb_kzg_verify_cell_proof_batch), in either field mode.  The batch's combiner (computeCellBatchR:
+// c-kzg computeCells, computeCellsAndKzgProofs and verifyCellKzgProofBatch(commitments, cellIndices,
+// cells, proofs), always on the GPU (kzgComputeCells -> lb_kzg_compute_cells, kzgComputeCellsAndProofs
+// -> lb_kzg_compute_cells_and_proofs: FK20, kzgVerifyCellProofBatch -> lb_kzg_verify_cell_proof_batch),
+// in either field mode.  The batch's combiner (computeCellBatchR:
 // the commitments deduplicated in order of first appearance) hashes only the caller's bytes; like
 // the other transcripts its byte parity with c-kzg is unpinned, and no verdict depends on it.
-// computeCellsAndKzgProofs (FK20) and recoverCellsAndKzgProofs are not here.
+// recoverCellsAndKzgProofs is not here.
 const BYTES_PER_CELL = 2048;
 const CELLS_PER_EXT_BLOB = 128;
 const CELL_DOMAIN = Buffer.from("RCKZGCBATCH__V1_", "ascii");
@@ -432,6 +433,39 @@ function computeCells(blob) {
   checkBlob(blob);
   const all = addon.kzgComputeCells(engine, blob);
   return Array.from({length: CELLS_PER_EXT_BLOB}, (_, i) => all.slice(BYTES_PER_CELL * i, BYTES_PER_CELL * (i + 1)));
+}
+// One entry per blob: [cells, proofs] (128 of each) as c-kzg's computeCellsAndKzgProofs gives them, or
+// the Error the single call would throw -- returned, not thrown.  A wrong blob length throws before
+// anything is sent; more than 128 blobs go in passes.
+const MAX_BLOBS_PER_CELLS_AND_PROOFS_CALL = 128;
+function computeCellsAndKzgProofsMany(blobs) {
+  requireSetup();
+  blobs.forEach(checkBlob);
+  const res = [];
+  for (let lo = 0; lo < blobs.length; lo += MAX_BLOBS_PER_CELLS_AND_PROOFS_CALL) {
+    const part = blobs.slice(lo, lo + MAX_BLOBS_PER_CELLS_AND_PROOFS_CALL);
+    const flat = new Uint8Array(BYTES_PER_BLOB * part.length);
+    part.forEach((b, i) => flat.set(b, BYTES_PER_BLOB * i));
+    const {cells, proofs, status} = addon.kzgComputeCellsAndProofs(engine, flat);
+    part.forEach((_, b) => {
+      if (status[b] !== 0) {
+        res.push(Error(addon.errorName(status[b])));
+        return;
+      }
+      const c0 = b * CELLS_PER_EXT_BLOB * BYTES_PER_CELL;
+      const p0 = b * CELLS_PER_EXT_BLOB * 48;
+      res.push([
+        Array.from({length: CELLS_PER_EXT_BLOB}, (_x, i) => cells.slice(c0 + BYTES_PER_CELL * i, c0 + BYTES_PER_CELL * (i + 1))),
+        Array.from({length: CELLS_PER_EXT_BLOB}, (_x, i) => proofs.slice(p0 + 48 * i, p0 + 48 * (i + 1))),
+      ]);
+    });
+  }
+  return res;
+}
+function computeCellsAndKzgProofs(blob) {
+  const res = computeCellsAndKzgProofsMany([blob])[0];
+  if (res instanceof Error) throw res;
+  return res;
 }
 // groups: {commitments, cellIndices, cells, proofs}[], one of each per cell.  One entry per group:
 // true, false, or the Error the single call would throw -- returned, not thrown.  Malformed input
@@ -477,6 +511,8 @@ function verifyCellKzgProofBatch(commitments, cellIndices, cells, proofs) {
 module.exports = {
   loadTrustedSetup,
   computeCells,
+  computeCellsAndKzgProofs,
+  computeCellsAndKzgProofsMany,
   verifyCellKzgProofBatch,
   verifyCellKzgProofBatchMany,
   BYTES_PER_CELL,

@@ -31,9 +31,10 @@ pass) always run on the GPU (`lb_kzg_verify_blob_proof_batch`).
 Cells (EIP-7594, "PeerDAS", the Fulu fork; c-kzg `computeCells`, `verifyCellKzgProofBatch`): the
 blob's polynomial over the 8192-point domain in 128 cells of 64 values, each cell with its own proof.
 `Kzg.compute_cells`, `Kzg.compute_cell_kzg_proofs` (the direct per-cell route, one multi-scalar
-multiplication per cell -- NOT `computeCellsAndKzgProofs`, which needs FK20) and
-`Kzg.verify_cell_kzg_proof_batch(_many)` always run on the GPU (`lb_kzg_compute_cells`,
-`lb_kzg_compute_cell_proofs`, `lb_kzg_verify_cell_proof_batch`), whatever `field` is.
+multiplication per cell), `Kzg.compute_cells_and_kzg_proofs(_many)` (c-kzg `computeCellsAndKzgProofs`:
+all 128 proofs of a blob by FK20) and `Kzg.verify_cell_kzg_proof_batch(_many)` always run on the GPU
+(`lb_kzg_compute_cells`, `lb_kzg_compute_cell_proofs`, `lb_kzg_compute_cells_and_proofs`,
+`lb_kzg_verify_cell_proof_batch`), whatever `field` is.
 `compute_cell_batch_r` restates the batch's combiner; like the other transcripts its byte parity
 with c-kzg is UNPINNED, and the verdicts do not depend on its exact bytes: a valid batch passes for
 any r, an invalid one fails except with negligible probability.
@@ -215,6 +216,7 @@ FIELD_ELEMENTS_PER_EXT_BLOB = 8192
 FIELD_ELEMENTS_PER_CELL = 64
 BYTES_PER_CELL = FIELD_ELEMENTS_PER_CELL * BYTES_PER_FIELD_ELEMENT
 CELLS_PER_EXT_BLOB = FIELD_ELEMENTS_PER_EXT_BLOB // FIELD_ELEMENTS_PER_CELL
+MAX_BLOBS_PER_CELLS_AND_PROOFS_CALL = 128   # lb_kzg_compute_cells_and_proofs' limit; longer lists go in passes
 RANDOM_CHALLENGE_KZG_CELL_BATCH_DOMAIN = b"RCKZGCBATCH__V1_"
 ROOT_OF_UNITY_EXT = pow(PRIMITIVE_ROOT_OF_UNITY, (BLS_MODULUS - 1) // FIELD_ELEMENTS_PER_EXT_BLOB, BLS_MODULUS)
 
@@ -574,8 +576,8 @@ class Kzg:
 
     def compute_cell_kzg_proofs(self, blob: bytes, cell_indices: Sequence[int]) -> List[bytes]:
         """the proofs of the chosen cells of one blob by the direct route (`lb_kzg_compute_cell_proofs`):
-        one 4096-term multi-scalar multiplication per cell, so for a few cells -- this is not
-        computeCellsAndKzgProofs"""
+        one 4096-term multi-scalar multiplication per cell, so for a few cells; compute_cells_and_kzg_proofs
+        gives all 128"""
         what = "computeCellKzgProofs"
         idx = [int(i) for i in cell_indices]
         if any(not 0 <= i < CELLS_PER_EXT_BLOB for i in idx):
@@ -590,6 +592,43 @@ class Kzg:
                                                         out.ctypes.data_as(u8), status.ctypes.data_as(i32)), what)
         self._check(int(status[0]), what)
         return [out[48 * c: 48 * c + 48].tobytes() for c in range(len(idx))]
+
+    def compute_cells_and_kzg_proofs_many(self, blobs: Sequence[bytes]) -> list:
+        """compute_cells_and_kzg_proofs for many blobs in passes of up to 128 over the GPU
+        (`lb_kzg_compute_cells_and_proofs`: FK20), whatever `field` is.  One entry per blob: the pair
+        (128 cells, 128 proofs), or the KzgError the single call would raise -- returned, not raised.
+        A wrong blob length raises before anything is sent."""
+        what = "computeCellsAndKzgProofs"
+        for b in blobs:
+            if len(b) != BYTES_PER_BLOB:
+                raise ValueError(f"blob length {len(b)} != {BYTES_PER_BLOB}")
+        u8, i32 = ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_int32)
+        res: list = []
+        for lo in range(0, len(blobs), MAX_BLOBS_PER_CELLS_AND_PROOFS_CALL):
+            part = blobs[lo: lo + MAX_BLOBS_PER_CELLS_AND_PROOFS_CALL]
+            n = len(part)
+            src = self._blob_bytes(part)
+            cells = np.zeros(n * CELLS_PER_EXT_BLOB * BYTES_PER_CELL, np.uint8)
+            proofs = np.zeros(n * CELLS_PER_EXT_BLOB * 48, np.uint8)
+            status = np.zeros(n, np.int32)
+            self._check(self.lib.lb_kzg_compute_cells_and_proofs(self.engine.h, n, src.ctypes.data_as(u8), cells.ctypes.data_as(u8),
+                                                                 proofs.ctypes.data_as(u8), status.ctypes.data_as(i32)), f"{what}Many")
+            craw, praw = cells.tobytes(), proofs.tobytes()
+            for b in range(n):
+                if status[b] != 0:
+                    res.append(KzgError(f"{what}: {self._N.error_name(int(status[b]))}"))
+                    continue
+                c0, p0 = b * CELLS_PER_EXT_BLOB * BYTES_PER_CELL, b * CELLS_PER_EXT_BLOB * 48
+                res.append(([craw[c0 + BYTES_PER_CELL * i: c0 + BYTES_PER_CELL * (i + 1)] for i in range(CELLS_PER_EXT_BLOB)],
+                            [praw[p0 + 48 * i: p0 + 48 * (i + 1)] for i in range(CELLS_PER_EXT_BLOB)]))
+        return res
+
+    def compute_cells_and_kzg_proofs(self, blob: bytes) -> Tuple[List[bytes], List[bytes]]:
+        """c-kzg computeCellsAndKzgProofs: (the blob's 128 cells, their 128 proofs)"""
+        res = self.compute_cells_and_kzg_proofs_many([blob])[0]
+        if isinstance(res, KzgError):
+            raise res
+        return res
 
     def verify_cell_kzg_proof_batch_many(self, groups: Sequence[Tuple[Sequence[bytes], Sequence[int], Sequence[bytes], Sequence[bytes]]]) -> list:
         """verify_cell_kzg_proof_batch for many groups (one group = one call's commitments, cell
@@ -637,6 +676,8 @@ class Kzg:
 
     # the ckzg names kzg.ts binds
     computeCells = compute_cells
+    computeCellsAndKzgProofs = compute_cells_and_kzg_proofs
+    computeCellsAndKzgProofsMany = compute_cells_and_kzg_proofs_many
     verifyCellKzgProofBatch = verify_cell_kzg_proof_batch
     verifyCellKzgProofBatchMany = verify_cell_kzg_proof_batch_many
     computeBlobKzgProof = compute_blob_kzg_proof

@@ -18,7 +18,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "lodestar_amd", "csrc")
-FILES = ["lb_kernels.h", "lb_group_exec.h", "lb_kzg.h", "lb_kzg_field.h", "lb_ssz.h", "lb_latency.h"]
+FILES = ["lb_kernels.h", "lb_group_exec.h", "lb_kzg.h", "lb_kzg_field.h", "lb_kzg_fk20.h", "lb_ssz.h", "lb_latency.h"]
 OUT = os.path.join(CSRC, "lb_kdecl.h")
 
 # kernel -> translation-unit group (balanced by measured compile time; the one-lane per-root and
@@ -50,6 +50,8 @@ GROUPS = {
     16: ["k_fr_blob_load", "k_fr_aggregate", "k_fr_intt4096", "k_fr_eval_quotient", "k_fr_aggregate_seg",
          "k_fr_eval_many", "k_fr_eval_quotient_many", "k_fr_cell_load", "k_fr_coset_ntt4096", "k_fr_cell_interp",
          "k_fr_cell_sum", "k_fr_cell_quotient"],
+    # FK20 (lb_kzg_fk20.h): the G1 transform, the table, the column transforms, the proofs' way out
+    17: ["k_g1_fk_gather", "k_g1_fft128", "k_fr_fk_cols", "k_g1_jac_terms", "k_g1_fk_out48"],
 }
 N_GROUPS = len(GROUPS)
 GROUP_OF = {k: g for g, ks in GROUPS.items() for k in ks}
