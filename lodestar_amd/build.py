@@ -48,10 +48,13 @@ def _jobs():
     return max(1, min(16, n, int(os.environ.get("MAX_JOBS", "16") or 16)))
 
 
+HOST_UNITS = [("lb_engine.hip", "engine.o"), ("lb_kzg_host.hip", "kzg_host.o")]
+
+
 def build_lib(force=False, verbose=True, extra_flags=(), out=None):
     """The split build (tools/gen_kdecls.py): lb_kgroup.hip once per kernel group (-DLB_KGROUP=g)
-    and lb_engine.hip (host code + launches, -DLB_KGROUP=99), compiled in parallel, linked into
-    one shared library."""
+    and the host units (host code + launches, -DLB_KGROUP=99: lb_engine.hip, the BLS pipeline, and
+    lb_kzg_host.hip, the KZG calls), compiled in parallel, linked into one shared library."""
     out = out or LIB
     if not force and not extra_flags and not _stale(out, _deps()):
         return out
@@ -65,34 +68,35 @@ def build_lib(force=False, verbose=True, extra_flags=(), out=None):
     os.makedirs(odir, exist_ok=True)
     base = [HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result",
             "-Wno-unused-value", "-I" + INC, "-I" + CSRC, *extra_flags]
-    units = [(os.path.join(CSRC, "lb_engine.hip"), "99", os.path.join(odir, "engine.o"))]
+    units = [(os.path.join(CSRC, src), "99", os.path.join(odir, obj)) for src, obj in HOST_UNITS]
     units += [(os.path.join(CSRC, "lb_kgroup.hip"), str(g), os.path.join(odir, f"kgroup{g}.o"))
               for g in range(gen_kdecls.N_GROUPS)]
     # the slowest units first
     order = [u for u in units if u[1] in ("3", "6", "8", "9", "7")] + [u for u in units if u[1] not in ("3", "6", "8", "9", "7")]
     running, failed = [], []
     t0 = time.time()
-    # per-unit staleness: the kernel groups do not include lb_engine.hip (host code + launches)
-    kdeps = [d for d in _deps() if os.path.basename(d) != "lb_engine.hip"]
-    pend = [u for u in order if force or extra_flags or _stale(u[2], _deps() if u[1] == "99" else kdeps)]
+    # per-unit staleness: every unit on the headers, lb_kgroup.hip and a host unit also on itself;
+    # no unit includes a host unit, so the kernel groups outlive a change to the host code
+    hdrs = [d for d in _deps() if os.path.basename(d) not in [src for src, _ in HOST_UNITS]]
+    pend = [u for u in order if force or extra_flags or _stale(u[2], hdrs + [u[0]])]
     while pend or running:
         while pend and len(running) < _jobs():
             src, g, obj = pend.pop(0)
             cmd = base + ["-DLB_KGROUP=" + g, "-c", src, "-o", obj]
             if verbose:
                 print("[build]", " ".join(cmd[-5:]), flush=True)
-            running.append((subprocess.Popen(cmd), g, time.time()))
+            running.append((subprocess.Popen(cmd), os.path.basename(obj), time.time()))
         time.sleep(0.2)
         for r in list(running):
             rc = r[0].poll()
             if rc is not None:
                 running.remove(r)
                 if verbose:
-                    print(f"[build] group {r[1]} done in {time.time() - r[2]:.0f} s (rc {rc})", flush=True)
+                    print(f"[build] {r[1]} done in {time.time() - r[2]:.0f} s (rc {rc})", flush=True)
                 if rc != 0:
                     failed.append(r[1])
     if failed:
-        raise subprocess.CalledProcessError(1, f"hipcc (groups {failed})")
+        raise subprocess.CalledProcessError(1, f"hipcc ({failed})")
     cmd = [HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", *[u[2] for u in units], "-o", out + ".tmp"]
     subprocess.run(cmd, check=True)
     os.replace(out + ".tmp", out)
@@ -101,144 +105,75 @@ def build_lib(force=False, verbose=True, extra_flags=(), out=None):
     return out
 
 
-def build_harness(force=False, verbose=True):
-    src = os.path.join(ROOT, "tests", "harness", "lb_harness.cpp")
-    os.makedirs(os.path.dirname(HARNESS), exist_ok=True)
-    if not force and not _stale(HARNESS, _deps() + [src]):
-        return HARNESS
-    cmd = ["g++", "-O2", "-shared", "-fPIC", "-I" + INC, "-I" + CSRC, src, "-o", HARNESS + ".tmp"]
+def _build_so(src, out, extra_deps=(), flags=("-O2",), force=False, verbose=True):
+    """one g++ shared object from one source; stale on the source, the csrc headers and extra_deps"""
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    if not force and not _stale(out, _deps() + [src, *extra_deps]):
+        return out
+    cmd = ["g++", *flags, "-shared", "-fPIC", "-I" + INC, "-I" + CSRC, src, "-o", out + ".tmp"]
     if verbose:
         print("[build]", " ".join(cmd), flush=True)
     subprocess.run(cmd, check=True)
-    os.replace(HARNESS + ".tmp", HARNESS)
-    return HARNESS
+    os.replace(out + ".tmp", out)
+    return out
 
 
+HDIR = os.path.join(ROOT, "tests", "harness")
+FR_VIEWS = os.path.join(HDIR, "fr_views.h")  # the pointer views the kzg_*_lanes.h headers share
 COMB_HARNESS = os.path.join(ROOT, "build", "lb_comb_harness.so")
+FR_HARNESS = os.path.join(ROOT, "build", "lb_fr_harness.so")
+KZG_BATCH_HARNESS = os.path.join(ROOT, "build", "lb_kzg_batch_harness.so")
+KZG_BLOB_HARNESS = os.path.join(ROOT, "build", "lb_kzg_blob_harness.so")
+KZG_CELLS_HARNESS = os.path.join(ROOT, "build", "lb_kzg_cells_harness.so")
+KZG_FK20_HARNESS = os.path.join(ROOT, "build", "lb_kzg_fk20_harness.so")
+
+
+def build_harness(force=False, verbose=True):
+    return _build_so(os.path.join(HDIR, "lb_harness.cpp"), HARNESS, force=force, verbose=verbose)
 
 
 def build_comb_harness(force=False, verbose=True):
     """the fixed-base comb of the resident pubkey table on the CPU (tests/test_pk_comb_cpu.py)"""
-    src = os.path.join(ROOT, "tests", "harness", "lb_comb_harness.cpp")
-    os.makedirs(os.path.dirname(COMB_HARNESS), exist_ok=True)
-    if not force and not _stale(COMB_HARNESS, _deps() + [src]):
-        return COMB_HARNESS
-    cmd = ["g++", "-O2", "-shared", "-fPIC", "-I" + INC, "-I" + CSRC, src, "-o", COMB_HARNESS + ".tmp"]
-    if verbose:
-        print("[build]", " ".join(cmd), flush=True)
-    subprocess.run(cmd, check=True)
-    os.replace(COMB_HARNESS + ".tmp", COMB_HARNESS)
-    return COMB_HARNESS
-
-
-FR_HARNESS = os.path.join(ROOT, "build", "lb_fr_harness.so")
+    return _build_so(os.path.join(HDIR, "lb_comb_harness.cpp"), COMB_HARNESS, force=force, verbose=verbose)
 
 
 def build_fr_harness(force=False, verbose=True):
     """the scalar field, its transform and the evaluate-and-divide scan on the CPU (tests/test_fr_cpu.py)"""
-    src = os.path.join(ROOT, "tests", "harness", "lb_fr_harness.cpp")
-    os.makedirs(os.path.dirname(FR_HARNESS), exist_ok=True)
-    if not force and not _stale(FR_HARNESS, _deps() + [src]):
-        return FR_HARNESS
-    cmd = ["g++", "-O2", "-shared", "-fPIC", "-I" + INC, "-I" + CSRC, src, "-o", FR_HARNESS + ".tmp"]
-    if verbose:
-        print("[build]", " ".join(cmd), flush=True)
-    subprocess.run(cmd, check=True)
-    os.replace(FR_HARNESS + ".tmp", FR_HARNESS)
-    return FR_HARNESS
-
-
-KZG_BATCH_HARNESS = os.path.join(ROOT, "build", "lb_kzg_batch_harness.so")
+    return _build_so(os.path.join(HDIR, "lb_fr_harness.cpp"), FR_HARNESS, force=force, verbose=verbose)
 
 
 def build_kzg_batch_harness(force=False, verbose=True):
     """the segmented aggregation and the evaluation of the batched KZG verification on the CPU
     (tests/test_kzg_batch_cpu.py)"""
-    src = os.path.join(ROOT, "tests", "harness", "lb_kzg_batch_harness.cpp")
-    os.makedirs(os.path.dirname(KZG_BATCH_HARNESS), exist_ok=True)
-    if not force and not _stale(KZG_BATCH_HARNESS, _deps() + [src]):
-        return KZG_BATCH_HARNESS
-    cmd = ["g++", "-O2", "-shared", "-fPIC", "-I" + INC, "-I" + CSRC, src, "-o", KZG_BATCH_HARNESS + ".tmp"]
-    if verbose:
-        print("[build]", " ".join(cmd), flush=True)
-    subprocess.run(cmd, check=True)
-    os.replace(KZG_BATCH_HARNESS + ".tmp", KZG_BATCH_HARNESS)
-    return KZG_BATCH_HARNESS
-
-
-KZG_BLOB_HARNESS = os.path.join(ROOT, "build", "lb_kzg_blob_harness.so")
+    return _build_so(os.path.join(HDIR, "lb_kzg_batch_harness.cpp"), KZG_BATCH_HARNESS, force=force, verbose=verbose)
 
 
 def build_kzg_blob_harness(force=False, verbose=True):
-    """the transcripts, the many-polynomial quotient scan and the status fold of the per-blob KZG
-    calls on the CPU (tests/test_kzg_blob_cpu.py)"""
-    hdir = os.path.join(ROOT, "tests", "harness")
-    src = os.path.join(hdir, "lb_kzg_blob_harness.cpp")
-    os.makedirs(os.path.dirname(KZG_BLOB_HARNESS), exist_ok=True)
-    if not force and not _stale(KZG_BLOB_HARNESS, _deps() + [src, os.path.join(hdir, "kzg_blob_lanes.h")]):
-        return KZG_BLOB_HARNESS
-    cmd = ["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-pthread", "-I" + INC, "-I" + CSRC, src,
-           "-o", KZG_BLOB_HARNESS + ".tmp"]
-    if verbose:
-        print("[build]", " ".join(cmd), flush=True)
-    subprocess.run(cmd, check=True)
-    os.replace(KZG_BLOB_HARNESS + ".tmp", KZG_BLOB_HARNESS)
-    return KZG_BLOB_HARNESS
-
-
-KZG_CELLS_HARNESS = os.path.join(ROOT, "build", "lb_kzg_cells_harness.so")
+    """the transcripts, the many-polynomial quotient scan, the status fold and the offsets validator of
+    the per-blob KZG calls on the CPU (tests/test_kzg_blob_cpu.py)"""
+    return _build_so(os.path.join(HDIR, "lb_kzg_blob_harness.cpp"), KZG_BLOB_HARNESS,
+                     [os.path.join(HDIR, "kzg_blob_lanes.h"), FR_VIEWS], ("-O2", "-std=c++17", "-pthread"), force, verbose)
 
 
 def build_kzg_cells_harness(force=False, verbose=True):
     """the combiner, the coset transform, the cell interpolation and quotient lanes and the status fold
     of the cell calls on the CPU (tests/test_kzg_cells_cpu.py)"""
-    hdir = os.path.join(ROOT, "tests", "harness")
-    src = os.path.join(hdir, "lb_kzg_cells_harness.cpp")
-    os.makedirs(os.path.dirname(KZG_CELLS_HARNESS), exist_ok=True)
-    if not force and not _stale(KZG_CELLS_HARNESS, _deps() + [src, os.path.join(hdir, "kzg_cells_lanes.h")]):
-        return KZG_CELLS_HARNESS
-    cmd = ["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-pthread", "-I" + INC, "-I" + CSRC, src,
-           "-o", KZG_CELLS_HARNESS + ".tmp"]
-    if verbose:
-        print("[build]", " ".join(cmd), flush=True)
-    subprocess.run(cmd, check=True)
-    os.replace(KZG_CELLS_HARNESS + ".tmp", KZG_CELLS_HARNESS)
-    return KZG_CELLS_HARNESS
-
-
-KZG_FK20_HARNESS = os.path.join(ROOT, "build", "lb_kzg_fk20_harness.so")
+    return _build_so(os.path.join(HDIR, "lb_kzg_cells_harness.cpp"), KZG_CELLS_HARNESS,
+                     [os.path.join(HDIR, "kzg_cells_lanes.h"), FR_VIEWS], ("-O2", "-std=c++17", "-pthread"), force, verbose)
 
 
 def build_kzg_fk20_harness(force=False, verbose=True):
     """the column transforms and the 128-point transform's schedule, over the scalar field and over G1
     points, of the FK20 call on the CPU (tests/test_kzg_fk20_cpu.py)"""
-    hdir = os.path.join(ROOT, "tests", "harness")
-    src = os.path.join(hdir, "lb_kzg_fk20_harness.cpp")
-    os.makedirs(os.path.dirname(KZG_FK20_HARNESS), exist_ok=True)
-    if not force and not _stale(KZG_FK20_HARNESS, _deps() + [src, os.path.join(hdir, "kzg_fk20_lanes.h")]):
-        return KZG_FK20_HARNESS
-    cmd = ["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-I" + INC, "-I" + CSRC, src, "-o", KZG_FK20_HARNESS + ".tmp"]
-    if verbose:
-        print("[build]", " ".join(cmd), flush=True)
-    subprocess.run(cmd, check=True)
-    os.replace(KZG_FK20_HARNESS + ".tmp", KZG_FK20_HARNESS)
-    return KZG_FK20_HARNESS
+    return _build_so(os.path.join(HDIR, "lb_kzg_fk20_harness.cpp"), KZG_FK20_HARNESS,
+                     [os.path.join(HDIR, "kzg_fk20_lanes.h"), FR_VIEWS], ("-O2", "-std=c++17"), force, verbose)
 
 
 def build_cpu_pool(force=False, verbose=True):
     src = os.path.join(ROOT, "oracle", "cpu_pool.cpp")
     if not os.path.exists(src):
         return None
-    os.makedirs(os.path.dirname(CPU_POOL), exist_ok=True)
-    if not force and not _stale(CPU_POOL, _deps() + [src]):
-        return CPU_POOL
-    cmd = ["g++", "-O3", "-shared", "-fPIC", "-pthread", "-I" + INC, "-I" + CSRC, src,
-           "-o", CPU_POOL + ".tmp"]
-    if verbose:
-        print("[build]", " ".join(cmd), flush=True)
-    subprocess.run(cmd, check=True)
-    os.replace(CPU_POOL + ".tmp", CPU_POOL)
-    return CPU_POOL
+    return _build_so(src, CPU_POOL, flags=("-O3", "-pthread"), force=force, verbose=verbose)
 
 
 UBENCH = ["fpmul_asm"]  # tools/ubench programs the GPU tests run (correctness of the asm Fp multiply)

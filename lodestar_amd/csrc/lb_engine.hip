@@ -22,74 +22,12 @@
 #include <vector>
 
 #include "lb_kernels.h"
-#include "lb_kzg.h"
-#include "lb_kzg_field.h"
-#include "lb_kzg_fk20.h"
-#include "lb_kzg_transcript.h"
+#include "lb_engine_impl.h"  // dbuf, lb_engine, LB_HIP, run_simple: shared with lb_kzg_host.hip (the KZG calls)
 #include "lb_kdecl.h"  // kernels of the other translation units (split build)
 
 #define LB_ABI_VERSION 1
 
 namespace {
-
-struct dbuf {
-  void* p = nullptr;
-  size_t cap = 0;
-  bool view = false;  // p points into another buffer (a batch's upload arena): never freed here
-  hipError_t ensure(size_t bytes) {
-    if (view) {
-      p = nullptr;
-      cap = 0;
-      view = false;
-    }
-    if (bytes <= cap) return hipSuccess;
-    if (p) hipFree(p);
-    p = nullptr;
-    cap = 0;
-    size_t want = bytes + bytes / 4 + 4096;
-    hipError_t e = hipMalloc(&p, want);
-    if (e == hipSuccess) cap = want;
-    return e;
-  }
-  void release() {
-    if (p && !view) hipFree(p);
-    p = nullptr;
-    cap = 0;
-    view = false;
-  }
-  void set_view(void* q, size_t bytes) {
-    if (p && !view) hipFree(p);
-    p = q;
-    cap = bytes;
-    view = true;
-  }
-  template <class T>
-  T* as() const { return reinterpret_cast<T*>(p); }
-};
-
-// Pipeline stages; (s1) / (s2) = the HIP stream a stage runs on.  s2 carries signature decode,
-// pubkey aggregation + blinding and the whole sum(r_i sig_i) branch; s1 groups the sets by
-// signing root, hashes each distinct root, sums r_i PK_i per root and runs one Miller loop per
-// root into the message product tree.  They join before the root check.  Only a failing root
-// runs the per-set fallback (per-set Miller loops + the job tree) and the bisection.
-enum {
-  ST_DECODE = 0,  // s2
-  ST_DEDUP,       // s1
-  ST_HASH_MAP,    // s1
-  ST_HASH_FIN,    // s1
-  ST_PK_CHUNKS,   // s2
-  ST_PK_BLIND,    // s2
-  ST_SIG_MSM,     // s2
-  ST_GSUM,        // s1
-  ST_MILLER,      // s1
-  ST_TREE_P,      // s1
-  ST_ML_S,        // s2
-  ST_ROOT,        // s1 (after joining s2)
-  ST_FALLBACK,    // s1: invalid-set search, range MSMs + part sums
-  ST_BISECT,      // s1: invalid-set search, node checks
-  ST_TOTAL,
-  kStages
-};
 const char* const kStageNames[kStages] = {"decode_sigs", "dedup",   "hash_map", "hash_finish", "pk_chunks",
                                           "pk_blind",    "sig_msm", "group_sum", "miller",    "tree_up_P",
                                           "ml_S",        "root_check", "search_msm", "search_check", "total"};
@@ -128,145 +66,6 @@ struct lb_batch {
     d_chunk_lo.release();
     d_route.release();
   }
-};
-
-#ifndef LB_SEARCH_CHUNK_DEF
-#define LB_SEARCH_CHUNK_DEF 8
-#endif
-struct lb_engine {
-  int device = 0;
-  // LB_ENGINE_LATENCY (lb_engine_create_ex): streams confined to the device's reserved CUs, the
-  // latency forms always (the partition keeps every other engine off those CUs)
-  bool latency = false;
-  int n_cus = 0;  // CUs its streams may use (the whole device, or one side of the partition)
-  hipStream_t stream = nullptr;   // s1
-  hipStream_t stream2 = nullptr;  // s2
-  hipStream_t stream3 = nullptr;  // s3: pubkey aggregation + blinding, beside the signature decode
-  hipEvent_t ev_g1 = nullptr, ev_s = nullptr, ev_fork = nullptr, ev_dec = nullptr, ev_pk = nullptr;
-  hipEvent_t ev_pkst = nullptr;  // the pubkey statuses (k_pk_blind mode 1), before the ladder
-  // small batches alone (round 6): the decoded signatures (s2) -> r_i sig_i on s3 beside the
-  // subgroup check (ev_sdec), and the terms ready for the sum on s2 (ev_sblind)
-  hipEvent_t ev_sdec = nullptr, ev_sblind = nullptr;
-  std::mutex mu;
-  // workspace
-  dbuf scalars, sig_aff, sig_inf, sig_status, q, h_aff, rpk, rsig, pk_status, ml, treeP, treeS, job_status,
-      nodes, verdict, parts, ok, chunk_acc, chunk_status, fS;
-  // message grouping (k_msg_*, k_gsum_*)
-  dbuf msg_tab, rep_of, uid_of, uniq_set, n_u, set_uid, gcnt, gpos, goff, gch, chunk_beg, chunk_end, members,
-      set_live, gacc, gp_aff, gp_inf, chunk_root;
-  // this pipeline run's forms: `alone` (device_alone at its start) picks the latency forms -- the
-  // row engine (row_fe: LB_ROW_FE=0 disables it) and the per-root sums' chunks combined by a
-  // segmented shuffle tree in one launch (k_gsum_wave, chunks of LB_GROUP_CHUNK_WAVE); under load
-  // k_gsum_chunks over LB_GROUP_CHUNK members, the chunk sums added serially per root
-  bool alone = false, row_fe = true;
-  int alone_force = -1;  // LB_ALONE=1 / 0 pins device_alone() (tests: the latency forms must run), -1 by load
-  uint32_t gchunk = LB_GROUP_CHUNK;
-  // bucket MSM for sum r_i sig_i (k_msm_*)
-  dbuf sig_aos, bcnt, bcursor, boff, bch, bchunk_beg, bchunk_end, bmembers, bacc, bsum, wsum;
-  // parked lone-lane state: k_hash_finish's points (4 x 72 words per launched lane), k_miller_lane's T
-  dbuf park;
-  // serial of the batch upload whose lb_batch_partial left its state (trees, statuses, scalars) in
-  // this engine's workspace, for lb_batch_search_after_partial; any other pipeline run clears it
-  uint64_t partial_serial = 0;
-  uint32_t partial_mu = 0;
-  // bucket sums and the bucket reduction by 8-lane groups (k_msm_buckets_g8, k_msm_window_g8,
-  // k_msm_horner_g8); LB_MSM_G8=0: the lone-lane kernels (k_msm_buckets, k_msm_reduce)
-  bool msm_g8 = true;
-  // invalid-set search (search_invalid): node descriptors and per-node results
-  dbuf sx[32];   // search round buffers (search_invalid: SX_*)
-  dbuf pk_aff;  // affine aggregate pubkey per set (single-set checks of the search)
-  dbuf y_root;  // FE value of the root check (the search starts from it)
-  uint64_t msg_key = 0;  // keyed probe hash (CSPRNG)
-  // batches with at most this many distinct roots run their Miller loops one wave per root
-  // (k_miller_wave); larger ones one lane per root (k_miller_lane) while other batches are in
-  // flight on the device, else 8 lanes per root (k_miller_g8).  LB_MILLER_WAVE_MAX;
-  // LB_MILLER_FORM = lane | g8 pins the large-batch form (default: by device load).
-  uint32_t miller_wave_max = 2048;
-  // ... and up to this many roots (tree nodes of a level) on the row engine (lb_row.h: one 16-wave
-  // workgroup per item, the products split over 16-lane rows; latency).  LB_ROW_MAX.
-  uint32_t row_max = 256;
-  int miller_form = 0;  // 0 by load, 1 lane, 2 g8
-  // one-lane Miller loops with f and a temporary in LDS (two waves per CU) up to this many roots,
-  // f alone in LDS (one wave per SIMD) above: LB_MILLER_LDS3_MAX (lb_kernels.h k_miller_lane)
-  uint32_t miller_lds3_max = 32768;
-  // ... and hash_to_G2's cofactor clearing with 8 lanes per root (k_hash_finish_g8).  LB_HASH_G8_MAX.
-  uint32_t hash_g8_max = 2048;
-  // ... and with a workgroup per root on the row engine while the device is alone.  LB_HASH_ROW_MAX.
-  uint32_t hash_row_max = 256;
-  bool hash_row_careful = false;  // LB_HASH_ROW_CAREFUL=1: the exceptional-case path always (tests)
-  // ... and the signature decode's square roots on rows up to this many sets.  LB_DEC_ROW_MAX.
-  uint32_t dec_row_max = 4096;
-  // ... and the signatures' subgroup check with 8 lanes per set (k_sig_subgroup_g8).  LB_SUBGROUP_G8_MAX.
-  uint32_t subgroup_g8_max = 4096;
-  // ... and S = sum r_i sig_i by per-set 8-lane scalar multiplications + trees instead of the
-  // bucket MSM (k_sig_blind_g8).  LB_SMALL_S_MAX.
-  uint32_t small_s_max = 32768;
-  uint32_t small_s_g8_max = 2048;  // ... with 8 lanes per set up to here, one lane above (LB_SMALL_S_G8_MAX)
-  // search rounds whose weighted sums cover at most this many positions skip the bucket MSM
-  // (k_smsm_terms_g8 + segmented sums).  LB_SEARCH_SMALL_MAX.
-  uint32_t search_small_max = 32768;
-  // one launch pair per search round (look-ahead tests not skipped for passing checks)
-  bool search_merge = true;
-  dbuf s_terms, s_part;
-  // per-root signature sums for the search's root-level instances (LB_SEARCH_ROOTSUM)
-  dbuf s_root, rs_idx, s_set;
-  bool search_rootsum = true;
-  // the small rounds' per-position terms: 0 by load (8 lanes per position while the device runs no
-  // other batch, one lane under load), 1 one lane, 2 eight lanes (LB_SMSM_FORM=lane / g8)
-  int smsm_form = 0;
-  // members per lane in the search rounds' bucket MSM chunks (k_msm_chunks).  Its buckets hold ~8
-  // members (109 instances x 1 024 buckets over ~0.9 M entries), so long chunks leave most lanes
-  // of a wave idle behind the longest one; LB_SEARCH_CHUNK
-  uint32_t search_chunk = LB_SEARCH_CHUNK_DEF;
-  // large batches: the first round checks the root tree's top subtrees directly, their S_j from
-  // one 4-window bucket MSM over all sets, without look-ahead tests and without the per-root sums
-  // (one GLV ladder per set); LB_SEARCH_BLOCKS=0 restores the per-root sums + look-ahead round
-  bool search_blk = true;
-  // distinct roots numbered in hash-table order (pseudo-random) rather than input order, so the
-  // search's first-round subtrees hold comparable numbers of sets (LB_ROOT_SHUFFLE=0: input order)
-  bool root_shuffle = true;
-  std::vector<uint64_t> h_scalars;
-  // resident pubkey table: one 128-byte record per key (g1a + flag, LB_TABLE_REC words)
-  dbuf table;
-  uint32_t table_n = 0, table_cap = 0;
-  // fixed-base comb entries of the table's first comb_n keys (k_comb_fill: LB_COMB_ENTRIES points
-  // of 96 B per key, 6.75 KiB), so that r PK of a single-key set is 18 mixed additions
-  // (k_pk_blind_comb) instead of the GLV ladder.  comb_max = keys the engine's budget allows:
-  // LB_PK_COMB_MB (MiB per engine, default 8192: a 2^20-key table in full), LB_PK_COMB=0 turns
-  // the comb off (every set takes the ladder, the A/B).  Keys past the budget take the ladder.
-  dbuf comb;
-  uint32_t comb_n = 0, comb_cap = 0, comb_max = 0;
-  uint64_t comb_sets = 0;  // sets k_pk_blind_comb was launched over, all batches (lb_pubkey_comb_sets)
-  // KZG trusted setup (lb_kzg_load_setup): [tau^i] G1 as g1a SoA (kzg_n entries), [tau^0,1] G2
-  dbuf kzg_g1, kzg_g2;
-  uint32_t kzg_n = 0;
-  // ... and the inverse transform's twiddles for the blob-level calls (lb_fr.h fr_intt_table(12):
-  // 2048 powers of the inverse root and 1 / 4096, Montgomery form), built on the host at load
-  dbuf kzg_tw;
-  // ... and, when the setup holds [tau^64] G2 (a third g2a in kzg_g2), the cell calls' table (lb_fr.h
-  // fr_cell_tables) with the 128 coset factors h_i^64 kept on the host (Montgomery form, by cell index)
-  dbuf kzg_cell_tab;
-  bool kzg_cells = false;
-  std::vector<fr> kzg_h64;
-  // FK20 (lb_kzg_compute_cells_and_proofs; lb_fk20.h): the twiddle table of fk_tables and the extended
-  // setup X_i[r] (8192 g1j SoA, entry 64 r + i, Jacobian so that O is z = 0), built on the first call
-  // under `mu` and dropped by lb_kzg_load_setup
-  dbuf kzg_fk_tw, kzg_fk_x;
-  bool kzg_fk_ready = false;
-  uint64_t kzg_batch_hash_ns = 0;  // host transcript hashing of the last batch verification (lb_kzg_batch_hash_ns)
-  // profiling
-  bool profiling = false;
-  hipEvent_t ev0[kStages] = {}, ev1[kStages] = {};
-  bool used[kStages] = {};
-  float last_ms[kStages] = {};
-  float acc_ms[kStages] = {};  // stages run once per search round: summed over the rounds
-  // pinned host word for the distinct-root count read back after grouping: the per-root kernels
-  // are launched over that count, not over the set count (their scratch is sized per dispatch)
-  uint32_t* h_nu = nullptr;
-  void* h_stage = nullptr;  // pinned staging of small batch uploads (batch_fill, under mu)
-  size_t h_stage_cap = 0;
-  // engine-owned input workspace reused by lb_verify_jobs* (no per-call device allocation)
-  lb_batch* scratch = nullptr;
 };
 
 // Engines per device are capped so that one process cannot create more concurrently active
@@ -348,17 +147,6 @@ static int max_engines_per_device() {
   return k > 0 ? k : 10;  // the highest engine count measured abort-free (profiles/r4_engines_ab.txt)
 }
 
-#define LB_HIP(call)                                                                        \
-  do {                                                                                      \
-    hipError_t _e = (call);                                                                 \
-    if (_e != hipSuccess) {                                                                 \
-      fprintf(stderr, "lodestar_bls: %s failed: %s (%s:%d)\n", #call, hipGetErrorString(_e), \
-              __FILE__, __LINE__);                                                          \
-      return LB_ERR_DEVICE;                                                                 \
-    }                                                                                       \
-  } while (0)
-
-static inline uint32_t nblk(uint32_t n) { return (n + LB_TPB - 1) / LB_TPB; }
 static inline uint32_t nblk_inv(uint32_t n) { return (n + LB_INV_TPB - 1) / LB_INV_TPB; }
 
 // unblinded: the verdict of this run covers exactly this batch (lb_batch_verify / lb_verify_jobs*),
@@ -601,10 +389,10 @@ void lb_engine_destroy(lb_engine* e) {
                   &e->rep_of, &e->uid_of, &e->uniq_set, &e->n_u, &e->set_uid, &e->gcnt, &e->gpos, &e->goff,
                   &e->gch, &e->chunk_beg, &e->chunk_end, &e->members, &e->set_live, &e->gacc, &e->gp_aff,
                   &e->gp_inf, &e->chunk_root, &e->sig_aos, &e->bcnt, &e->bcursor, &e->boff, &e->bch, &e->bchunk_beg,
-                  &e->bchunk_end, &e->bmembers, &e->bacc, &e->bsum, &e->wsum, &e->park, &e->pk_aff, &e->y_root, &e->kzg_g1,
-                  &e->kzg_g2, &e->kzg_tw, &e->kzg_cell_tab, &e->kzg_fk_tw, &e->kzg_fk_x, &e->s_terms, &e->s_part, &e->s_root,
-                  &e->rs_idx, &e->s_set};
+                  &e->bchunk_end, &e->bmembers, &e->bacc, &e->bsum, &e->wsum, &e->park, &e->pk_aff, &e->y_root,
+                  &e->s_terms, &e->s_part, &e->s_root, &e->rs_idx, &e->s_set};
   for (dbuf* b : bufs) b->release();
+  e->kzg.release();
   for (dbuf& b : e->sx) b.release();
   for (int i = 0; i < kStages; i++) {
     if (e->ev0[i]) hipEventDestroy(e->ev0[i]);
@@ -2261,45 +2049,6 @@ extern "C" int32_t lb_aggregate_signatures(lb_engine* e, uint32_t n_groups, cons
   return LB_OK;
 }
 
-// Generic "n items in, per-item outputs back" launcher for the small helper kernels.
-namespace {
-struct io_spec {
-  const void* src;
-  size_t bytes;
-  bool out;  // copy back after the launch
-  void* dst;
-};
-}  // namespace
-
-template <class Launch>
-static int32_t run_simple(lb_engine* e, std::vector<io_spec> io, Launch launch) {
-  std::lock_guard<std::mutex> lk(e->mu);
-  LB_HIP(hipSetDevice(e->device));
-  std::vector<dbuf> bufs(io.size());
-  hipError_t r = hipSuccess;
-  for (size_t k = 0; k < io.size() && r == hipSuccess; k++) {
-    r = bufs[k].ensure(io[k].bytes ? io[k].bytes : 16);
-    if (r == hipSuccess && !io[k].out && io[k].bytes)
-      r = hipMemcpyAsync(bufs[k].p, io[k].src, io[k].bytes, hipMemcpyHostToDevice, e->stream);
-  }
-  if (r == hipSuccess) {
-    std::vector<void*> ptrs;
-    for (auto& b : bufs) ptrs.push_back(b.p);
-    launch(ptrs);
-    r = hipGetLastError();
-  }
-  for (size_t k = 0; k < io.size() && r == hipSuccess; k++)
-    if (io[k].out && io[k].dst && io[k].bytes)
-      r = hipMemcpyAsync(io[k].dst, bufs[k].p, io[k].bytes, hipMemcpyDeviceToHost, e->stream);
-  if (r == hipSuccess) r = hipStreamSynchronize(e->stream);
-  for (auto& b : bufs) b.release();
-  if (r != hipSuccess) {
-    fprintf(stderr, "lodestar_bls: helper kernel failed: %s\n", hipGetErrorString(r));
-    return LB_ERR_DEVICE;
-  }
-  return LB_OK;
-}
-
 extern "C" int32_t lb_merkleize(lb_engine* e, uint32_t n_trees, const uint32_t* chunk_offsets, const uint8_t* chunks32,
                                 const uint32_t* depths, const uint64_t* mix_lengths, uint8_t* out_roots32) {
   if (!e || !chunk_offsets || (n_trees && (!depths || !mix_lengths || !out_roots32))) return LB_ERR_ARGUMENT;
@@ -2358,992 +2107,4 @@ extern "C" int32_t lb_sign(lb_engine* e, uint32_t n, const uint8_t* sks32, const
                       hipLaunchKernelGGL(k_sign, dim3(nblk(n)), dim3(LB_TPB), 0, e->stream, n,
                                          (const uint8_t*)p[0], (const uint8_t*)p[1], (uint8_t*)p[2]);
                     });
-}
-
-// ---------------------------------------------------------------- KZG (lb_kzg.h)
-extern "C" int32_t lb_kzg_load_setup(lb_engine* e, const uint8_t* g1_48, uint32_t n_g1, const uint8_t* g2_96,
-                                     uint32_t n_g2, int32_t* out_status) {
-  if (!e || !n_g1 || !g1_48 || !g2_96 || n_g2 < 2 || !out_status) return LB_ERR_ARGUMENT;
-  // [tau^0] G2, [tau^1] G2 and, where the setup reaches it, [tau^64] G2 (the cell calls), side by side
-  const uint32_t n2 = n_g2 >= 65 ? 3 : 2;
-  std::vector<uint8_t> g2in((size_t)n2 * 96);
-  memcpy(g2in.data(), g2_96, 2 * 96);
-  if (n2 == 3) memcpy(g2in.data() + 2 * 96, g2_96 + (size_t)64 * 96, 96);
-  std::vector<int32_t> st2(3, LB_OK);
-  int32_t r;
-  e->kzg_cells = false;
-  {
-    std::lock_guard<std::mutex> lk(e->mu);
-    LB_HIP(hipSetDevice(e->device));
-    e->kzg_fk_ready = false;  // the FK20 table belongs to the setup it was built from
-    e->kzg_fk_x.release();
-    LB_HIP(e->kzg_g1.ensure((size_t)n_g1 * sizeof(g1a)));
-    LB_HIP(e->kzg_g2.ensure(3 * sizeof(g2a)));
-  }
-  lb_engine* ee = e;
-  r = run_simple(e, {{g1_48, (size_t)n_g1 * 48, false, nullptr}, {nullptr, (size_t)n_g1 * 4, true, out_status},
-                     {g2in.data(), g2in.size(), false, nullptr}, {nullptr, (size_t)n2 * 4, true, st2.data()}},
-                 [&](std::vector<void*>& p) {
-                   hipLaunchKernelGGL(k_kzg_setup_g1, dim3(nblk(n_g1)), dim3(LB_TPB), 0, ee->stream, n_g1,
-                                      (const uint8_t*)p[0], ee->kzg_g1.as<uint32_t>(), n_g1, (int32_t*)p[1]);
-                   hipLaunchKernelGGL(k_kzg_setup_g2, dim3(1), dim3(64), 0, ee->stream, n2, (const uint8_t*)p[2],
-                                      ee->kzg_g2.as<uint32_t>(), (int32_t*)p[3]);
-                 });
-  if (r != LB_OK) return r;
-  if (st2[0] != LB_OK || st2[1] != LB_OK || st2[2] != LB_OK) {
-    e->kzg_n = 0;
-    return st2[0] != LB_OK ? st2[0] : (st2[1] != LB_OK ? st2[1] : st2[2]);
-  }
-  for (uint32_t i = 0; i < n_g1; i++)
-    if (out_status[i] != LB_OK) {
-      e->kzg_n = 0;
-      return out_status[i];
-    }
-  {
-    // the blob-level calls' inverse-transform table (lb_fr.h), computed here on the host
-    std::vector<fr> tw(LB_FR_TW_LEN);
-    fr_intt_table(tw.data(), LB_FR_LOGN);
-    std::lock_guard<std::mutex> lk(e->mu);
-    LB_HIP(hipSetDevice(e->device));
-    LB_HIP(e->kzg_tw.ensure(tw.size() * sizeof(fr)));
-    LB_HIP(hipMemcpyAsync(e->kzg_tw.p, tw.data(), tw.size() * sizeof(fr), hipMemcpyHostToDevice, e->stream));
-    // the cell calls' tables beside it: forward twiddles, w^j, w^-m, the 64-point inverse table
-    std::vector<fr> ct(LB_FR_CELL_TAB_LEN);
-    fr_cell_tables(ct.data());
-    e->kzg_h64.resize(LB_FR_CELLS);
-    for (uint32_t i = 0; i < LB_FR_CELLS; i++) e->kzg_h64[i] = ct[LB_FR_CELL_TAB_WINV + fr_cell_h64_index(i)];
-    LB_HIP(e->kzg_cell_tab.ensure(ct.size() * sizeof(fr)));
-    LB_HIP(hipMemcpyAsync(e->kzg_cell_tab.p, ct.data(), ct.size() * sizeof(fr), hipMemcpyHostToDevice, e->stream));
-    LB_HIP(hipStreamSynchronize(e->stream));
-    e->kzg_fk_ready = false;  // ... also one that a call built while this load was under way
-  }
-  e->kzg_n = n_g1;
-  e->kzg_cells = n2 == 3;
-  return LB_OK;
-}
-
-// The launches of out48 = compress(sum_i s_i P_i) over device buffers: P_i = setup point i
-// (d_pts48 null) or n compressed points; d_scalars n x 8 LE words; d_terms n and d_part
-// ceil(n / 64) g1j (SoA); d_status n codes (LB_OK for setup points).  n >= 1.
-static void g1_lincomb_launch(lb_engine* e, uint32_t n, const uint8_t* d_pts48, const uint32_t* d_scalars,
-                              uint32_t* d_terms, uint32_t* d_part, int32_t* d_status, uint8_t* d_out48) {
-  hipLaunchKernelGGL(k_g1_terms, dim3(nblk(n)), dim3(LB_TPB), 0, e->stream, n, d_pts48, e->kzg_g1.as<uint32_t>(),
-                     e->kzg_n, d_scalars, d_terms, d_status);
-  // reduce 64:1 per level, ping-ponging between the term buffer and the partials buffer
-  uint32_t* bufs[2] = {d_terms, d_part};
-  uint32_t m = n;
-  int cur = 0;
-  while (m > 1) {
-    const uint32_t mo = (m + 63) / 64;
-    hipLaunchKernelGGL(k_g1_sum64, dim3(mo), dim3(64), 0, e->stream, m, bufs[cur], mo, bufs[cur ^ 1]);
-    m = mo;
-    cur ^= 1;
-  }
-  hipLaunchKernelGGL(k_g1_out48, dim3(1), dim3(64), 0, e->stream, bufs[cur], m, d_out48);
-}
-
-extern "C" int32_t lb_g1_lincomb(lb_engine* e, uint32_t n, const uint8_t* points48, const uint8_t* scalars32,
-                                 uint8_t* out48) {
-  if (!e || !out48 || (n && !scalars32)) return LB_ERR_ARGUMENT;
-  if (!points48 && n > e->kzg_n) return LB_ERR_ARGUMENT;
-  if (!n) {  // empty sum: infinity
-    memset(out48, 0, 48);
-    out48[0] = 0xc0;
-    return LB_OK;
-  }
-  const uint32_t n1 = (n + 63) / 64;
-  std::vector<int32_t> st(n, LB_OK);
-  lb_engine* ee = e;
-  const int32_t r = run_simple(
-      e, {{points48, points48 ? (size_t)n * 48 : 0, false, nullptr}, {scalars32, (size_t)n * 32, false, nullptr},
-          {nullptr, (size_t)n * sizeof(g1j), true, nullptr}, {nullptr, (size_t)n1 * sizeof(g1j), true, nullptr},
-          {nullptr, (size_t)n * 4, true, st.data()}, {nullptr, 48, true, out48}},
-      [&](std::vector<void*>& p) {
-        g1_lincomb_launch(ee, n, points48 ? (const uint8_t*)p[0] : nullptr, (const uint32_t*)p[1], (uint32_t*)p[2],
-                          (uint32_t*)p[3], (int32_t*)p[4], (uint8_t*)p[5]);
-      });
-  if (r != LB_OK) return r;
-  for (uint32_t i = 0; i < n; i++)
-    if (st[i] != LB_OK) return st[i];
-  return LB_OK;
-}
-
-extern "C" int32_t lb_kzg_verify_proof(lb_engine* e, const uint8_t* commitment48, const uint8_t* z32,
-                                       const uint8_t* y32, const uint8_t* proof48, int32_t* ok) {
-  if (!e || !commitment48 || !z32 || !y32 || !proof48 || !ok) return LB_ERR_ARGUMENT;
-  if (e->kzg_n == 0) return LB_ERR_ARGUMENT;  // no setup loaded
-  uint8_t io[96];
-  memcpy(io, commitment48, 48);
-  memcpy(io + 48, proof48, 48);
-  uint8_t yz[64];
-  memcpy(yz, y32, 32);
-  memcpy(yz + 32, z32, 32);
-  lb_engine* ee = e;
-  return run_simple(e, {{io, 96, false, nullptr}, {yz, 64, false, nullptr}, {nullptr, 4, true, ok}},
-                    [&](std::vector<void*>& p) {
-                      hipLaunchKernelGGL(k_kzg_check, dim3(1), dim3(64), 0, ee->stream, (const uint8_t*)p[0],
-                                         (const uint32_t*)p[1], ee->kzg_g2.as<uint32_t>(), (int32_t*)p[2]);
-                    });
-}
-
-// ---------------------------------------------------------------- KZG, blob level (lb_kzg_field.h)
-namespace {
-// hash_to_bls_field(h || tag): SHA-256, read as a big-endian integer, mod r (Montgomery form)
-fr kzg_hash_to_field(const uint8_t h[32], uint8_t tag) {
-  sha_stream s;
-  s.update(h, 32);
-  s.update(&tag, 1);
-  uint8_t d[32];
-  s.finish(d);
-  uint32_t w[8];
-  for (int k = 0; k < 8; k++)
-    w[k] = ((uint32_t)d[28 - 4 * k] << 24) | ((uint32_t)d[29 - 4 * k] << 16) | ((uint32_t)d[30 - 4 * k] << 8) | d[31 - 4 * k];
-  return fr_reduce256(w);
-}
-
-// compute_challenges (lodestar_amd/kzg.py): transcript = domain || 4096 and n as 8-byte BE || the
-// blobs' field elements (32-byte BE: a valid blob's own bytes) || the commitments;
-// r = H(h || 0), x = H(h || 1)
-void kzg_challenges(uint32_t n, const uint8_t* blobs, const uint8_t* commitments48, fr& r, fr& x) {
-  sha_stream s;
-  s.update(reinterpret_cast<const uint8_t*>("FSBLOBVERIFY_V1_"), 16);
-  uint8_t be[16] = {0};
-  be[6] = (uint8_t)(LB_FR_N >> 8);
-  be[7] = (uint8_t)LB_FR_N;
-  for (int i = 0; i < 4; i++) be[12 + i] = (uint8_t)(n >> (24 - 8 * i));
-  s.update(be, 16);
-  if (n) s.update(blobs, (size_t)n * LB_FR_N * 32);
-  if (n) s.update(commitments48, (size_t)n * 48);
-  uint8_t h[32];
-  s.finish(h);
-  r = kzg_hash_to_field(h, 0);
-  x = kzg_hash_to_field(h, 1);
-}
-
-constexpr size_t kBlobBytes = (size_t)LB_FR_N * 32;
-constexpr uint32_t kMaxBlobs = 1024;  // per call (the spec's MAX_BLOBS_PER_BLOCK is 4)
-// the compressed G1 generator: the point whose scalar is y in the batched checks' k_g1_terms launch
-const uint8_t kG1Gen48[48] = {0x97, 0xf1, 0xd3, 0xa7, 0x31, 0x97, 0xd7, 0x94, 0x26, 0x95, 0x63, 0x8c,
-                              0x4f, 0xa9, 0xac, 0x0f, 0xc3, 0x68, 0x8c, 0x4f, 0x97, 0x74, 0xb9, 0x05,
-                              0xa1, 0x4e, 0x3a, 0x3f, 0x17, 0x1b, 0xac, 0x58, 0x6c, 0x55, 0xe8, 0x3f,
-                              0xf9, 0x7a, 0x1a, 0xef, 0xfb, 0x3a, 0xf0, 0x0a, 0xdb, 0x22, 0xc6, 0xbb};
-
-// device workspace of one blob-level call, freed when it returns.  Field elements: 8 words each.
-struct kzg_ws {
-  dbuf blobs;   // n blobs as given
-  dbuf polys;   // ... as Montgomery Fr (k_fr_blob_load)
-  dbuf status;  // per-blob status
-  dbuf agg;     // sum r^j poly_j
-  dbuf coef;    // monomial coefficients, Montgomery (k_fr_eval_quotient's input)
-  dbuf le;      // scalars for k_g1_terms: n polynomials' coefficients, or one quotient
-  dbuf terms, part, tstatus;  // g1_lincomb_launch
-  dbuf pts;     // n x 48: commitments out (blob_to_commitment) or in (verify)
-  dbuf pw, pw_le;  // r^j, Montgomery and plain LE
-  dbuf z;       // evaluation point, Montgomery
-  dbuf io, yz;  // k_kzg_check's inputs: C || proof, y || z as LE words
-  dbuf off, ok;  // the batched verification: sidecar offsets in, verdicts out
-  dbuf cidx, doff;           // the cell calls: cell indices; distinct-commitment offsets per group
-  dbuf tsc;                  // ... the table part's scalars (k_fr_cell_sum -> k_g1_cell_terms)
-  std::vector<int32_t> h_status;
-  ~kzg_ws() {
-    for (dbuf* b : {&blobs, &polys, &status, &agg, &coef, &le, &terms, &part, &tstatus, &pts, &pw, &pw_le, &z, &io, &yz,
-                    &off, &ok, &cidx, &doff, &tsc})
-      b->release();
-  }
-};
-
-#define LB_KZG_TRY(call)                                                                          \
-  do {                                                                                            \
-    hipError_t _e = (call);                                                                       \
-    if (_e != hipSuccess) {                                                                       \
-      fprintf(stderr, "lodestar_bls: %s failed: %s (%s:%d)\n", #call, hipGetErrorString(_e), __FILE__, __LINE__); \
-      return LB_ERR_DEVICE;                                                                       \
-    }                                                                                             \
-  } while (0)
-
-// upload n blobs and turn them into Montgomery Fr; h_status[b] = LB_OK / LB_BAD_SCALAR (synchronises).
-// Also sizes the buffers every call shares.  Caller holds e->mu.
-int32_t kzg_load_blobs(lb_engine* e, kzg_ws& w, uint32_t n, const uint8_t* blobs) {
-  LB_KZG_TRY(hipSetDevice(e->device));
-  LB_KZG_TRY(w.blobs.ensure(n * kBlobBytes));
-  LB_KZG_TRY(w.polys.ensure(n * kBlobBytes));
-  LB_KZG_TRY(w.status.ensure((size_t)n * 4));
-  LB_KZG_TRY(w.terms.ensure((size_t)LB_FR_N * sizeof(g1j)));
-  LB_KZG_TRY(w.part.ensure((size_t)(LB_FR_N / 64) * sizeof(g1j)));
-  LB_KZG_TRY(w.tstatus.ensure((size_t)LB_FR_N * 4));
-  LB_KZG_TRY(hipMemcpyAsync(w.blobs.p, blobs, n * kBlobBytes, hipMemcpyHostToDevice, e->stream));
-  LB_KZG_TRY(hipMemsetAsync(w.status.p, 0, (size_t)n * 4, e->stream));
-  const uint32_t n_elems = n * LB_FR_N;
-  hipLaunchKernelGGL(k_fr_blob_load, dim3((n_elems + 255) / 256), dim3(256), 0, e->stream, n_elems,
-                     w.blobs.as<uint8_t>(), w.polys.as<uint32_t>(), w.status.as<int32_t>());
-  LB_KZG_TRY(hipGetLastError());
-  w.h_status.assign(n, LB_OK);
-  LB_KZG_TRY(hipMemcpyAsync(w.h_status.data(), w.status.p, (size_t)n * 4, hipMemcpyDeviceToHost, e->stream));
-  LB_KZG_TRY(hipStreamSynchronize(e->stream));
-  return LB_OK;
-}
-
-// n_polys polynomials of evaluations -> coefficients (one workgroup each, the polynomial in LDS)
-int32_t kzg_intt(lb_engine* e, uint32_t n_polys, const uint32_t* in, uint32_t* out_mont, uint32_t* out_le) {
-  LB_KZG_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_fr_intt4096),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)LB_FR_INTT_LDS));
-  hipLaunchKernelGGL(k_fr_intt4096, dim3(n_polys), dim3(LB_FR_WG), LB_FR_INTT_LDS, e->stream, in,
-                     e->kzg_tw.as<uint32_t>(), out_mont, out_le);
-  LB_KZG_TRY(hipGetLastError());
-  return LB_OK;
-}
-
-// commitments of the n loaded blobs -> w.pts (device, 48 B each): coefficients as LE scalars, one
-// 4096-term linear combination of the setup per blob
-int32_t kzg_commit(lb_engine* e, kzg_ws& w, uint32_t n) {
-  LB_KZG_TRY(w.le.ensure(n * kBlobBytes));
-  LB_KZG_TRY(w.pts.ensure((size_t)n * 48));
-  const int32_t rc = kzg_intt(e, n, w.polys.as<uint32_t>(), nullptr, w.le.as<uint32_t>());
-  if (rc != LB_OK) return rc;
-  for (uint32_t b = 0; b < n; b++)
-    g1_lincomb_launch(e, LB_FR_N, nullptr, w.le.as<uint32_t>() + (size_t)b * LB_FR_N * 8, w.terms.as<uint32_t>(),
-                      w.part.as<uint32_t>(), w.tstatus.as<int32_t>(), w.pts.as<uint8_t>() + (size_t)48 * b);
-  LB_KZG_TRY(hipGetLastError());
-  return LB_OK;
-}
-
-// evaluations `evals` (Montgomery, device) and the point z -> y = p(z) as LE words at d_y and the
-// quotient's scalars in w.le; if d_proof48, also the proof = commitment to the quotient
-int32_t kzg_open(lb_engine* e, kzg_ws& w, const uint32_t* evals, const fr& z, uint32_t* d_y, uint8_t* d_proof48) {
-  LB_KZG_TRY(w.coef.ensure(kBlobBytes));
-  LB_KZG_TRY(w.le.ensure(kBlobBytes));
-  LB_KZG_TRY(w.z.ensure(sizeof(fr)));
-  LB_KZG_TRY(hipMemcpyAsync(w.z.p, &z, sizeof(fr), hipMemcpyHostToDevice, e->stream));
-  const int32_t rc = kzg_intt(e, 1, evals, w.coef.as<uint32_t>(), nullptr);
-  if (rc != LB_OK) return rc;
-  hipLaunchKernelGGL(k_fr_eval_quotient, dim3(1), dim3(LB_FR_WG), LB_FR_EQ_LDS, e->stream, w.coef.as<uint32_t>(),
-                     w.z.as<uint32_t>(), w.le.as<uint32_t>(), d_y);
-  LB_KZG_TRY(hipGetLastError());
-  if (d_proof48) {
-    g1_lincomb_launch(e, LB_FR_N, nullptr, w.le.as<uint32_t>(), w.terms.as<uint32_t>(), w.part.as<uint32_t>(),
-                      w.tstatus.as<int32_t>(), d_proof48);
-    LB_KZG_TRY(hipGetLastError());
-  }
-  return LB_OK;
-}
-
-// sum_j r^j poly_j of the n loaded blobs -> w.agg; the powers also as LE scalars in w.pw_le
-int32_t kzg_aggregate(lb_engine* e, kzg_ws& w, uint32_t n, const fr& r) {
-  std::vector<fr> pw(n), pw_le(n);
-  fr p = fr_one();
-  for (uint32_t j = 0; j < n; j++) {
-    pw[j] = p;
-    fr_to_le_words(pw_le[j].l, p);
-    p = fr_mul(p, r);
-  }
-  LB_KZG_TRY(w.pw.ensure(n * sizeof(fr)));
-  LB_KZG_TRY(w.pw_le.ensure(n * sizeof(fr)));
-  LB_KZG_TRY(w.agg.ensure(kBlobBytes));
-  LB_KZG_TRY(hipMemcpyAsync(w.pw.p, pw.data(), n * sizeof(fr), hipMemcpyHostToDevice, e->stream));
-  LB_KZG_TRY(hipMemcpyAsync(w.pw_le.p, pw_le.data(), n * sizeof(fr), hipMemcpyHostToDevice, e->stream));
-  hipLaunchKernelGGL(k_fr_aggregate, dim3(LB_FR_N / 256), dim3(256), 0, e->stream, n, w.polys.as<uint32_t>(),
-                     w.pw.as<uint32_t>(), w.agg.as<uint32_t>());
-  LB_KZG_TRY(hipGetLastError());
-  // pageable uploads return once staged, but pw / pw_le die with this frame: be safe
-  LB_KZG_TRY(hipStreamSynchronize(e->stream));
-  return LB_OK;
-}
-
-bool kzg_ready(const lb_engine* e) { return e && e->kzg_n == LB_FR_N && e->kzg_tw.p; }
-}  // namespace
-
-extern "C" int32_t lb_kzg_blob_to_commitment(lb_engine* e, uint32_t n_blobs, const uint8_t* blobs, uint8_t* out48,
-                                             int32_t* out_status) {
-  if (!kzg_ready(e) || n_blobs > kMaxBlobs || (n_blobs && (!blobs || !out48 || !out_status))) return LB_ERR_ARGUMENT;
-  if (!n_blobs) return LB_OK;
-  std::lock_guard<std::mutex> lk(e->mu);
-  kzg_ws w;
-  int32_t rc = kzg_load_blobs(e, w, n_blobs, blobs);
-  if (rc == LB_OK) rc = kzg_commit(e, w, n_blobs);
-  if (rc != LB_OK) return rc;
-  LB_KZG_TRY(hipMemcpyAsync(out48, w.pts.p, (size_t)n_blobs * 48, hipMemcpyDeviceToHost, e->stream));
-  LB_KZG_TRY(hipStreamSynchronize(e->stream));
-  for (uint32_t b = 0; b < n_blobs; b++) {
-    out_status[b] = w.h_status[b];
-    if (w.h_status[b] != LB_OK) memset(out48 + (size_t)48 * b, 0, 48);
-  }
-  return LB_OK;
-}
-
-extern "C" int32_t lb_kzg_blob_coefficients(lb_engine* e, const uint8_t* blob, uint8_t* out_coeffs32le) {
-  if (!kzg_ready(e) || !blob || !out_coeffs32le) return LB_ERR_ARGUMENT;
-  std::lock_guard<std::mutex> lk(e->mu);
-  kzg_ws w;
-  int32_t rc = kzg_load_blobs(e, w, 1, blob);
-  if (rc != LB_OK) return rc;
-  if (w.h_status[0] != LB_OK) return w.h_status[0];
-  LB_KZG_TRY(w.le.ensure(kBlobBytes));
-  rc = kzg_intt(e, 1, w.polys.as<uint32_t>(), nullptr, w.le.as<uint32_t>());
-  if (rc != LB_OK) return rc;
-  LB_KZG_TRY(hipMemcpyAsync(out_coeffs32le, w.le.p, kBlobBytes, hipMemcpyDeviceToHost, e->stream));
-  LB_KZG_TRY(hipStreamSynchronize(e->stream));
-  return LB_OK;
-}
-
-extern "C" int32_t lb_kzg_compute_proof(lb_engine* e, const uint8_t* blob, const uint8_t* z32le, uint8_t* out_proof48,
-                                        uint8_t* out_y32le) {
-  if (!kzg_ready(e) || !blob || !z32le || !out_proof48 || !out_y32le) return LB_ERR_ARGUMENT;
-  fr zp;
-  for (int k = 0; k < 8; k++)
-    zp.l[k] = (uint32_t)z32le[4 * k] | ((uint32_t)z32le[4 * k + 1] << 8) | ((uint32_t)z32le[4 * k + 2] << 16) |
-              ((uint32_t)z32le[4 * k + 3] << 24);
-  if (!fr_lt_mod(zp)) return LB_BAD_SCALAR;
-  std::lock_guard<std::mutex> lk(e->mu);
-  kzg_ws w;
-  int32_t rc = kzg_load_blobs(e, w, 1, blob);
-  if (rc != LB_OK) return rc;
-  if (w.h_status[0] != LB_OK) return w.h_status[0];
-  LB_KZG_TRY(w.yz.ensure(64));
-  LB_KZG_TRY(w.io.ensure(96));
-  const fr z = fr_to_mont(zp);  // outlives the upload: the stream is synchronised below
-  rc = kzg_open(e, w, w.polys.as<uint32_t>(), z, w.yz.as<uint32_t>(), w.io.as<uint8_t>());
-  if (rc != LB_OK) return rc;
-  LB_KZG_TRY(hipMemcpyAsync(out_proof48, w.io.p, 48, hipMemcpyDeviceToHost, e->stream));
-  LB_KZG_TRY(hipMemcpyAsync(out_y32le, w.yz.p, 32, hipMemcpyDeviceToHost, e->stream));
-  LB_KZG_TRY(hipStreamSynchronize(e->stream));
-  return LB_OK;
-}
-
-extern "C" int32_t lb_kzg_compute_aggregate_proof(lb_engine* e, uint32_t n_blobs, const uint8_t* blobs, uint8_t* out48) {
-  if (!kzg_ready(e) || n_blobs > kMaxBlobs || !out48 || (n_blobs && !blobs)) return LB_ERR_ARGUMENT;
-  if (!n_blobs) {  // the zero polynomial's proof: infinity
-    memset(out48, 0, 48);
-    out48[0] = 0xc0;
-    return LB_OK;
-  }
-  std::lock_guard<std::mutex> lk(e->mu);
-  kzg_ws w;
-  int32_t rc = kzg_load_blobs(e, w, n_blobs, blobs);
-  if (rc != LB_OK) return rc;
-  for (uint32_t b = 0; b < n_blobs; b++)
-    if (w.h_status[b] != LB_OK) return w.h_status[b];
-  rc = kzg_commit(e, w, n_blobs);
-  if (rc != LB_OK) return rc;
-  std::vector<uint8_t> comms((size_t)n_blobs * 48);
-  LB_KZG_TRY(hipMemcpyAsync(comms.data(), w.pts.p, comms.size(), hipMemcpyDeviceToHost, e->stream));
-  LB_KZG_TRY(hipStreamSynchronize(e->stream));
-  fr r, x;
-  kzg_challenges(n_blobs, blobs, comms.data(), r, x);
-  rc = kzg_aggregate(e, w, n_blobs, r);
-  if (rc != LB_OK) return rc;
-  LB_KZG_TRY(w.yz.ensure(64));
-  LB_KZG_TRY(w.io.ensure(96));
-  rc = kzg_open(e, w, w.agg.as<uint32_t>(), x, w.yz.as<uint32_t>(), w.io.as<uint8_t>());
-  if (rc != LB_OK) return rc;
-  LB_KZG_TRY(hipMemcpyAsync(out48, w.io.p, 48, hipMemcpyDeviceToHost, e->stream));
-  LB_KZG_TRY(hipStreamSynchronize(e->stream));
-  return LB_OK;
-}
-
-extern "C" int32_t lb_kzg_verify_aggregate_proof(lb_engine* e, uint32_t n_blobs, const uint8_t* blobs,
-                                                 const uint8_t* commitments48, const uint8_t* proof48, int32_t* ok) {
-  if (!kzg_ready(e) || n_blobs > kMaxBlobs || !proof48 || !ok || (n_blobs && (!blobs || !commitments48)))
-    return LB_ERR_ARGUMENT;
-  std::lock_guard<std::mutex> lk(e->mu);
-  kzg_ws w;
-  LB_KZG_TRY(hipSetDevice(e->device));
-  LB_KZG_TRY(w.yz.ensure(64));
-  LB_KZG_TRY(w.io.ensure(96));
-  LB_KZG_TRY(w.status.ensure(4));
-  fr r, x;
-  if (!n_blobs) {
-    // aggregated commitment = infinity, y = 0: e(proof, [tau - x] G2) == 1 iff the proof is infinity
-    kzg_challenges(0, nullptr, nullptr, r, x);
-    uint8_t inf48[48] = {0xc0};
-    LB_KZG_TRY(hipMemcpyAsync(w.io.p, inf48, 48, hipMemcpyHostToDevice, e->stream));
-    LB_KZG_TRY(hipMemsetAsync(w.yz.p, 0, 32, e->stream));
-  } else {
-    int32_t rc = kzg_load_blobs(e, w, n_blobs, blobs);
-    if (rc != LB_OK) return rc;
-    for (uint32_t b = 0; b < n_blobs; b++)
-      if (w.h_status[b] != LB_OK) return w.h_status[b];
-    kzg_challenges(n_blobs, blobs, commitments48, r, x);
-    rc = kzg_aggregate(e, w, n_blobs, r);
-    if (rc != LB_OK) return rc;
-    // y = agg(x) (the quotient the scan also yields is not needed here)
-    rc = kzg_open(e, w, w.agg.as<uint32_t>(), x, w.yz.as<uint32_t>(), nullptr);
-    if (rc != LB_OK) return rc;
-    // C = sum r^j C_j; the commitments are curve- and subgroup-checked by k_g1_terms
-    LB_KZG_TRY(w.pts.ensure((size_t)n_blobs * 48));
-    LB_KZG_TRY(hipMemcpyAsync(w.pts.p, commitments48, (size_t)n_blobs * 48, hipMemcpyHostToDevice, e->stream));
-    g1_lincomb_launch(e, n_blobs, w.pts.as<uint8_t>(), w.pw_le.as<uint32_t>(), w.terms.as<uint32_t>(),
-                      w.part.as<uint32_t>(), w.tstatus.as<int32_t>(), w.io.as<uint8_t>());
-    LB_KZG_TRY(hipGetLastError());
-    std::vector<int32_t> tst(n_blobs, LB_OK);
-    LB_KZG_TRY(hipMemcpyAsync(tst.data(), w.tstatus.p, (size_t)n_blobs * 4, hipMemcpyDeviceToHost, e->stream));
-    LB_KZG_TRY(hipStreamSynchronize(e->stream));
-    for (uint32_t b = 0; b < n_blobs; b++)
-      if (tst[b] != LB_OK) {
-        *ok = -tst[b];
-        return LB_OK;
-      }
-  }
-  uint32_t x_le[8];
-  fr_to_le_words(x_le, x);
-  LB_KZG_TRY(hipMemcpyAsync(w.io.as<uint8_t>() + 48, proof48, 48, hipMemcpyHostToDevice, e->stream));
-  LB_KZG_TRY(hipMemcpyAsync(w.yz.as<uint8_t>() + 32, x_le, 32, hipMemcpyHostToDevice, e->stream));
-  hipLaunchKernelGGL(k_kzg_check, dim3(1), dim3(64), 0, e->stream, w.io.as<uint8_t>(), w.yz.as<uint32_t>(),
-                     e->kzg_g2.as<uint32_t>(), w.status.as<int32_t>());
-  LB_KZG_TRY(hipGetLastError());
-  LB_KZG_TRY(hipMemcpyAsync(ok, w.status.p, 4, hipMemcpyDeviceToHost, e->stream));
-  LB_KZG_TRY(hipStreamSynchronize(e->stream));
-  return LB_OK;
-}
-
-// Many sidecars in one pass: every stage once over all of them, one synchronisation at the end.
-// Device arrays in k_g1_terms' order: the commitments, then the proofs, then one G1 generator per
-// sidecar; their scalars r_k^j, x_k from the host and y_k written by k_fr_eval_many.
-extern "C" int32_t lb_kzg_verify_aggregate_proof_batch(lb_engine* e, uint32_t n, const uint32_t* blob_offsets,
-                                                       const uint8_t* blobs, const uint8_t* commitments48,
-                                                       const uint8_t* proofs48, int32_t* out_ok) {
-  if (!kzg_ready(e) || n > 1024) return LB_ERR_ARGUMENT;
-  if (!n) return LB_OK;
-  if (!blob_offsets || !proofs48 || !out_ok || blob_offsets[0] != 0) return LB_ERR_ARGUMENT;
-  for (uint32_t k = 0; k < n; k++)
-    if (blob_offsets[k + 1] < blob_offsets[k]) return LB_ERR_ARGUMENT;
-  const uint32_t nb = blob_offsets[n];
-  if (nb > kMaxBlobs || (nb && (!blobs || !commitments48))) return LB_ERR_ARGUMENT;
-  const uint32_t n_pts = nb + 2 * n;
-  std::lock_guard<std::mutex> lk(e->mu);
-  kzg_ws w;
-  LB_KZG_TRY(hipSetDevice(e->device));
-  LB_KZG_TRY(w.blobs.ensure(std::max<size_t>(nb, 1) * kBlobBytes));
-  LB_KZG_TRY(w.polys.ensure(std::max<size_t>(nb, 1) * kBlobBytes));
-  LB_KZG_TRY(w.status.ensure(std::max<size_t>(nb, 1) * 4));
-  LB_KZG_TRY(w.pw.ensure(std::max<size_t>(nb, 1) * sizeof(fr)));
-  LB_KZG_TRY(w.z.ensure((size_t)n * sizeof(fr)));
-  LB_KZG_TRY(w.agg.ensure((size_t)n * kBlobBytes));
-  LB_KZG_TRY(w.coef.ensure((size_t)n * kBlobBytes));
-  LB_KZG_TRY(w.pts.ensure((size_t)n_pts * 48));
-  LB_KZG_TRY(w.le.ensure((size_t)n_pts * 32));
-  LB_KZG_TRY(w.terms.ensure((size_t)n_pts * sizeof(g1j)));
-  LB_KZG_TRY(w.tstatus.ensure((size_t)n_pts * 4));
-  LB_KZG_TRY(w.off.ensure((size_t)(n + 1) * 4));
-  LB_KZG_TRY(w.ok.ensure((size_t)n * 4));
-  // 1. the blobs go up and are decoded while the host hashes
-  LB_KZG_TRY(hipMemcpyAsync(w.off.p, blob_offsets, (size_t)(n + 1) * 4, hipMemcpyHostToDevice, e->stream));
-  if (nb) {
-    LB_KZG_TRY(hipMemcpyAsync(w.blobs.p, blobs, nb * kBlobBytes, hipMemcpyHostToDevice, e->stream));
-    LB_KZG_TRY(hipMemsetAsync(w.status.p, 0, (size_t)nb * 4, e->stream));
-    const uint32_t n_elems = nb * LB_FR_N;
-    hipLaunchKernelGGL(k_fr_blob_load, dim3((n_elems + 255) / 256), dim3(256), 0, e->stream, n_elems,
-                       w.blobs.as<uint8_t>(), w.polys.as<uint32_t>(), w.status.as<int32_t>());
-    LB_KZG_TRY(hipGetLastError());
-  }
-  // 2. challenges per sidecar; the host arrays live until the synchronisation below
-  std::vector<fr> pw(std::max<uint32_t>(nb, 1)), zs(n), sc(nb + n);
-  uint64_t hash_ns = 0;
-  for (uint32_t k = 0; k < n; k++) {
-    const uint32_t lo = blob_offsets[k], cnt = blob_offsets[k + 1] - lo;
-    fr r, x;
-    const auto h0 = std::chrono::steady_clock::now();
-    kzg_challenges(cnt, cnt ? blobs + lo * kBlobBytes : nullptr, cnt ? commitments48 + (size_t)48 * lo : nullptr, r, x);
-    hash_ns += (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - h0).count();
-    fr p = fr_one();
-    for (uint32_t j = 0; j < cnt; j++) {
-      pw[lo + j] = p;
-      fr_to_le_words(sc[lo + j].l, p);
-      p = fr_mul(p, r);
-    }
-    zs[k] = x;
-    fr_to_le_words(sc[nb + k].l, x);
-  }
-  e->kzg_batch_hash_ns = hash_ns;
-  std::vector<uint8_t> pts((size_t)n_pts * 48);
-  if (nb) memcpy(pts.data(), commitments48, (size_t)nb * 48);
-  memcpy(pts.data() + (size_t)nb * 48, proofs48, (size_t)n * 48);
-  for (uint32_t k = 0; k < n; k++) memcpy(pts.data() + (size_t)(nb + n + k) * 48, kG1Gen48, 48);
-  if (nb) LB_KZG_TRY(hipMemcpyAsync(w.pw.p, pw.data(), (size_t)nb * sizeof(fr), hipMemcpyHostToDevice, e->stream));
-  LB_KZG_TRY(hipMemcpyAsync(w.z.p, zs.data(), (size_t)n * sizeof(fr), hipMemcpyHostToDevice, e->stream));
-  LB_KZG_TRY(hipMemcpyAsync(w.le.p, sc.data(), (size_t)(nb + n) * sizeof(fr), hipMemcpyHostToDevice, e->stream));
-  LB_KZG_TRY(hipMemcpyAsync(w.pts.p, pts.data(), pts.size(), hipMemcpyHostToDevice, e->stream));
-  // 3. - 5. aggregates, their coefficients, their values y_k into the generators' scalar slots
-  hipLaunchKernelGGL(k_fr_aggregate_seg, dim3(n * (LB_FR_N / 256)), dim3(256), 0, e->stream, n, w.off.as<uint32_t>(), nb,
-                     w.polys.as<uint32_t>(), w.pw.as<uint32_t>(), w.agg.as<uint32_t>());
-  LB_KZG_TRY(hipGetLastError());
-  const int32_t rc = kzg_intt(e, n, w.agg.as<uint32_t>(), w.coef.as<uint32_t>(), nullptr);
-  if (rc != LB_OK) return rc;
-  hipLaunchKernelGGL(k_fr_eval_many, dim3(n), dim3(LB_FR_WG), LB_FR_EV_LDS, e->stream, w.coef.as<uint32_t>(),
-                     w.z.as<uint32_t>(), w.le.as<uint32_t>() + (size_t)8 * (nb + n));
-  LB_KZG_TRY(hipGetLastError());
-  // 6. every ladder and subgroup check of the segment in one launch
-  hipLaunchKernelGGL(k_g1_terms, dim3(nblk(n_pts)), dim3(LB_TPB), 0, e->stream, n_pts, w.pts.as<uint8_t>(),
-                     e->kzg_g1.as<uint32_t>(), e->kzg_n, w.le.as<uint32_t>(), w.terms.as<uint32_t>(),
-                     w.tstatus.as<int32_t>());
-  LB_KZG_TRY(hipGetLastError());
-  // 7. one wave per sidecar: status, T_k, the two-pair product
-  hipLaunchKernelGGL(k_kzg_check_many, dim3(n), dim3(64), 0, e->stream, n, w.off.as<uint32_t>(), nb,
-                     w.status.as<int32_t>(), w.pts.as<uint8_t>(), w.terms.as<uint32_t>(), w.tstatus.as<int32_t>(),
-                     e->kzg_g2.as<uint32_t>(), w.ok.as<int32_t>());
-  LB_KZG_TRY(hipGetLastError());
-  // 8. the verdicts
-  LB_KZG_TRY(hipMemcpyAsync(out_ok, w.ok.p, (size_t)n * 4, hipMemcpyDeviceToHost, e->stream));
-  LB_KZG_TRY(hipStreamSynchronize(e->stream));
-  return LB_OK;
-}
-
-// ---------------------------------------------------------------- KZG, one proof per blob (Deneb)
-namespace {
-// host threads that hash the per-blob challenges: LB_KZG_HASH_THREADS, default 8, 1 .. 16
-uint32_t kzg_hash_threads() {
-  const char* s = getenv("LB_KZG_HASH_THREADS");
-  const long v = s && *s ? strtol(s, nullptr, 10) : 8;
-  return (uint32_t)std::min<long>(16, std::max<long>(1, v));
-}
-uint64_t kzg_ns_since(const std::chrono::steady_clock::time_point& t0) {
-  return (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
-}
-}  // namespace
-
-// compute_blob_kzg_proof for n_blobs blobs: every stage once over all of them, the 4096-term
-// commitment to each quotient as in kzg_commit, one synchronisation at the end.
-extern "C" int32_t lb_kzg_compute_blob_proofs(lb_engine* e, uint32_t n_blobs, const uint8_t* blobs,
-                                              const uint8_t* commitments48, uint8_t* out_proofs48, int32_t* out_status) {
-  if (!kzg_ready(e) || n_blobs > kMaxBlobs) return LB_ERR_ARGUMENT;
-  if (!n_blobs) return LB_OK;
-  if (!blobs || !commitments48 || !out_proofs48 || !out_status) return LB_ERR_ARGUMENT;
-  const uint32_t n = n_blobs;
-  std::lock_guard<std::mutex> lk(e->mu);
-  kzg_ws w;
-  LB_KZG_TRY(hipSetDevice(e->device));
-  LB_KZG_TRY(w.blobs.ensure(n * kBlobBytes));
-  LB_KZG_TRY(w.polys.ensure(n * kBlobBytes));
-  LB_KZG_TRY(w.coef.ensure(n * kBlobBytes));
-  LB_KZG_TRY(w.le.ensure(n * kBlobBytes));
-  LB_KZG_TRY(w.status.ensure((size_t)n * 4));
-  LB_KZG_TRY(w.pts.ensure((size_t)n * 48));
-  LB_KZG_TRY(w.pw_le.ensure((size_t)n * sizeof(fr)));
-  LB_KZG_TRY(w.agg.ensure((size_t)n * sizeof(g1j)));  // the validation launch's terms (unused)
-  LB_KZG_TRY(w.ok.ensure((size_t)n * 4));             // ... and its statuses: the commitments'
-  LB_KZG_TRY(w.z.ensure((size_t)n * sizeof(fr)));
-  LB_KZG_TRY(w.yz.ensure((size_t)n * sizeof(fr)));
-  LB_KZG_TRY(w.io.ensure((size_t)n * 48));
-  LB_KZG_TRY(w.terms.ensure((size_t)LB_FR_N * sizeof(g1j)));
-  LB_KZG_TRY(w.part.ensure((size_t)(LB_FR_N / 64) * sizeof(g1j)));
-  LB_KZG_TRY(w.tstatus.ensure((size_t)LB_FR_N * 4));
-  // 1. the blobs go up and are decoded; 2. the commitments are decoded and subgroup-checked (unit
-  // scalars) while the host hashes the challenges
-  LB_KZG_TRY(hipMemcpyAsync(w.blobs.p, blobs, n * kBlobBytes, hipMemcpyHostToDevice, e->stream));
-  LB_KZG_TRY(hipMemsetAsync(w.status.p, 0, (size_t)n * 4, e->stream));
-  const uint32_t n_elems = n * LB_FR_N;
-  hipLaunchKernelGGL(k_fr_blob_load, dim3((n_elems + 255) / 256), dim3(256), 0, e->stream, n_elems, w.blobs.as<uint8_t>(),
-                     w.polys.as<uint32_t>(), w.status.as<int32_t>());
-  LB_KZG_TRY(hipGetLastError());
-  std::vector<fr> ones(n), zs(n);
-  for (uint32_t b = 0; b < n; b++) {
-    ones[b] = fr_zero();
-    ones[b].l[0] = 1;
-  }
-  LB_KZG_TRY(hipMemcpyAsync(w.pts.p, commitments48, (size_t)n * 48, hipMemcpyHostToDevice, e->stream));
-  LB_KZG_TRY(hipMemcpyAsync(w.pw_le.p, ones.data(), (size_t)n * sizeof(fr), hipMemcpyHostToDevice, e->stream));
-  hipLaunchKernelGGL(k_g1_terms, dim3(nblk(n)), dim3(LB_TPB), 0, e->stream, n, w.pts.as<uint8_t>(), e->kzg_g1.as<uint32_t>(),
-                     e->kzg_n, w.pw_le.as<uint32_t>(), w.agg.as<uint32_t>(), w.ok.as<int32_t>());
-  LB_KZG_TRY(hipGetLastError());
-  kzg_blob_challenges(n, blobs, commitments48, zs.data(), kzg_hash_threads());
-  LB_KZG_TRY(hipMemcpyAsync(w.z.p, zs.data(), (size_t)n * sizeof(fr), hipMemcpyHostToDevice, e->stream));
-  // 3. coefficients; 4. y_b and the quotients' scalars; 5. their commitments
-  const int32_t rc = kzg_intt(e, n, w.polys.as<uint32_t>(), w.coef.as<uint32_t>(), nullptr);
-  if (rc != LB_OK) return rc;
-  hipLaunchKernelGGL(k_fr_eval_quotient_many, dim3(n), dim3(LB_FR_WG), LB_FR_EQ_LDS, e->stream, w.coef.as<uint32_t>(),
-                     w.z.as<uint32_t>(), w.le.as<uint32_t>(), w.yz.as<uint32_t>());
-  LB_KZG_TRY(hipGetLastError());
-  for (uint32_t b = 0; b < n; b++)
-    g1_lincomb_launch(e, LB_FR_N, nullptr, w.le.as<uint32_t>() + (size_t)b * LB_FR_N * 8, w.terms.as<uint32_t>(),
-                      w.part.as<uint32_t>(), w.tstatus.as<int32_t>(), w.io.as<uint8_t>() + (size_t)48 * b);
-  LB_KZG_TRY(hipGetLastError());
-  // 6. proofs and statuses
-  std::vector<int32_t> bst(n, LB_OK), cst(n, LB_OK);
-  LB_KZG_TRY(hipMemcpyAsync(out_proofs48, w.io.p, (size_t)n * 48, hipMemcpyDeviceToHost, e->stream));
-  LB_KZG_TRY(hipMemcpyAsync(bst.data(), w.status.p, (size_t)n * 4, hipMemcpyDeviceToHost, e->stream));
-  LB_KZG_TRY(hipMemcpyAsync(cst.data(), w.ok.p, (size_t)n * 4, hipMemcpyDeviceToHost, e->stream));
-  LB_KZG_TRY(hipStreamSynchronize(e->stream));
-  for (uint32_t b = 0; b < n; b++) {
-    out_status[b] = cst[b] != LB_OK ? cst[b] : bst[b];
-    if (out_status[b] != LB_OK) memset(out_proofs48 + (size_t)48 * b, 0, 48);
-  }
-  return LB_OK;
-}
-
-// verify_blob_kzg_proof_batch for many groups in one pass: every stage once over all blobs, two
-// synchronisations (the combiner r_k hashes the y_i, which the device computes).  Device arrays in
-// k_kzg_check_groups' order: the commitments, the proofs twice, one G1 generator per group.
-extern "C" int32_t lb_kzg_verify_blob_proof_batch(lb_engine* e, uint32_t n_groups, const uint32_t* group_offsets,
-                                                  const uint8_t* blobs, const uint8_t* commitments48,
-                                                  const uint8_t* proofs48, int32_t* out_ok) {
-  const uint32_t n = n_groups;
-  if (!kzg_ready(e) || n > 1024) return LB_ERR_ARGUMENT;
-  if (!n) return LB_OK;
-  if (!group_offsets || !out_ok || group_offsets[0] != 0) return LB_ERR_ARGUMENT;
-  for (uint32_t k = 0; k < n; k++)
-    if (group_offsets[k + 1] < group_offsets[k]) return LB_ERR_ARGUMENT;
-  const uint32_t nb = group_offsets[n];
-  if (nb > kMaxBlobs || (nb && (!blobs || !commitments48 || !proofs48))) return LB_ERR_ARGUMENT;
-  const uint32_t n_pts = 3 * nb + n;
-  std::lock_guard<std::mutex> lk(e->mu);
-  kzg_ws w;
-  LB_KZG_TRY(hipSetDevice(e->device));
-  LB_KZG_TRY(w.blobs.ensure(std::max<size_t>(nb, 1) * kBlobBytes));
-  LB_KZG_TRY(w.polys.ensure(std::max<size_t>(nb, 1) * kBlobBytes));
-  LB_KZG_TRY(w.coef.ensure(std::max<size_t>(nb, 1) * kBlobBytes));
-  LB_KZG_TRY(w.status.ensure(std::max<size_t>(nb, 1) * 4));
-  LB_KZG_TRY(w.z.ensure(std::max<size_t>(nb, 1) * sizeof(fr)));
-  LB_KZG_TRY(w.yz.ensure(std::max<size_t>(nb, 1) * sizeof(fr)));
-  LB_KZG_TRY(w.pts.ensure((size_t)n_pts * 48));
-  LB_KZG_TRY(w.le.ensure((size_t)n_pts * 32));
-  LB_KZG_TRY(w.terms.ensure((size_t)n_pts * sizeof(g1j)));
-  LB_KZG_TRY(w.tstatus.ensure((size_t)n_pts * 4));
-  LB_KZG_TRY(w.off.ensure((size_t)(n + 1) * 4));
-  LB_KZG_TRY(w.ok.ensure((size_t)n * 4));
-  LB_KZG_TRY(hipMemcpyAsync(w.off.p, group_offsets, (size_t)(n + 1) * 4, hipMemcpyHostToDevice, e->stream));
-  // the host arrays live until the last synchronisation
-  std::vector<fr> zs(std::max<uint32_t>(nb, 1)), ys(std::max<uint32_t>(nb, 1)), y_le(std::max<uint32_t>(nb, 1)), sc(n_pts);
-  uint64_t hash_ns = 0;
-  if (nb) {
-    // 1. the blobs go up and are decoded while 2. the host threads hash the z_i
-    LB_KZG_TRY(hipMemcpyAsync(w.blobs.p, blobs, nb * kBlobBytes, hipMemcpyHostToDevice, e->stream));
-    LB_KZG_TRY(hipMemsetAsync(w.status.p, 0, (size_t)nb * 4, e->stream));
-    const uint32_t n_elems = nb * LB_FR_N;
-    hipLaunchKernelGGL(k_fr_blob_load, dim3((n_elems + 255) / 256), dim3(256), 0, e->stream, n_elems,
-                       w.blobs.as<uint8_t>(), w.polys.as<uint32_t>(), w.status.as<int32_t>());
-    LB_KZG_TRY(hipGetLastError());
-    const auto h0 = std::chrono::steady_clock::now();
-    kzg_blob_challenges(nb, blobs, commitments48, zs.data(), kzg_hash_threads());
-    hash_ns += kzg_ns_since(h0);
-    // 3. coefficients, y_i = p_i(z_i), back to the host: the first synchronisation
-    LB_KZG_TRY(hipMemcpyAsync(w.z.p, zs.data(), (size_t)nb * sizeof(fr), hipMemcpyHostToDevice, e->stream));
-    const int32_t rc = kzg_intt(e, nb, w.polys.as<uint32_t>(), w.coef.as<uint32_t>(), nullptr);
-    if (rc != LB_OK) return rc;
-    hipLaunchKernelGGL(k_fr_eval_many, dim3(nb), dim3(LB_FR_WG), LB_FR_EV_LDS, e->stream, w.coef.as<uint32_t>(),
-                       w.z.as<uint32_t>(), w.yz.as<uint32_t>());
-    LB_KZG_TRY(hipGetLastError());
-    LB_KZG_TRY(hipMemcpyAsync(y_le.data(), w.yz.p, (size_t)nb * sizeof(fr), hipMemcpyDeviceToHost, e->stream));
-    LB_KZG_TRY(hipStreamSynchronize(e->stream));
-    for (uint32_t j = 0; j < nb; j++) ys[j] = fr_to_mont(y_le[j]);
-  }
-  // 4. r_k per group and the scalars r^i, r^i z_i, sum r^i y_i
-  for (uint32_t k = 0; k < n; k++) {
-    const uint32_t lo = group_offsets[k], cnt = group_offsets[k + 1] - lo;
-    fr r = fr_one();
-    if (cnt > 1) {  // r^0 = 1 alone is used otherwise: verify_blob_kzg_proof
-      const auto h0 = std::chrono::steady_clock::now();
-      r = kzg_batch_r(cnt, commitments48 + (size_t)48 * lo, zs.data() + lo, ys.data() + lo, proofs48 + (size_t)48 * lo);
-      hash_ns += kzg_ns_since(h0);
-    }
-    fr p = fr_one(), ysum = fr_zero();
-    for (uint32_t i = 0; i < cnt; i++) {
-      const uint32_t j = lo + i;
-      fr_to_le_words(sc[j].l, p);
-      fr_to_le_words(sc[nb + j].l, fr_mul(p, zs[j]));
-      sc[2 * nb + j] = sc[j];
-      ysum = fr_add(ysum, fr_mul(p, ys[j]));
-      p = fr_mul(p, r);
-    }
-    fr_to_le_words(sc[3 * nb + k].l, ysum);
-  }
-  e->kzg_batch_hash_ns = hash_ns;
-  std::vector<uint8_t> pts((size_t)n_pts * 48);
-  if (nb) {
-    memcpy(pts.data(), commitments48, (size_t)nb * 48);
-    memcpy(pts.data() + (size_t)nb * 48, proofs48, (size_t)nb * 48);
-    memcpy(pts.data() + (size_t)2 * nb * 48, proofs48, (size_t)nb * 48);
-  }
-  for (uint32_t k = 0; k < n; k++) memcpy(pts.data() + (size_t)(3 * nb + k) * 48, kG1Gen48, 48);
-  LB_KZG_TRY(hipMemcpyAsync(w.le.p, sc.data(), (size_t)n_pts * sizeof(fr), hipMemcpyHostToDevice, e->stream));
-  LB_KZG_TRY(hipMemcpyAsync(w.pts.p, pts.data(), pts.size(), hipMemcpyHostToDevice, e->stream));
-  // 5. every ladder and subgroup check of the call in one launch
-  hipLaunchKernelGGL(k_g1_terms, dim3(nblk(n_pts)), dim3(LB_TPB), 0, e->stream, n_pts, w.pts.as<uint8_t>(),
-                     e->kzg_g1.as<uint32_t>(), e->kzg_n, w.le.as<uint32_t>(), w.terms.as<uint32_t>(),
-                     w.tstatus.as<int32_t>());
-  LB_KZG_TRY(hipGetLastError());
-  // 6. one wave per group: status, T_k and P_k, the two-pair product; the second synchronisation
-  hipLaunchKernelGGL(k_kzg_check_groups, dim3(n), dim3(64), 0, e->stream, n, w.off.as<uint32_t>(), nb,
-                     w.status.as<int32_t>(), w.terms.as<uint32_t>(), w.tstatus.as<int32_t>(), e->kzg_g2.as<uint32_t>(),
-                     w.ok.as<int32_t>());
-  LB_KZG_TRY(hipGetLastError());
-  LB_KZG_TRY(hipMemcpyAsync(out_ok, w.ok.p, (size_t)n * 4, hipMemcpyDeviceToHost, e->stream));
-  LB_KZG_TRY(hipStreamSynchronize(e->stream));
-  return LB_OK;
-}
-
-extern "C" uint64_t lb_kzg_batch_hash_ns(const lb_engine* e) { return e ? e->kzg_batch_hash_ns : 0; }
-
-// ---------------------------------------------------------------- KZG cells (EIP-7594, PeerDAS)
-// compute_cells for n_blobs blobs: decode, coefficients (k_fr_intt4096), then one workgroup per blob
-// writes its 128 cells (k_fr_coset_ntt4096).
-extern "C" int32_t lb_kzg_compute_cells(lb_engine* e, uint32_t n_blobs, const uint8_t* blobs, uint8_t* out_cells,
-                                        int32_t* out_status) {
-  if (!kzg_ready(e) || n_blobs > kMaxBlobs) return LB_ERR_ARGUMENT;
-  if (!n_blobs) return LB_OK;
-  if (!blobs || !out_cells || !out_status) return LB_ERR_ARGUMENT;
-  const uint32_t n = n_blobs;
-  std::lock_guard<std::mutex> lk(e->mu);
-  kzg_ws w;
-  int32_t rc = kzg_load_blobs(e, w, n, blobs);
-  if (rc != LB_OK) return rc;
-  LB_KZG_TRY(w.coef.ensure(n * kBlobBytes));
-  LB_KZG_TRY(w.le.ensure(n * LB_FR_EXT_BYTES));
-  rc = kzg_intt(e, n, w.polys.as<uint32_t>(), w.coef.as<uint32_t>(), nullptr);
-  if (rc != LB_OK) return rc;
-  LB_KZG_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_fr_coset_ntt4096),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)LB_FR_INTT_LDS));
-  hipLaunchKernelGGL(k_fr_coset_ntt4096, dim3(n), dim3(LB_FR_WG), LB_FR_INTT_LDS, e->stream, w.coef.as<uint32_t>(),
-                     w.blobs.as<uint8_t>(), e->kzg_cell_tab.as<uint32_t>(), w.le.as<uint8_t>());
-  LB_KZG_TRY(hipGetLastError());
-  LB_KZG_TRY(hipMemcpyAsync(out_cells, w.le.p, n * LB_FR_EXT_BYTES, hipMemcpyDeviceToHost, e->stream));
-  LB_KZG_TRY(hipStreamSynchronize(e->stream));
-  for (uint32_t b = 0; b < n; b++) {
-    out_status[b] = w.h_status[b];
-    if (out_status[b] != LB_OK) memset(out_cells + b * LB_FR_EXT_BYTES, 0, LB_FR_EXT_BYTES);
-  }
-  return LB_OK;
-}
-
-// The direct (non-FK20) proofs of chosen cells of one blob: the quotient by X^64 - h^64 per cell on
-// the device (k_fr_cell_quotient), then one 4096-term linear combination of the setup per cell.
-extern "C" int32_t lb_kzg_compute_cell_proofs(lb_engine* e, const uint8_t* blob, uint32_t n_cells, const uint32_t* cell_indices,
-                                              uint8_t* out_proofs48, int32_t* out_status) {
-  if (!kzg_ready(e) || !blob || !out_status || n_cells > LB_FR_CELLS) return LB_ERR_ARGUMENT;
-  if (n_cells && (!cell_indices || !out_proofs48)) return LB_ERR_ARGUMENT;
-  for (uint32_t c = 0; c < n_cells; c++)
-    if (cell_indices[c] >= LB_FR_CELLS) return LB_ERR_ARGUMENT;
-  std::lock_guard<std::mutex> lk(e->mu);
-  kzg_ws w;
-  int32_t rc = kzg_load_blobs(e, w, 1, blob);
-  if (rc != LB_OK) return rc;
-  *out_status = w.h_status[0];
-  if (!n_cells) return LB_OK;
-  if (*out_status != LB_OK) {
-    memset(out_proofs48, 0, (size_t)n_cells * 48);
-    return LB_OK;
-  }
-  LB_KZG_TRY(w.coef.ensure(kBlobBytes));
-  LB_KZG_TRY(w.le.ensure(n_cells * kBlobBytes));
-  LB_KZG_TRY(w.cidx.ensure((size_t)n_cells * 4));
-  LB_KZG_TRY(w.io.ensure((size_t)n_cells * 48));
-  LB_KZG_TRY(hipMemcpyAsync(w.cidx.p, cell_indices, (size_t)n_cells * 4, hipMemcpyHostToDevice, e->stream));
-  rc = kzg_intt(e, 1, w.polys.as<uint32_t>(), w.coef.as<uint32_t>(), nullptr);
-  if (rc != LB_OK) return rc;
-  hipLaunchKernelGGL(k_fr_cell_quotient, dim3(n_cells), dim3(64), 0, e->stream, n_cells, w.coef.as<uint32_t>(),
-                     w.cidx.as<uint32_t>(), e->kzg_cell_tab.as<uint32_t>(), w.le.as<uint32_t>());
-  LB_KZG_TRY(hipGetLastError());
-  for (uint32_t c = 0; c < n_cells; c++)
-    g1_lincomb_launch(e, LB_FR_N, nullptr, w.le.as<uint32_t>() + (size_t)c * LB_FR_N * 8, w.terms.as<uint32_t>(),
-                      w.part.as<uint32_t>(), w.tstatus.as<int32_t>(), w.io.as<uint8_t>() + (size_t)48 * c);
-  LB_KZG_TRY(hipGetLastError());
-  LB_KZG_TRY(hipMemcpyAsync(out_proofs48, w.io.p, (size_t)n_cells * 48, hipMemcpyDeviceToHost, e->stream));
-  LB_KZG_TRY(hipStreamSynchronize(e->stream));
-  return LB_OK;
-}
-
-// verify_cell_kzg_proof_batch for many groups in one pass with ONE synchronisation: the combiner
-// hashes only the caller's bytes, so every scalar of the given-point ladders is known on the host
-// before anything comes back, and the interpolation coefficients never leave the device.
-extern "C" int32_t lb_kzg_verify_cell_proof_batch(lb_engine* e, uint32_t n_groups, const uint32_t* cell_offsets,
-                                                  const uint8_t* commitments48, const uint32_t* cell_indices,
-                                                  const uint8_t* cells, const uint8_t* proofs48, int32_t* out_ok) {
-  const uint32_t n = n_groups;
-  if (!kzg_ready(e) || !e->kzg_cells || n > 1024) return LB_ERR_ARGUMENT;
-  if (!n) return LB_OK;
-  if (!cell_offsets || !out_ok || cell_offsets[0] != 0) return LB_ERR_ARGUMENT;
-  for (uint32_t g = 0; g < n; g++)
-    if (cell_offsets[g + 1] < cell_offsets[g]) return LB_ERR_ARGUMENT;
-  const uint32_t nc = cell_offsets[n];
-  if (nc > 16384 || (nc && (!commitments48 || !cell_indices || !cells || !proofs48))) return LB_ERR_ARGUMENT;
-  for (uint32_t k = 0; k < nc; k++)
-    if (cell_indices[k] >= LB_FR_CELLS) return LB_ERR_ARGUMENT;
-  std::lock_guard<std::mutex> lk(e->mu);
-  kzg_ws w;
-  const size_t nc1 = std::max<size_t>(nc, 1);
-  LB_KZG_TRY(hipSetDevice(e->device));
-  LB_KZG_TRY(w.blobs.ensure(nc1 * LB_FR_CELL_BYTES));
-  LB_KZG_TRY(w.polys.ensure(nc1 * LB_FR_CELL_BYTES));
-  LB_KZG_TRY(w.status.ensure(nc1 * 4));
-  LB_KZG_TRY(w.cidx.ensure(nc1 * 4));
-  LB_KZG_TRY(w.pw.ensure(nc1 * sizeof(fr)));
-  LB_KZG_TRY(w.off.ensure((size_t)(n + 1) * 4));
-  LB_KZG_TRY(w.doff.ensure((size_t)(n + 1) * 4));
-  LB_KZG_TRY(w.tsc.ensure((size_t)n * 64 * sizeof(fr)));
-  LB_KZG_TRY(w.ok.ensure((size_t)n * 4));
-  // 1. the cells go up and are decoded while 2. the host deduplicates and hashes
-  LB_KZG_TRY(hipMemcpyAsync(w.off.p, cell_offsets, (size_t)(n + 1) * 4, hipMemcpyHostToDevice, e->stream));
-  if (nc) {
-    LB_KZG_TRY(hipMemcpyAsync(w.blobs.p, cells, (size_t)nc * LB_FR_CELL_BYTES, hipMemcpyHostToDevice, e->stream));
-    LB_KZG_TRY(hipMemcpyAsync(w.cidx.p, cell_indices, (size_t)nc * 4, hipMemcpyHostToDevice, e->stream));
-    LB_KZG_TRY(hipMemsetAsync(w.status.p, 0, (size_t)nc * 4, e->stream));
-    const uint32_t n_elems = nc * LB_FR_CELL;
-    hipLaunchKernelGGL(k_fr_cell_load, dim3((n_elems + 255) / 256), dim3(256), 0, e->stream, n_elems, w.blobs.as<uint8_t>(),
-                       w.polys.as<uint32_t>(), w.status.as<int32_t>());
-    LB_KZG_TRY(hipGetLastError());
-  }
-  // the host arrays live until the synchronisation
-  std::vector<uint32_t> ci(nc1), first, doff(n + 1, 0);
-  std::vector<fr> rs(n), wt(nc1);
-  const auto h0 = std::chrono::steady_clock::now();
-  for (uint32_t g = 0; g < n; g++) {
-    const uint32_t lo = cell_offsets[g];
-    doff[g + 1] = doff[g] + kzg_cell_dedup(cell_offsets[g + 1] - lo, commitments48 + (size_t)48 * lo, ci.data() + lo, first);
-  }
-  kzg_cell_batch_rs(n, cell_offsets, doff.data(), commitments48, ci.data(), first.data(), cell_indices, cells, proofs48,
-                    rs.data(), kzg_hash_threads());
-  e->kzg_batch_hash_ns = kzg_ns_since(h0);
-  // 3. the scalars: r^i per proof, r^i h^64 per proof, the summed r^i per distinct commitment
-  const uint32_t nd = doff[n], n_pts = 2 * nc + nd;
-  const size_t np1 = std::max<size_t>(n_pts, 1);
-  std::vector<fr> sc(np1);
-  std::vector<uint8_t> pts(np1 * 48);
-  for (uint32_t g = 0; g < n; g++) {
-    const uint32_t lo = cell_offsets[g], cnt = cell_offsets[g + 1] - lo, dcnt = doff[g + 1] - doff[g];
-    std::vector<fr> wsum(dcnt, fr_zero());
-    fr p = fr_one();
-    for (uint32_t i = 0; i < cnt; i++) {
-      const uint32_t k = lo + i;
-      wt[k] = p;
-      fr_to_le_words(sc[k].l, p);
-      fr_to_le_words(sc[nc + k].l, fr_mul(p, e->kzg_h64[cell_indices[k]]));
-      wsum[ci[k]] = fr_add(wsum[ci[k]], p);
-      p = fr_mul(p, rs[g]);
-    }
-    for (uint32_t d = 0; d < dcnt; d++) {
-      fr_to_le_words(sc[2 * nc + doff[g] + d].l, wsum[d]);
-      memcpy(pts.data() + (size_t)(2 * nc + doff[g] + d) * 48, commitments48 + (size_t)48 * (lo + first[doff[g] + d]), 48);
-    }
-  }
-  if (nc) {
-    memcpy(pts.data(), proofs48, (size_t)nc * 48);
-    memcpy(pts.data() + (size_t)nc * 48, proofs48, (size_t)nc * 48);
-  }
-  LB_KZG_TRY(w.pts.ensure(np1 * 48));
-  LB_KZG_TRY(w.le.ensure(np1 * 32));
-  const uint32_t n_tab = n * LB_FR_CELL, n_terms = n_pts + n_tab;
-  LB_KZG_TRY(w.terms.ensure((size_t)n_terms * sizeof(g1j)));
-  LB_KZG_TRY(w.tstatus.ensure((size_t)n_terms * 4));
-  LB_KZG_TRY(hipMemcpyAsync(w.doff.p, doff.data(), (size_t)(n + 1) * 4, hipMemcpyHostToDevice, e->stream));
-  if (nc) {
-    LB_KZG_TRY(hipMemcpyAsync(w.pw.p, wt.data(), (size_t)nc * sizeof(fr), hipMemcpyHostToDevice, e->stream));
-    LB_KZG_TRY(hipMemcpyAsync(w.le.p, sc.data(), (size_t)n_pts * sizeof(fr), hipMemcpyHostToDevice, e->stream));
-    LB_KZG_TRY(hipMemcpyAsync(w.pts.p, pts.data(), (size_t)n_pts * 48, hipMemcpyHostToDevice, e->stream));
-    // 4. one wave per cell: r^i I_k, in place; then 5. the per-group sums, negated, as scalars
-    hipLaunchKernelGGL(k_fr_cell_interp, dim3(nc), dim3(64), 0, e->stream, nc, w.polys.as<uint32_t>(), w.cidx.as<uint32_t>(),
-                       w.pw.as<uint32_t>(), e->kzg_cell_tab.as<uint32_t>());
-    LB_KZG_TRY(hipGetLastError());
-  }
-  hipLaunchKernelGGL(k_fr_cell_sum, dim3(n), dim3(64), 0, e->stream, n, w.off.as<uint32_t>(), nc, w.polys.as<uint32_t>(),
-                     w.tsc.as<uint32_t>());
-  LB_KZG_TRY(hipGetLastError());
-  // 6. every ladder of the call in one launch: the given points and the 64 setup points per group
-  hipLaunchKernelGGL(k_g1_cell_terms, dim3(nblk(n_terms)), dim3(LB_TPB), 0, e->stream, n_pts, w.pts.as<uint8_t>(),
-                     w.le.as<uint32_t>(), n_tab, e->kzg_g1.as<uint32_t>(), e->kzg_n, (uint32_t)LB_FR_CELL, w.tsc.as<uint32_t>(),
-                     w.terms.as<uint32_t>(), w.tstatus.as<int32_t>());
-  LB_KZG_TRY(hipGetLastError());
-  // 7. one wave per group: status, LL and RL, the two-pair product; the synchronisation
-  hipLaunchKernelGGL(k_kzg_check_cells, dim3(n), dim3(64), 0, e->stream, n, w.off.as<uint32_t>(), nc, w.doff.as<uint32_t>(), nd,
-                     w.status.as<int32_t>(), w.terms.as<uint32_t>(), w.tstatus.as<int32_t>(), e->kzg_g2.as<uint32_t>(),
-                     w.ok.as<int32_t>());
-  LB_KZG_TRY(hipGetLastError());
-  LB_KZG_TRY(hipMemcpyAsync(out_ok, w.ok.p, (size_t)n * 4, hipMemcpyDeviceToHost, e->stream));
-  LB_KZG_TRY(hipStreamSynchronize(e->stream));
-  return LB_OK;
-}
-
-// ---------------------------------------------------------------- KZG cells and all their proofs (FK20; lb_fk20.h)
-namespace {
-constexpr uint32_t kMaxFkBlobs = 128;  // per call: 8192 ladders and 1.2 MB of terms per blob
-
-// n_tr transforms of 128 points between g1j SoA buffers (k_g1_fft128); tw_entry: LB_FK_TAB_FWD / _INV
-void kzg_fk_fft(lb_engine* e, uint32_t n_tr, const uint32_t* in, uint32_t in_cap, uint32_t in_st, uint32_t in_sj, uint32_t n_live,
-                uint32_t tw_entry, uint32_t* out, uint32_t out_cap, uint32_t out_st, uint32_t out_sm) {
-  hipLaunchKernelGGL(k_g1_fft128, dim3(n_tr), dim3(64), 0, e->stream, n_tr, in, in_cap, in_st, in_sj, n_live,
-                     e->kzg_fk_tw.as<uint32_t>() + (size_t)8 * tw_entry, (const uint32_t*)nullptr, out, out_cap, out_st, out_sm);
-}
-
-// The extended setup X_i[r] = DFT128(x_i)[r] at entry 64 r + i, once per loaded setup: the 64 strided,
-// padded columns of the setup (k_g1_fk_gather), one transform each.  Caller holds e->mu.
-int32_t kzg_fk_table(lb_engine* e) {
-  if (e->kzg_fk_ready) return LB_OK;
-  std::vector<fr> tab(LB_FK_TAB_LEN);
-  fk_tables(tab.data());
-  kzg_ws w;  // w.terms: the gathered columns, freed on every way out
-  LB_KZG_TRY(e->kzg_fk_tw.ensure(tab.size() * sizeof(fr)));
-  LB_KZG_TRY(e->kzg_fk_x.ensure((size_t)LB_FK_POINTS * sizeof(g1j)));
-  LB_KZG_TRY(w.terms.ensure((size_t)LB_FK_POINTS * sizeof(g1j)));
-  LB_KZG_TRY(hipMemcpyAsync(e->kzg_fk_tw.p, tab.data(), tab.size() * sizeof(fr), hipMemcpyHostToDevice, e->stream));
-  hipLaunchKernelGGL(k_g1_fk_gather, dim3(nblk(LB_FK_POINTS)), dim3(LB_TPB), 0, e->stream, e->kzg_g1.as<uint32_t>(), e->kzg_n,
-                     w.terms.as<uint32_t>());
-  kzg_fk_fft(e, LB_FK_COLS, w.terms.as<uint32_t>(), LB_FK_POINTS, LB_FK_N, 1, LB_FK_N, LB_FK_TAB_FWD, e->kzg_fk_x.as<uint32_t>(),
-             LB_FK_POINTS, 1, LB_FK_COLS);
-  LB_KZG_TRY(hipGetLastError());
-  LB_KZG_TRY(hipStreamSynchronize(e->stream));
-  e->kzg_fk_ready = true;
-  return LB_OK;
-}
-}  // namespace
-
-// compute_cells_and_kzg_proofs for n_blobs blobs with ONE synchronisation (after the table's first
-// build): a blob with an element >= r still runs, on the reduced element, and is zeroed afterwards.
-extern "C" int32_t lb_kzg_compute_cells_and_proofs(lb_engine* e, uint32_t n_blobs, const uint8_t* blobs, uint8_t* out_cells,
-                                                   uint8_t* out_proofs48, int32_t* out_status) {
-  if (!kzg_ready(e) || n_blobs > kMaxFkBlobs) return LB_ERR_ARGUMENT;
-  if (!n_blobs) return LB_OK;
-  if (!blobs || !out_cells || !out_proofs48 || !out_status) return LB_ERR_ARGUMENT;
-  const uint32_t n = n_blobs, np = n * LB_FK_N, nt = n * LB_FK_POINTS;
-  const size_t proof_bytes = (size_t)LB_FK_N * 48;
-  std::lock_guard<std::mutex> lk(e->mu);
-  kzg_ws w;
-  LB_KZG_TRY(hipSetDevice(e->device));
-  int32_t rc = kzg_fk_table(e);
-  if (rc != LB_OK) return rc;
-  LB_KZG_TRY(w.blobs.ensure(n * kBlobBytes));
-  LB_KZG_TRY(w.polys.ensure(n * kBlobBytes));
-  LB_KZG_TRY(w.status.ensure((size_t)n * 4));
-  LB_KZG_TRY(w.coef.ensure(n * kBlobBytes));
-  LB_KZG_TRY(w.le.ensure(n * LB_FR_EXT_BYTES));
-  LB_KZG_TRY(w.tsc.ensure((size_t)nt * sizeof(fr)));
-  LB_KZG_TRY(w.terms.ensure((size_t)nt * sizeof(g1j)));
-  LB_KZG_TRY(w.part.ensure((size_t)np * sizeof(g1j)));
-  LB_KZG_TRY(w.agg.ensure((size_t)np * sizeof(g1j)));
-  LB_KZG_TRY(w.io.ensure(n * proof_bytes));
-  // 1. decode, coefficients, and the cells by the path of lb_kzg_compute_cells
-  LB_KZG_TRY(hipMemcpyAsync(w.blobs.p, blobs, n * kBlobBytes, hipMemcpyHostToDevice, e->stream));
-  LB_KZG_TRY(hipMemsetAsync(w.status.p, 0, (size_t)n * 4, e->stream));
-  hipLaunchKernelGGL(k_fr_blob_load, dim3((n * LB_FR_N + 255) / 256), dim3(256), 0, e->stream, n * LB_FR_N, w.blobs.as<uint8_t>(),
-                     w.polys.as<uint32_t>(), w.status.as<int32_t>());
-  LB_KZG_TRY(hipGetLastError());
-  rc = kzg_intt(e, n, w.polys.as<uint32_t>(), w.coef.as<uint32_t>(), nullptr);
-  if (rc != LB_OK) return rc;
-  LB_KZG_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_fr_coset_ntt4096),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)LB_FR_INTT_LDS));
-  hipLaunchKernelGGL(k_fr_coset_ntt4096, dim3(n), dim3(LB_FR_WG), LB_FR_INTT_LDS, e->stream, w.coef.as<uint32_t>(),
-                     w.blobs.as<uint8_t>(), e->kzg_cell_tab.as<uint32_t>(), w.le.as<uint8_t>());
-  LB_KZG_TRY(hipGetLastError());
-  // 2. the 64 column transforms per blob -> the scalars C_i[r] / 128 in the table's order
-  hipLaunchKernelGGL(k_fr_fk_cols, dim3(n * LB_FK_COLS), dim3(64), 0, e->stream, n, w.coef.as<uint32_t>(), e->kzg_fk_tw.as<uint32_t>(),
-                     w.tsc.as<uint32_t>());
-  // 3. every ladder of the call in one launch, then E[r]: entry 128 b + r of w.part
-  hipLaunchKernelGGL(k_g1_jac_terms, dim3(nblk(nt)), dim3(LB_TPB), 0, e->stream, nt, e->kzg_fk_x.as<uint32_t>(), LB_FK_POINTS,
-                     w.tsc.as<uint32_t>(), w.terms.as<uint32_t>());
-  hipLaunchKernelGGL(k_g1_sum64, dim3(np), dim3(64), 0, e->stream, nt, w.terms.as<uint32_t>(), np, w.part.as<uint32_t>());
-  LB_KZG_TRY(hipGetLastError());
-  // 4. h = IDFT(E) (scaled already); the proofs = DFT(h[0 .. 63], O ...): h[64 .. 127] are dropped by the load
-  kzg_fk_fft(e, n, w.part.as<uint32_t>(), np, LB_FK_N, 1, LB_FK_N, LB_FK_TAB_INV, w.agg.as<uint32_t>(), np, LB_FK_N, 1);
-  kzg_fk_fft(e, n, w.agg.as<uint32_t>(), np, LB_FK_N, 1, LB_FK_LIVE, LB_FK_TAB_FWD, w.part.as<uint32_t>(), np, LB_FK_N, 1);
-  hipLaunchKernelGGL(k_g1_fk_out48, dim3(np / 64), dim3(64), 0, e->stream, np, w.part.as<uint32_t>(), w.io.as<uint8_t>());
-  LB_KZG_TRY(hipGetLastError());
-  w.h_status.assign(n, LB_OK);
-  LB_KZG_TRY(hipMemcpyAsync(out_cells, w.le.p, n * LB_FR_EXT_BYTES, hipMemcpyDeviceToHost, e->stream));
-  LB_KZG_TRY(hipMemcpyAsync(out_proofs48, w.io.p, n * proof_bytes, hipMemcpyDeviceToHost, e->stream));
-  LB_KZG_TRY(hipMemcpyAsync(w.h_status.data(), w.status.p, (size_t)n * 4, hipMemcpyDeviceToHost, e->stream));
-  LB_KZG_TRY(hipStreamSynchronize(e->stream));
-  for (uint32_t b = 0; b < n; b++) {
-    out_status[b] = w.h_status[b];
-    if (out_status[b] != LB_OK) {
-      memset(out_cells + b * LB_FR_EXT_BYTES, 0, LB_FR_EXT_BYTES);
-      memset(out_proofs48 + b * proof_bytes, 0, proof_bytes);
-    }
-  }
-  return LB_OK;
 }

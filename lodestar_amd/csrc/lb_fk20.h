@@ -1,6 +1,6 @@
 // FK20: all 128 cell proofs of a blob (EIP-7594 computeCellsAndKzgProofs) from ONE pass over the
 // setup instead of one 4096-term combination per cell.  LB_HD like lb_fr.h: the same source runs in
-// the gfx950 kernels (lb_kzg_fk20.h), in lb_engine.hip's host code (the twiddle table) and in the CPU
+// the gfx950 kernels (lb_kzg_fk20.h), in lb_kzg_host.hip's host code (the twiddle table) and in the CPU
 // harness (tests/harness/lb_kzg_fk20_harness.cpp).
 //
 // With a[0 .. 4095] the coefficients, s[t] = [tau^t] G1 and y_i = h_i^64 = w128^brp7(i), w128 = w^64:

@@ -1,7 +1,7 @@
 // The BLS12-381 scalar field Fr (r = 0x73eda753 299d7d48 3339d808 09a1d805 53bda402 fffe5bfe
 // ffffffff 00000001, the G1 subgroup order): the field of KZG blob elements, polynomial
 // coefficients and Fiat-Shamir challenges.  LB_HD like the rest of the arithmetic, so the same
-// source runs in the gfx950 kernels (lb_kzg_field.h), in lb_engine.hip's host code (twiddle
+// source runs in the gfx950 kernels (lb_kzg_field.h), in lb_kzg_host.hip's host code (twiddle
 // table, challenges) and in the CPU harness (tests/harness/lb_fr_harness.cpp).
 //
 // Representation: Montgomery form with R = 2^256, eight 32-bit limbs, little endian.  Products are

@@ -20,7 +20,7 @@
   }
 LB_CONST uint32_t LB_SHA_K[64] = LB_SHA_K_WORDS;
 // hipcc's host pass: a __constant__ array has no value on the host, so host callers of
-// sha256_compress (lb_engine.hip's KZG transcript hash) read a plain copy
+// sha256_compress (lb_kzg_host.hip's KZG transcript hash) read a plain copy
 #if defined(__HIPCC__) && !defined(__HIP_DEVICE_COMPILE__)
 static const uint32_t LB_SHA_K_HOST[64] = LB_SHA_K_WORDS;
 #define LB_SHA_K_AT(i) LB_SHA_K_HOST[i]

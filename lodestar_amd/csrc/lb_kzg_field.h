@@ -2,7 +2,7 @@
 // Montgomery Fr in device memory, are aggregated over the blobs (sum r^j poly_j), transformed to
 // monomial coefficients (inverse NTT), evaluated at a challenge and divided by (X - z), and leave
 // as the plain little-endian scalars k_g1_terms reads -- so between the blob's bytes and the
-// 48-byte commitment or proof nothing travels back to the host (lb_engine.hip lb_kzg_blob_*,
+// 48-byte commitment or proof nothing travels back to the host (lb_kzg_host.hip lb_kzg_blob_*,
 // lb_kzg_compute_*, lb_kzg_verify_aggregate_proof).  Field elements in device buffers are 8 words
 // each, array of structures.
 #pragma once

@@ -1,4 +1,4 @@
-// The Fiat-Shamir transcripts of the KZG calls, hashed on the host (host-only: lb_engine.hip's host
+// The Fiat-Shamir transcripts of the KZG calls, hashed on the host (host-only: lb_kzg_host.hip's host
 // pass and the CPU harness include it; no kernel does).  sha_stream is the streaming SHA-256 every
 // transcript goes through; kzg_blob_challenge and kzg_batch_r are the two transcripts of the
 // per-blob (Deneb) proof form, restated in lodestar_amd/kzg.py compute_challenge / compute_batch_r:
@@ -6,7 +6,7 @@
 //   r   = hash_to_bls_field(RC_DOMAIN || 4096 as 8 bytes BE || n as 8 bytes BE ||
 //                           for each i: C_i || z_i (32 BE) || y_i (32 BE) || proof_i)
 // with hash_to_bls_field = SHA-256 read as a big-endian integer mod r (no tag byte, unlike the
-// aggregate form's transcript in lb_engine.hip).
+// aggregate form's transcript in lb_kzg_host.hip).
 #pragma once
 #include <string.h>
 #include <algorithm>

@@ -5,18 +5,14 @@
 #pragma once
 #include <vector>
 #include "lb_fr.h"
-
-struct kzg_blob_flat {
-  const fr* p;
-  fr ld(uint32_t i) const { return p[i]; }
-};
+#include "fr_views.h"
 
 static inline void eval_quotient_many_lanes(uint32_t n_polys, uint32_t n, const fr* coef, const fr* z_all, uint32_t* q_le,
                                             uint32_t* y_le) {
   const uint32_t lanes = n / 4;
   std::vector<fr> buf0(lanes), buf1(lanes);
   for (uint32_t k = 0; k < n_polys; k++) {
-    const kzg_blob_flat A{coef + (size_t)k * n};
+    const fr_cview A{coef + (size_t)k * n};
     const fr z = z_all[k];
     fr* src = buf0.data();
     fr* dst = buf1.data();

@@ -5,20 +5,8 @@
 #pragma once
 #include <vector>
 #include "lb_fr.h"
+#include "fr_views.h"
 
-struct kzg_cells_flat {
-  fr* p;
-  fr ld(uint32_t i) const { return p[i]; }
-  void st(uint32_t i, const fr& v) { p[i] = v; }
-};
-struct kzg_cells_cflat {
-  const fr* p;
-  fr ld(uint32_t i) const { return p[i]; }
-};
-struct kzg_cells_table {
-  const fr* p;
-  fr operator()(uint32_t k) const { return p[k]; }
-};
 struct kzg_cells_of {
   const fr* p;
   fr operator()(uint32_t k, uint32_t j) const { return p[(size_t)k * LB_FR_CELL + j]; }
@@ -29,9 +17,9 @@ struct kzg_cells_of {
 static inline void coset_ntt4096_lanes(const fr* coef, const fr* tab, uint32_t* out_be) {
   const uint32_t lanes = 1024;
   std::vector<fr> lds(4096);
-  kzg_cells_flat A{lds.data()};
-  const kzg_cells_cflat C{coef};
-  const kzg_cells_table SC{tab + LB_FR_CELL_TAB_SCALE}, T{tab + LB_FR_CELL_TAB_FWD};
+  fr_view A{lds.data()};
+  const fr_cview C{coef};
+  const fr_table SC{tab + LB_FR_CELL_TAB_SCALE}, T{tab + LB_FR_CELL_TAB_FWD};
   for (uint32_t t = 0; t < lanes; t++) fr_coset_load(A, C, SC, t, lanes);
   for (int s = 0; s < 12; s++)
     for (uint32_t t = 0; t < lanes; t++) fr_ntt_stage(A, 12, s, T, t, lanes);
@@ -41,10 +29,10 @@ static inline void coset_ntt4096_lanes(const fr* coef, const fr* tab, uint32_t* 
 
 // k_fr_cell_interp over n_cells cells in place (one wave of 64 lanes each)
 static inline void cell_interp_lanes(uint32_t n_cells, fr* cells, const uint32_t* cell_index, const fr* weight, const fr* tab) {
-  const kzg_cells_table T{tab + LB_FR_CELL_TAB_ITW}, W{tab + LB_FR_CELL_TAB_WINV};
+  const fr_table T{tab + LB_FR_CELL_TAB_ITW}, W{tab + LB_FR_CELL_TAB_WINV};
   for (uint32_t c = 0; c < n_cells; c++) {
     fr lds[LB_FR_CELL];
-    kzg_cells_flat V{lds};
+    fr_view V{lds};
     for (uint32_t t = 0; t < LB_FR_CELL; t++) V.st(t, cells[(size_t)c * LB_FR_CELL + t]);
     for (int s = 0; s < LB_FR_CELL_LOG; s++)
       for (uint32_t t = 0; t < LB_FR_CELL; t++) fr_ntt_stage(V, LB_FR_CELL_LOG, s, T, t, LB_FR_CELL);
@@ -65,7 +53,7 @@ static inline void cell_sum_lanes(uint32_t n_groups, const uint32_t* off, uint32
 
 // k_fr_cell_quotient for one (blob, cell): 4096 plain LE scalars
 static inline void cell_quotient_lanes(const fr* coef, uint32_t cell_index, const fr* tab, uint32_t* q_le) {
-  const kzg_cells_table W{tab + LB_FR_CELL_TAB_WINV};
+  const fr_table W{tab + LB_FR_CELL_TAB_WINV};
   for (uint32_t l = 0; l < 64; l++)
-    fr_cell_quotient_lane(kzg_cells_cflat{coef}, 4096u, W(fr_cell_h64_index(cell_index & (LB_FR_CELLS - 1u))), l, q_le);
+    fr_cell_quotient_lane(fr_cview{coef}, 4096u, W(fr_cell_h64_index(cell_index & (LB_FR_CELLS - 1u))), l, q_le);
 }

@@ -6,6 +6,7 @@
 #pragma once
 #include <vector>
 #include "lb_fk20.h"
+#include "fr_views.h"
 
 struct fk_fr_slots {
   fr* p;
@@ -28,14 +29,6 @@ struct fk_g1_slots {
 struct fk_g1_mulw_cpu {
   const fr* tw;  // plain LE words
   g1j operator()(const g1j& v, uint32_t k) const { return jac_mul_u255_jac(v, tw[k].l); }
-};
-struct fk_fr_cpoly {
-  const fr* p;
-  fr ld(uint32_t i) const { return p[i]; }
-};
-struct fk_fr_table {
-  const fr* p;
-  fr operator()(uint32_t k) const { return p[k]; }
 };
 
 // the schedule of k_g1_fft128 over fr: inputs from n_live on are 0
@@ -64,11 +57,11 @@ static inline void fk_fft_g1_lanes(const g1j* in, uint32_t n_live, const fr* tab
 
 // k_fr_fk_cols for one blob: 8192 plain LE scalars, scalar 64 r + i = C_i[r] / 128
 static inline void fk_cols_lanes(const fr* coef, const fr* tab, uint32_t* out_le) {
-  const fk_fr_table T{tab + LB_FK_TAB_FWD_MONT};
+  const fr_table T{tab + LB_FK_TAB_FWD_MONT};
   for (uint32_t i = 0; i < LB_FK_COLS; i++) {
     fr lds[LB_FK_N];
     fk_fr_slots V{lds};
-    for (uint32_t t = 0; t < 64; t++) fk_col_load(V, fk_fr_cpoly{coef}, i, t);
+    for (uint32_t t = 0; t < 64; t++) fk_col_load(V, fr_cview{coef}, i, t);
     for (int s = 0; s < LB_FK_LOG; s++)
       for (uint32_t t = 0; t < 64; t++) fr_ntt_stage(V, LB_FK_LOG, s, T, t, 64u);
     for (uint32_t t = 0; t < 64; t++) fk_col_store(V, tab[LB_FK_TAB_SCALE_MONT], i, t, out_le);

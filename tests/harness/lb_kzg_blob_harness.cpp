@@ -1,20 +1,17 @@
 // CPU harness of the host and per-lane pieces of the per-blob (Deneb) KZG calls: the two transcripts
 // of lb_kzg_transcript.h (kzg_blob_challenge, kzg_batch_r, the threaded kzg_blob_challenges), the
 // phases of k_fr_eval_quotient_many (kzg_blob_lanes.h over lb_fr.h fr_eq_*) and the status fold of
-// k_kzg_check_groups (lb_fr.h kzg_group_status), compiled as plain C++ for
+// k_kzg_check_groups (lb_fr.h kzg_group_status), and the device-free helpers of the calls' host code
+// (lb_kzg_host.h: the offsets validator, the per-item status fold), compiled as plain C++ for
 // tests/test_kzg_blob_cpu.py.  Field elements cross the boundary as 32 bytes: big endian where the
 // transcript has them so, little endian plain form for the scan.  Test infrastructure only.
 #include <string.h>
 #include <vector>
 #include "kzg_blob_lanes.h"
+#include "lb_kzg_host.h"
 #include "lb_kzg_transcript.h"
 
-static fr rd_le(const uint8_t* b) {
-  fr p;
-  for (int w = 0; w < 8; w++)
-    p.l[w] = (uint32_t)b[4 * w] | ((uint32_t)b[4 * w + 1] << 8) | ((uint32_t)b[4 * w + 2] << 16) | ((uint32_t)b[4 * w + 3] << 24);
-  return fr_to_mont(p);
-}
+static fr rd_le(const uint8_t* b) { return fr_to_mont(kzg_fr_from_le32(b)); }
 static fr rd_be(const uint8_t* b) {
   fr v;
   fr_from_be32(v, b);
@@ -56,5 +53,10 @@ void c_fr_eval_quotient_many(uint32_t n_polys, uint32_t n, const uint8_t* coeffs
 }
 int32_t c_kzg_group_status(const int32_t* bstatus, const int32_t* tstatus, uint32_t n_blobs, uint32_t lo, uint32_t hi) {
   return kzg_group_status(bstatus, tstatus, n_blobs, lo, hi);
+}
+int32_t c_kzg_offsets_ok(uint32_t n, const uint32_t* off, uint32_t cap) { return kzg_offsets_ok(n, off, cap) ? 1 : 0; }
+void c_kzg_fold_status(uint32_t n, const int32_t* first, const int32_t* second, int32_t* out_status, uint8_t* out0,
+                       uint32_t stride0, uint8_t* out1, uint32_t stride1) {
+  kzg_fold_status(n, first, second, out_status, out0, stride0, out1, stride1);
 }
 }

@@ -1,7 +1,7 @@
 """The host and per-lane pieces of the per-blob (Deneb) KZG calls on the CPU
 (build/lb_kzg_blob_harness.so: lb_kzg_transcript.h's two transcripts, the phases of
-k_fr_eval_quotient_many and the status fold of k_kzg_check_groups, compiled for x86) against hashlib
-and Python integers; lodestar_amd.kzg's restatement of the transcripts against the independent one
+k_fr_eval_quotient_many, the status fold of k_kzg_check_groups and lb_kzg_host.h's offsets
+validator and per-item status fold, compiled for x86) against hashlib and Python integers; lodestar_amd.kzg's restatement of the transcripts against the independent one
 of tests/kzg_deneb_spec.py; one low-degree proof through the pure-Python pairing; and a stand-alone
 program of the harness cases under the address and undefined-behaviour sanitizers."""
 import ctypes
@@ -39,6 +39,9 @@ def L():
     lib.c_fr_eval_quotient_many.argtypes = [u, u, c, c, c, c]
     lib.c_kzg_group_status.argtypes = [I32, I32, u, u, u]
     lib.c_kzg_group_status.restype = ctypes.c_int32
+    lib.c_kzg_offsets_ok.argtypes = [u, ctypes.POINTER(u), u]
+    lib.c_kzg_offsets_ok.restype = ctypes.c_int32
+    lib.c_kzg_fold_status.argtypes = [u, I32, I32, I32, c, u, c, u]
     return lib
 
 
@@ -160,6 +163,41 @@ def test_status_fold(L):
     bst, tst = list(clean_b), list(clean_t)
     bst[0] = 5
     assert _fold(L, offsets, 1, bst, tst) == BAD_SCALAR
+
+
+def test_offsets_validator(L):
+    """the batched calls' offsets (lb_kzg_host.h kzg_offsets_ok): start at 0, never decrease, total
+    within the cap; empty groups anywhere; a null pointer is refused, not read"""
+    def ok(off, cap):
+        a = np.asarray(off, np.uint32)
+        return L.c_kzg_offsets_ok(len(off) - 1, a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), cap)
+
+    assert ok([0, 0, 1, 4], 4) == 1 and ok([0, 0, 1, 4], 1024) == 1
+    assert ok([0, 0], 0) == 1 and ok([0, 3, 3, 3], 3) == 1       # empty groups, an empty call's total
+    assert ok([0, 0, 1, 4], 3) == 0                              # total above the cap
+    assert ok([1, 1, 4], 1024) == 0                              # does not start at 0
+    assert ok([0, 2, 1, 4], 1024) == 0 and ok([0, 2, 4, 3], 1024) == 0   # decreases, in the middle and at the end
+    assert ok([0, 0xFFFFFFFF], 1024) == 0 and ok([0, 0xFFFFFFFF], 0xFFFFFFFF) == 1
+    assert L.c_kzg_offsets_ok(3, None, 1024) == 0
+
+
+def test_item_status_fold_and_zero_fill(L):
+    """the per-item fold of the compute calls (lb_kzg_host.h kzg_fold_status): the first list's code
+    wins over the second's, a rejected item's outputs are zeroed at each output's own stride, its
+    neighbours' bytes stay; one list and one output alone (null second list, null second output)"""
+    first = np.asarray([OK, NOT_IN_GROUP, OK, BAD_ENCODING], np.int32)
+    second = np.asarray([OK, BAD_SCALAR, BAD_SCALAR, OK], np.int32)
+    st = np.full(4, -1, np.int32)
+    a, b = ctypes.create_string_buffer(b"\xaa" * (4 * 48), 4 * 48), ctypes.create_string_buffer(b"\xbb" * (4 * 5), 4 * 5)
+    L.c_kzg_fold_status(4, first.ctypes.data_as(I32), second.ctypes.data_as(I32), st.ctypes.data_as(I32), a, 48, b, 5)
+    assert st.tolist() == [OK, NOT_IN_GROUP, BAD_SCALAR, BAD_ENCODING]
+    assert a.raw == b"\xaa" * 48 + bytes(3 * 48) and b.raw == b"\xbb" * 5 + bytes(3 * 5)
+    st = np.full(3, -1, np.int32)
+    a = ctypes.create_string_buffer(b"\xaa" * (3 * 48), 3 * 48)
+    one = np.asarray([OK, BAD_SCALAR, OK], np.int32)
+    L.c_kzg_fold_status(3, one.ctypes.data_as(I32), None, st.ctypes.data_as(I32), a, 48, None, 0)
+    assert st.tolist() == [OK, BAD_SCALAR, OK]
+    assert a.raw == b"\xaa" * 48 + bytes(48) + b"\xaa" * 48
 
 
 def test_low_degree_proof_through_the_python_pairing():

@@ -4,9 +4,10 @@
 The device code of every kernel used to compile in one translation unit (lb_engine.hip, ~9 min
 for gfx950).  The kernels are now assigned to groups (GROUPS below); lb_kgroup.hip is compiled
 once per group with -DLB_KGROUP=g and defines only that group's kernels (`#if LB_KG(g)` guards in
-the headers), and lb_engine.hip (-DLB_KGROUP=99) launches them through the declarations this
-script writes to lb_kdecl.h.  A host launch of a kernel defined in another translation unit goes
-through the kernel's handle symbol, which the defining unit registers: no -fgpu-rdc needed.
+the headers), and the host units (lb_engine.hip and lb_kzg_host.hip, -DLB_KGROUP=99) launch them
+through the declarations this script writes to lb_kdecl.h.  A host launch of a kernel defined
+in another translation unit goes through the kernel's handle symbol, which the defining unit
+registers: no -fgpu-rdc needed.
 
   python tools/gen_kdecls.py guard   # (one-time) wrap each kernel definition in its group guard
   python tools/gen_kdecls.py decl    # regenerate lb_kdecl.h (after a kernel signature changes)
@@ -55,7 +56,7 @@ GROUPS = {
 }
 N_GROUPS = len(GROUPS)
 GROUP_OF = {k: g for g, ks in GROUPS.items() for k in ks}
-# explicit instantiations of the template kernels that lb_engine.hip / lb_kzg.h launch
+# explicit instantiations of the template kernels that the host units launch
 INSTANCES = {
     "k_miller_lane": ["2", "3"],
     "k_msm_reduce": ["LB_MSM_W", "LB_SMSM_W"],
@@ -168,9 +169,9 @@ def render():
     if missing:
         sys.exit(f"GROUPS names kernels that do not exist: {missing}")
     txt = ["// GENERATED by tools/gen_kdecls.py decl -- do not edit.",
-           "// Declarations of every kernel for lb_engine.hip (compiled with LB_KGROUP=99: no kernel",
-           "// definitions) and the explicit instantiations of the template kernels for the group that",
-           "// defines them (lb_kgroup.hip with LB_KDECL_INSTANTIATE).",
+           "// Declarations of every kernel for the host units lb_engine.hip and lb_kzg_host.hip (compiled",
+           "// with LB_KGROUP=99: no kernel definitions) and the explicit instantiations of the template",
+           "// kernels for the group that defines them (lb_kgroup.hip with LB_KDECL_INSTANTIATE).",
            "#pragma once", ""]
     txt += decl
     txt += ["", "#ifdef LB_KDECL_INSTANTIATE"]
