@@ -49,6 +49,8 @@ def _jobs():
 
 
 HOST_UNITS = [("lb_engine.hip", "engine.o"), ("lb_kzg_host.hip", "kzg_host.o")]
+# every unit of the library compiles with these (tools/isa_compare.py compiles with them too)
+LIB_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result", "-Wno-unused-value"]
 
 
 def build_lib(force=False, verbose=True, extra_flags=(), out=None):
@@ -66,8 +68,7 @@ def build_lib(force=False, verbose=True, extra_flags=(), out=None):
             f.write(gen_kdecls.render())
     odir = os.path.join(ROOT, "build", "obj" + ("" if out == LIB else "_" + os.path.basename(out)))
     os.makedirs(odir, exist_ok=True)
-    base = [HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result",
-            "-Wno-unused-value", "-I" + INC, "-I" + CSRC, *extra_flags]
+    base = [HIPCC, *LIB_FLAGS, "-I" + INC, "-I" + CSRC, *extra_flags]
     units = [(os.path.join(CSRC, src), "99", os.path.join(odir, obj)) for src, obj in HOST_UNITS]
     units += [(os.path.join(CSRC, "lb_kgroup.hip"), str(g), os.path.join(odir, f"kgroup{g}.o"))
               for g in range(gen_kdecls.N_GROUPS)]

@@ -12,16 +12,6 @@
 #endif
 #define LB_KG(g) (LB_KGROUP < 0 || LB_KGROUP == (g))
 
-// k_hash_map_row: map_to_curve_g2_fold on row pairs (1) or map_to_curve_g2_i on single rows (0, A/B);
-// k_decompress_sigs_row: its square roots' exponentiations on row pairs (1) or single rows (0)
-#ifndef LB_H2C_FOLD
-#define LB_H2C_FOLD 1
-#endif
-// rfp2 products on the four rows of a wave (lb_row.h f_mul / f_sqr; k_hash_map_row one item per wave)
-#ifndef LBR_FP2_W4
-#define LBR_FP2_W4 1
-#endif
-
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
 #define LB_HD __host__ __device__ __forceinline__

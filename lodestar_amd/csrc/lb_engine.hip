@@ -80,9 +80,6 @@ static int g_engine_count[64];
 static std::atomic<uint64_t> g_batch_serial{0};
 // Batches currently inside the pipeline per device (all engines of the process).  With more than
 // one, the device is throughput-bound and the per-root kernels take their work-efficient forms.
-#ifndef LB_HASH_ALONE_G8
-#define LB_HASH_ALONE_G8 1  // cofactor clearing by 8-lane groups whenever the device is otherwise idle (0: by root count only)
-#endif
 static std::atomic<int> g_device_busy[64];
 // The two most recent pipeline exits per device by distinct engines (steady-clock ns): exit[0] the
 // latest, exit[1] the latest of any other engine than exit[0]'s, so an engine can ask when ANOTHER
@@ -975,7 +972,7 @@ static int32_t run_pipeline(lb_engine* e, lb_batch* b, const uint64_t* scalars, 
     {
       stage_scope sc(e, ST_DECODE, s2);
       if (row && n <= e->dec_row_max)
-        hipLaunchKernelGGL(k_decompress_sigs_row, dim3(LB_H2C_FOLD ? (n + 1) / 2 : (n + 3) / 4), dim3(64), 0, s2, n, b->d_sigs.as<uint8_t>(),
+        hipLaunchKernelGGL(k_decompress_sigs_row, dim3((n + 1) / 2), dim3(64), 0, s2, n, b->d_sigs.as<uint8_t>(),
                            b->has_sizes ? b->d_sig_sizes.as<uint32_t>() : nullptr, e->sig_aff.as<uint32_t>(),
                            e->sig_aos.as<uint4>(), e->sig_inf.as<uint32_t>(), e->sig_status.as<int32_t>());
       else
@@ -1089,7 +1086,7 @@ static int32_t run_pipeline(lb_engine* e, lb_batch* b, const uint64_t* scalars, 
     {
       stage_scope sc(e, ST_HASH_MAP, s1);
       if (row_hash)
-        hipLaunchKernelGGL(k_hash_map_row, dim3(LB_H2C_FOLD ? (LBR_FP2_W4 ? 2 * nuh : nuh) : (2 * nuh + 3) / 4), dim3(64), 0, s1, n, nuh,
+        hipLaunchKernelGGL(k_hash_map_row, dim3(2 * nuh), dim3(64), 0, s1, n, nuh,
                            e->uniq_set.as<uint32_t>(), b->d_msgs.as<uint8_t>(), e->q.as<uint32_t>());
       else
         hipLaunchKernelGGL(k_hash_map, dim3(nblk(2 * nuh)), dim3(LB_TPB), 0, s1, n, nuh, e->uniq_set.as<uint32_t>(),
@@ -1103,7 +1100,7 @@ static int32_t run_pipeline(lb_engine* e, lb_batch* b, const uint64_t* scalars, 
       if (row_hash)
         hipLaunchKernelGGL(k_hash_finish_row, dim3(nuh), dim3(LBR_NT), 0, s1, n, nu, e->q.as<uint32_t>(),
                            e->h_aff.as<uint32_t>(), e->hash_row_careful ? 1u : 0u);
-      else if (nuh <= e->hash_g8_max || (LB_HASH_ALONE_G8 && alone))
+      else if (nuh <= e->hash_g8_max || alone)  // by 8-lane groups for few roots, or whenever the device is otherwise idle
         hipLaunchKernelGGL(k_hash_finish_g8, dim3((nuh + 7) / 8), dim3(64), 0, s1, n, nu, e->q.as<uint32_t>(),
                            e->h_aff.as<uint32_t>());
       else
@@ -1258,13 +1255,8 @@ static uint32_t parts_per(uint32_t len, bool direct) {
   const uint32_t f = direct ? 64u : kWtParts;
   return (len + f - 1) / f;
 }
-#ifndef LB_SEARCH_SPEC
-#define LB_SEARCH_SPEC 1  // look-ahead tests over the parts of a fresh test's roots, device idle (0: off; A/B builds)
-#endif
-static constexpr uint32_t kSpecMaxSets = 16384;  // ... for nodes of at most this many sets
-#ifndef LB_SEARCH_BISECT
-#define LB_SEARCH_BISECT 0  // 1: the round-2 form (halve such a node), for A/B builds
-#endif
+// look-ahead tests over the parts of a fresh test's roots (device idle), for nodes of at most this many sets
+static constexpr uint32_t kSpecMaxSets = 16384;
 static void search_children(const search_ctx& x, const snode& a, bool direct, std::vector<snode>& out) {
   out.clear();
   if (a.kind == 2u || a.len <= 1) return;
@@ -1282,7 +1274,7 @@ static void search_children(const search_ctx& x, const snode& a, bool direct, st
   // direct children: subtrees of 64 roots (their weighted tests can name one failing root); a
   // node of <= 64 roots whose weighted test matched nothing (>= 2 failing roots) is checked root by
   // root in ONE round (halving it instead took up to six rounds for two wrong roots in a subtree)
-  int dd = direct ? (d >= L - 6 && !LB_SEARCH_BISECT ? L : std::max(d + 1, std::min(d + 7, L - 6))) : d + 6;
+  int dd = direct ? (d >= L - 6 ? L : std::max(d + 1, std::min(d + 7, L - 6))) : d + 6;
   if (dd > L) dd = L;
   const uint32_t k = (uint32_t)(dd - d), span = (uint32_t)(L - dd);
   for (uint32_t v = a.key << k; v < (a.key + 1) << k; v++) {
@@ -1635,7 +1627,7 @@ static int32_t search_invalid(lb_engine* e, lb_batch* b, uint32_t mu, int32_t* o
         break;
       }
     }
-    const bool spec_on = LB_SEARCH_SPEC && device_alone(e);
+    const bool spec_on = device_alone(e);
     for (size_t a = 0; a < work.size();) {
       // a launch set: whole failing nodes until the MSM instance budget is reached
       std::vector<fnode> Fs;

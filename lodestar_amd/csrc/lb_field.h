@@ -9,7 +9,6 @@
 #pragma once
 #include "lb_common.h"
 #include "lb_consts.h"
-#include "lb_fpmul_gfx950.h"
 
 struct fp {
   uint32_t v[12];
@@ -245,15 +244,7 @@ __device__ __forceinline__ fp fp_unpack(lb_v16u a) {
 }
 static __device__ __attribute__((noinline)) lb_v16u fp_mul_v(lb_v16u a, lb_v16u b) {
 #if defined(__HIP_DEVICE_COMPILE__)
-#if defined(LB_FPMUL_ASM32)
-  // 32-bit limbs, hand-scheduled MAD + carry chains (lb_fpmul_gfx950.h)
-  fp x = fp_unpack(a), y = fp_unpack(b);
-  uint32_t o[12], top;
-  lbm_mont_mul(o, &top, x.v, y.v);
-  return fp_pack(fp_reduce_once(o, top));
-#else
   return fp_pack(fp_mul28(fp_unpack(a), fp_unpack(b)));
-#endif
 #else
   return fp_pack(fp_mul_body(fp_unpack(a), fp_unpack(b)));
 #endif
@@ -351,9 +342,6 @@ LB_HD fp fp_sqr_inl(const fp& a) {
 // products: for inputs below 2^390 the output (ab + mp) / R' is below 2^388 + p, so every limb stays
 // below 2^28 and the column bounds of fp_mul28 / fp_sqr28 hold.  The end converts back with one
 // product by R mod p (r R / R' = r / 2^8 = x^e R), repacks and reduces once.
-#ifndef LB_POW28
-#define LB_POW28 1  // 0: the chains through fp_mul28 / fp_sqr28 (A/B builds)
-#endif
 struct fp28 {
   uint32_t l[14];
 };
@@ -432,42 +420,19 @@ LB_HD fp28 lb_tab8_28(const fp28* t, uint32_t k) {
     default: return t[7];
   }
 }
-#ifndef LB_POW28_WIN
-#define LB_POW28_WIN 4  // sliding-window width of the 28-bit-limb chains.  4: the 8 odd powers on the
-                        // stack (448 B per lane, ~170 VGPRs: three waves per SIMD in the signature
-                        // decode); 3: the 4 powers in registers, no stack, 222 VGPRs (two waves) and
-                        // ~10 % more decode instructions: 1.5 % lower throughput at 7 in flight
-                        // (profiles/r4_regress_ab.txt), for 268 -> 53 MB of decode traffic per batch
-#endif
-template <int NT>
-LB_HD fp28 lb_tab_sel28(const fp28* t, uint32_t k) {  // t[k] by selects (k is wave-uniform)
-  fp28 r = t[0];
-  LB_UNROLL for (int c = 1; c < NT; c++) {
-    const bool s = k == (uint32_t)c;
-    LB_UNROLL for (int w = 0; w < 14; w++) r.l[w] = s ? t[c].l[w] : r.l[w];
-  }
-  return r;
-}
+// Sliding window of 4 bits: the 8 odd powers on the stack (448 B per lane, ~170 VGPRs: three waves
+// per SIMD in the signature decode).  A 3-bit window keeps its 4 powers in registers, no stack, but
+// needs 222 VGPRs (two waves) and ~10 % more decode instructions: 1.5 % lower throughput at 7 in
+// flight (profiles/r4_regress_ab.txt), for 268 -> 53 MB of decode traffic per batch.
 LB_HD fp fp_pow_const_28(const fp& a, const uint32_t* e, int top_bit) {
-  constexpr int WIN = LB_POW28_WIN, NT = 1 << (WIN - 1);
-  fp28 tab[NT];
+  constexpr int WIN = 4;
+  fp28 tab[8];
   tab[0].l[0] = (a.v[0] << 8) & 0x0fffffffu;  // the limbs of a * 2^8: a's value in R'-form
   LB_UNROLL for (int k = 1; k < 14; k++) tab[0].l[k] = lb_bits28(a.v, 28 * k - 8);
   const fp28 a2 = fp28_sqr(tab[0]);
-  // odd powers one statement each: a loop here stays rolled (its body is too large for the
-  // unroller's budget) and then indexes the table dynamically, i.e. on the stack
-  if constexpr (NT == 8) {
-    // through a loop the unroller leaves rolled: the table indexed dynamically, on the stack
-    // (448 B per lane, cache-resident), at ~170 VGPRs
-    for (int k = 1; k < 8; k++) tab[k] = fp28_mul(tab[k - 1], a2);
-  } else {
-    tab[1] = fp28_mul(tab[0], a2);
-    if constexpr (NT >= 4) {
-      tab[2] = fp28_mul(tab[1], a2);
-      tab[3] = fp28_mul(tab[2], a2);
-    }
-  }
-  static_assert(NT == 2 || NT == 4 || NT == 8, "window of 2, 3 or 4 bits");
+  // the odd powers through a loop the unroller leaves rolled (its body is too large for the
+  // unroller's budget): the table indexed dynamically, on the stack (cache-resident)
+  for (int k = 1; k < 8; k++) tab[k] = fp28_mul(tab[k - 1], a2);
   auto bit = [&](int i) -> uint32_t { return (e[i >> 5] >> (i & 31)) & 1u; };
   fp28 r = tab[0];
   bool first = true;
@@ -483,11 +448,11 @@ LB_HD fp fp_pow_const_28(const fp& a, const uint32_t* e, int top_bit) {
     uint32_t val = 0;
     for (int k = i; k >= j; k--) val = (val << 1) | bit(k);
     if (first) {
-      r = NT == 8 ? lb_tab8_28(tab, val >> 1) : lb_tab_sel28<NT>(tab, val >> 1);
+      r = lb_tab8_28(tab, val >> 1);
       first = false;
     } else {
       for (int k = i; k >= j; k--) r = fp28_sqr(r);
-      r = fp28_mul(r, NT == 8 ? lb_tab8_28(tab, val >> 1) : lb_tab_sel28<NT>(tab, val >> 1));
+      r = fp28_mul(r, lb_tab8_28(tab, val >> 1));
     }
     i = j - 1;
   }
@@ -506,20 +471,18 @@ LB_HD fp fp_pow_const_28(const fp& a, const uint32_t* e, int top_bit) {
 
 template <bool kInlMul = false>
 LB_HD fp fp_pow_const_i(fp a, const uint32_t* e, int top_bit) {
-  if constexpr (kInlMul && LB_POW28) return fp_pow_const_28(a, e, top_bit);
-  auto mul = [](const fp& x, const fp& y) { return kInlMul ? fp_mul_inl(x, y) : fp_mul(x, y); };
-  auto sqr = [](const fp& x) { return kInlMul ? fp_sqr_inl(x) : fp_sqr(x); };
+  if constexpr (kInlMul) return fp_pow_const_28(a, e, top_bit);
   fp tab[8];
   tab[0] = a;
-  const fp a2 = sqr(a);
-  LB_UNROLL for (int k = 1; k < 8; k++) tab[k] = mul(tab[k - 1], a2);
+  const fp a2 = fp_sqr(a);
+  LB_UNROLL for (int k = 1; k < 8; k++) tab[k] = fp_mul(tab[k - 1], a2);
   auto bit = [&](int i) -> uint32_t { return (e[i >> 5] >> (i & 31)) & 1u; };
   fp r = fp_zero();
   bool first = true;
   int i = top_bit;
   while (i >= 0) {
     if (!bit(i)) {
-      r = sqr(r);
+      r = fp_sqr(r);
       i--;
       continue;
     }
@@ -531,17 +494,17 @@ LB_HD fp fp_pow_const_i(fp a, const uint32_t* e, int top_bit) {
       r = lb_tab8(tab, val >> 1);
       first = false;
     } else {
-      for (int k = i; k >= j; k--) r = sqr(r);
-      r = mul(r, lb_tab8(tab, val >> 1));
+      for (int k = i; k >= j; k--) r = fp_sqr(r);
+      r = fp_mul(r, lb_tab8(tab, val >> 1));
     }
     i = j - 1;
   }
   return r;
 }
 
-// ---- variable-time inversion (binary extended Euclid).  Every value this engine inverts is
-// derived from public data (signatures, pubkeys, messages), so timing does not leak secrets;
-// this replaces a 570-multiplication Fermat chain by ~400 cheap shift/subtract steps.
+// ---- word-array helpers of the variable-time algorithms below (the safegcd inversion, the binary
+// Jacobi symbol).  Every value this engine inverts or tests is derived from public data
+// (signatures, pubkeys, messages), so timing does not leak secrets.
 LB_HD bool lb_is_one_plain(const uint32_t* x) {
   uint32_t t = x[0] ^ 1u;
   LB_UNROLL for (int i = 1; i < 12; i++) t |= x[i];
@@ -553,20 +516,6 @@ LB_HD int lb_ctz32(uint32_t x) {
 #else
   return __builtin_ctz(x);
 #endif
-}
-// x <- x / 2^k mod p for 1 <= k <= 31 (Montgomery-style: add m*p so the low k bits vanish)
-LB_HD void lb_div2k_mod(uint32_t* x, int k) {
-  const uint32_t Pl[12] = {LB_P0, LB_P1, LB_P2, LB_P3, LB_P4, LB_P5, LB_P6, LB_P7, LB_P8, LB_P9, LB_P10, LB_P11};
-  uint32_t m = (x[0] * LB_PINV) & ((1u << k) - 1u);
-  uint32_t t[13];
-  uint64_t c = 0;
-  LB_UNROLL for (int j = 0; j < 12; j++) {
-    c = (uint64_t)m * Pl[j] + x[j] + (c >> 32);
-    t[j] = (uint32_t)c;
-  }
-  t[12] = (uint32_t)(c >> 32);
-  // (x + m p) < 2^k p, divisible by 2^k, result < p
-  LB_UNROLL for (int j = 0; j < 12; j++) x[j] = (t[j] >> k) | (t[j + 1] << (32 - k));
 }
 // u <- u / 2^k (plain shift), 1 <= k <= 31
 LB_HD void lb_shr(uint32_t* u, int k) {
@@ -581,55 +530,6 @@ LB_HD bool lb_geq(const uint32_t* a, const uint32_t* b) {
 LB_HD void lb_sub_in(uint32_t* a, const uint32_t* b) {
   uint32_t br = 0;
   LB_UNROLL for (int j = 0; j < 12; j++) a[j] = LB_SUBC(a[j], b[j], br, &br);
-}
-// plain a in [0, p) -> a^-1 mod p (plain), 0 -> 0.  fp_inv_plain_vt_i is the inline body (a
-// kernel whose call graph is all inline keeps its own register budget), fp_inv_plain_vt the
-// out-of-line entry.
-LB_HD fp fp_inv_plain_vt_i(fp a) {
-  if (fp_is_zero(a)) return a;
-  uint32_t u[12], v[12];
-  fp x1 = fp_zero(), x2 = fp_zero();
-  x1.v[0] = 1;
-  const uint32_t Pl[12] = {LB_P0, LB_P1, LB_P2, LB_P3, LB_P4, LB_P5, LB_P6, LB_P7, LB_P8, LB_P9, LB_P10, LB_P11};
-  LB_UNROLL for (int j = 0; j < 12; j++) {
-    u[j] = a.v[j];
-    v[j] = Pl[j];
-  }
-  // invariant: x1 * a == u, x2 * a == v (mod p); u, v > 0, v odd at loop head
-  while (true) {
-    while (u[0] == 0) {  // rare: shift whole words
-      LB_UNROLL for (int j = 0; j < 11; j++) u[j] = u[j + 1];
-      u[11] = 0;
-      lb_div2k_mod(x1.v, 16);
-      lb_div2k_mod(x1.v, 16);
-    }
-    int k = lb_ctz32(u[0]);
-    if (k) {
-      lb_shr(u, k);
-      lb_div2k_mod(x1.v, k);
-    }
-    if (lb_is_one_plain(u)) return x1;
-    if (lb_geq(u, v)) {
-      lb_sub_in(u, v);
-      x1 = fp_sub(x1, x2);
-    } else {
-      lb_sub_in(v, u);
-      x2 = fp_sub(x2, x1);
-      // v - u is even (both odd): normalise v here
-      while (v[0] == 0) {
-        LB_UNROLL for (int j = 0; j < 11; j++) v[j] = v[j + 1];
-        v[11] = 0;
-        lb_div2k_mod(x2.v, 16);
-        lb_div2k_mod(x2.v, 16);
-      }
-      int kv = lb_ctz32(v[0]);
-      if (kv) {
-        lb_shr(v, kv);
-        lb_div2k_mod(x2.v, kv);
-      }
-      if (lb_is_one_plain(v)) return x2;
-    }
-  }
 }
 // ---- Bernstein-Yang "safegcd" inversion, variable time (jumps of 62 divsteps on the low 64 bits,
 // then 2x2 transition matrices applied to the full-width values; the divstep loop and the
@@ -854,19 +754,15 @@ LB_HD fp fp_inv_plain_by_i(const fp& a) {
   }
   return r;
 }
-#ifndef LB_INV_EEA
-#define LB_INV_EEA 0  // 1: the binary extended Euclid above (A/B)
-#endif
-LB_NI fp fp_inv_plain_vt(fp a) { return LB_INV_EEA ? fp_inv_plain_vt_i(a) : fp_inv_plain_by_i(a); }
+// plain a in [0, p) -> a^-1 mod p (plain), 0 -> 0: the out-of-line entry (fp_inv_plain_by_i is the
+// inline body: a kernel whose call graph is all inline keeps its own register budget)
+LB_NI fp fp_inv_plain_vt(fp a) { return fp_inv_plain_by_i(a); }
 // Montgomery a R -> a^-1 R:  plain inverse of (a R) is a^-1 R^-1; times R^3 / R gives a^-1 R
 LB_HD fp fp_inv(const fp& a) { return fp_mul(fp_inv_plain_vt(a), fp_load(LB_R3)); }  // inv(0)=0
 LB_HD fp fp_inv_i(const fp& a) {
-  return fp_mul(LB_INV_EEA ? fp_inv_plain_vt_i(a) : fp_inv_plain_by_i(a), fp_load(LB_R3));
+  return fp_mul(fp_inv_plain_by_i(a), fp_load(LB_R3));
 }
-#ifndef LB_POW_INL
-#define LB_POW_INL true  // exponentiations with inline products (A/B: false = out-of-line fp_mul_v)
-#endif
-LB_NI fp fp_pow_const(fp a, const uint32_t* e, int top_bit) { return fp_pow_const_i<LB_POW_INL>(a, e, top_bit); }
+LB_NI fp fp_pow_const(fp a, const uint32_t* e, int top_bit) { return fp_pow_const_i<true>(a, e, top_bit); }
 LB_HD fp fp_sqrt_cand(const fp& a) { return fp_pow_const(a, LB_EXP_SQRT, 378); }   // a^((p+1)/4)
 LB_HD fp fp_isqrt_cand(const fp& a) { return fp_pow_const(a, LB_EXP_ISQRT, 378); }  // a^((p-3)/4)
 // Quadratic character by the binary Jacobi-symbol algorithm (variable time; every input is
@@ -1013,7 +909,7 @@ template <bool kInl = false>
 LB_HD bool fp2_sqrt_i(fp2& out, const fp2& a) {
   fp norm = fp_add(fp_sqr(a.c0), fp_sqr(a.c1));
   fp alpha;
-  if constexpr (kInl) alpha = fp_pow_const_i<LB_POW_INL>(norm, LB_EXP_SQRT, 378);
+  if constexpr (kInl) alpha = fp_pow_const_i<true>(norm, LB_EXP_SQRT, 378);
   else alpha = fp_sqrt_cand(norm);  // sqrt(norm) if it exists
   fp inv2 = fp_load(LB_INV2);
   fp d1 = fp_mul(fp_add(a.c0, alpha), inv2);
@@ -1023,7 +919,7 @@ LB_HD bool fp2_sqrt_i(fp2& out, const fp2& a) {
   // z = delta^((p-3)/4), s = delta z = delta^((p+1)/4), and s z = delta^((p-1)/2) = +-1, so
   // 1/s = +-z: the square root and the inverse it needs come from one exponentiation
   fp z;
-  if constexpr (kInl) z = fp_pow_const_i<LB_POW_INL>(delta, LB_EXP_ISQRT, 378);
+  if constexpr (kInl) z = fp_pow_const_i<true>(delta, LB_EXP_ISQRT, 378);
   else z = fp_isqrt_cand(delta);
   fp s = fp_mul(delta, z);
   bool delta_qr = fp_eq(fp_sqr(s), delta);

@@ -35,34 +35,14 @@
                        // profiles/r3_variants_ab.txt); the ladder state in LDS instead (24 KB per
                        // wave) still spilled and ran 4.7 M at one in flight.
 #endif
-#ifndef LB_SUBGROUP_INL
-#define LB_SUBGROUP_INL true  // k_sig_subgroup: Fp products inline (no call-boundary spills)
-#endif
 #ifndef LB_MINW_MSM
 #define LB_MINW_MSM 1  // k_msm_chunks (2 spills; within noise under load)
 #endif
 #ifndef LB_MINW_GSUM
 #define LB_MINW_GSUM 1  // k_gsum_chunks (all-inline)
 #endif
-#ifndef LB_G1_INL
-#define LB_G1_INL 1  // k_pk_blind's GLV ladder with inline products (jac<fpi>); 0: out-of-line calls
-#endif
-#ifndef LB_G2_INL
-#define LB_G2_INL 1  // the MSM's G2 additions (chunks, buckets, reduction) with inline products
-#endif
-#if LB_G1_INL
-typedef fpi lb_g1f;  // the G1 chunk and per-root sums' additions with inline products
-#else
-typedef fp lb_g1f;
-#endif
-#ifndef LB_G2_INL_SB
-#define LB_G2_INL_SB LB_G2_INL  // ... and k_sig_blind's per-set GLV ladder
-#endif
-#if LB_G2_INL
-typedef fp2i lb_g2f;
-#else
-typedef fp2 lb_g2f;
-#endif
+typedef fpi lb_g1f;   // the G1 chunk and per-root sums' additions and k_pk_blind's GLV ladder: inline products
+typedef fp2i lb_g2f;  // the MSM's G2 additions (chunks, buckets, reduction) and k_sig_blind's per-set GLV ladder
 typedef jac<lb_g2f> g2jm;
 #ifndef LB_MINW_G1
 #define LB_MINW_G1 2  // G1 kernels: one Fp multiply per step, so a second wave hides its latency
@@ -239,7 +219,8 @@ __global__ void __launch_bounds__(LB_TPB, LB_MINW_SUB) k_sig_subgroup(uint32_t n
   uint32_t i = lb_tid();
   if (i >= n) return;
   if (sig_status[i] != LB_OK || sig_inf[i]) return;
-  // Scott's test psi(P) == [x]P with [|x|]P by the register-lean ladder (lb_curve.h).  P is
+  // Scott's test psi(P) == [x]P with [|x|]P by the register-lean ladder (lb_curve.h), its Fp
+  // products inline (no call-boundary spills).  P is
   // re-read from memory coordinate by coordinate where the additions use it, through a base
   // pointer re-derived at each read: otherwise the compiler hoists the 48 row addresses (96
   // VGPRs) out of the ladder and spills them (696 B of private segment per lane before)
@@ -257,7 +238,7 @@ __global__ void __launch_bounds__(LB_TPB, LB_MINW_SUB) k_sig_subgroup(uint32_t n
   bool redo = false;
 #pragma clang loop unroll(disable)
   for (int b = 62; b >= 0;) {
-    g2_dbl_lean<LB_SUBGROUP_INL>(acc);
+    g2_dbl_lean<true>(acc);
     if (redo) {
       redo = false;
       b--;
@@ -270,10 +251,10 @@ __global__ void __launch_bounds__(LB_TPB, LB_MINW_SUB) k_sig_subgroup(uint32_t n
         continue;
       }
       // acc + P (madd-2007-bl with Z3 = 2 Z1 H), ordered so Z1Z1 dies before the Karatsuba temporaries
-      const fp2 Z1Z1 = lean2_sqr<LB_SUBGROUP_INL>(acc.z);
-      const fp2 H = fp2_sub(lean2_mul<LB_SUBGROUP_INL>(load_f2(0), Z1Z1), acc.x);
-      const fp2 t = lean2_mul<LB_SUBGROUP_INL>(acc.z, Z1Z1);
-      const fp2 rr = fp2_dbl(fp2_sub(lean2_mul<LB_SUBGROUP_INL>(load_f2(24), t), acc.y));
+      const fp2 Z1Z1 = lean2_sqr<true>(acc.z);
+      const fp2 H = fp2_sub(lean2_mul<true>(load_f2(0), Z1Z1), acc.x);
+      const fp2 t = lean2_mul<true>(acc.z, Z1Z1);
+      const fp2 rr = fp2_dbl(fp2_sub(lean2_mul<true>(load_f2(24), t), acc.y));
       if (fp2_is_zero(H)) {
         if (fp2_is_zero(rr)) {  // acc == P
           acc = jac_from_aff(g2a{load_f2(0), load_f2(24)});
@@ -284,24 +265,24 @@ __global__ void __launch_bounds__(LB_TPB, LB_MINW_SUB) k_sig_subgroup(uint32_t n
         }
         continue;
       }
-      acc.z = fp2_dbl(lean2_mul<LB_SUBGROUP_INL>(acc.z, H));
-      const fp2 I = fp2_mul4(lean2_sqr<LB_SUBGROUP_INL>(H));
-      const fp2 J = lean2_mul<LB_SUBGROUP_INL>(H, I);
-      const fp2 V = lean2_mul<LB_SUBGROUP_INL>(acc.x, I);
-      const fp2 YJ = fp2_dbl(lean2_mul<LB_SUBGROUP_INL>(acc.y, J));
-      acc.x = fp2_sub(fp2_sub(lean2_sqr<LB_SUBGROUP_INL>(rr), J), fp2_dbl(V));
-      acc.y = fp2_sub(lean2_mul<LB_SUBGROUP_INL>(rr, fp2_sub(V, acc.x)), YJ);
+      acc.z = fp2_dbl(lean2_mul<true>(acc.z, H));
+      const fp2 I = fp2_mul4(lean2_sqr<true>(H));
+      const fp2 J = lean2_mul<true>(H, I);
+      const fp2 V = lean2_mul<true>(acc.x, I);
+      const fp2 YJ = fp2_dbl(lean2_mul<true>(acc.y, J));
+      acc.x = fp2_sub(fp2_sub(lean2_sqr<true>(rr), J), fp2_dbl(V));
+      acc.y = fp2_sub(lean2_mul<true>(rr, fp2_sub(V, acc.x)), YJ);
     }
     b--;
   }
   bool ok = !jac_is_inf(acc);  // psi(P) is finite
   if (ok) {
-    const fp2 z2 = lean2_sqr<LB_SUBGROUP_INL>(acc.z);
-    ok = fp2_eq(lean2_mul<LB_SUBGROUP_INL>(lean2_mul<LB_SUBGROUP_INL>(fp2_conj(load_f2(0)), fp2_load(LB_PSI_CX)), z2),
+    const fp2 z2 = lean2_sqr<true>(acc.z);
+    ok = fp2_eq(lean2_mul<true>(lean2_mul<true>(fp2_conj(load_f2(0)), fp2_load(LB_PSI_CX)), z2),
                 acc.x);
     if (ok) {
-      const fp2 py = lean2_mul<LB_SUBGROUP_INL>(fp2_conj(load_f2(24)), fp2_load(LB_PSI_CY));
-      ok = fp2_eq(lean2_mul<LB_SUBGROUP_INL>(lean2_mul<LB_SUBGROUP_INL>(py, z2), acc.z), fp2_neg(acc.y));
+      const fp2 py = lean2_mul<true>(fp2_conj(load_f2(24)), fp2_load(LB_PSI_CY));
+      ok = fp2_eq(lean2_mul<true>(lean2_mul<true>(py, z2), acc.z), fp2_neg(acc.y));
     }
   }
   if (!ok) sig_status[i] = LB_POINT_NOT_IN_GROUP;
@@ -430,11 +411,8 @@ __device__ __forceinline__ bool fp_is_square_bin_i(const fp& a) {
     if (zero) return false;
   }
 }
-#ifndef LB_JAC_SG
-#define LB_JAC_SG 1  // 0: the binary Jacobi symbol only (A/B)
-#endif
 __device__ __forceinline__ bool fp_is_square_i(const fp& a) {
-  if (LB_JAC_SG) {
+  {  // (a scope of its own: without it k_hash_map's registers are allocated differently)
     const int s = fp_is_square_sg(a);  // (aR | p) = (a | p): R = 2^384 is a square
     if (s >= 0) return s == 1;
   }
@@ -501,16 +479,16 @@ __global__ void __launch_bounds__(LB_TPB, LB_MINW) k_hash_map(uint32_t n, uint32
   soa_st(q, 2 * n, which * n + u, map_to_curve_g2_i(hash_to_field_u(M, (int)which)));
 }
 #endif  // LB_KG
-// k_decompress_sigs with 16 lanes per signature (4 per wave): every lane of a row decodes the
-// same signature and the square root's exponentiations run as row products (r1_pow_const), for
-// small batches on a device running alone.
+// k_decompress_sigs with a row pair (32 lanes) per signature, two per wave: every lane of the pair
+// decodes the same signature and the square root's exponentiations run as row products on the pair
+// (r2_pow_const), for small batches on a device running alone.
 #if LB_KG(13)
 __global__ void __launch_bounds__(64) k_decompress_sigs_row(uint32_t n, const uint8_t* __restrict__ sigs,
                                                             const uint32_t* __restrict__ sig_sizes,
                                                             uint32_t* __restrict__ sig_aff, uint4* __restrict__ sig_aos,
                                                             uint32_t* __restrict__ sig_inf,
                                                             int32_t* __restrict__ sig_status) {
-  const uint32_t i = (blockIdx.x * 64 + threadIdx.x) >> (LB_H2C_FOLD ? 5 : 4);  // a row pair (r2_pow_const) / a row
+  const uint32_t i = (blockIdx.x * 64 + threadIdx.x) >> 5;  // a row pair (r2_pow_const)
   const uint32_t ic = i < n ? i : n - 1;  // rows past the end decode the last signature again
   int st = LB_OK;
   g2a a;
@@ -526,13 +504,9 @@ __global__ void __launch_bounds__(64) k_decompress_sigs_row(uint32_t n, const ui
       const uint4 v = s[k];
       w[4 * k] = v.x, w[4 * k + 1] = v.y, w[4 * k + 2] = v.z, w[4 * k + 3] = v.w;
     }
-#if LB_H2C_FOLD
     st = g2_decompress96_wp(w, a, inf, [](const fp& x, const uint32_t* e, int top) { return r2_pow_const(x, e, top); });
-#else
-    st = g2_decompress96_wp(w, a, inf, [](const fp& x, const uint32_t* e, int top) { return r1_pow_const(x, e, top); });
-#endif
   }
-  if (i >= n || (threadIdx.x & (LB_H2C_FOLD ? 31 : 15)) != 0) return;
+  if (i >= n || (threadIdx.x & 31) != 0) return;
   soa_st(sig_aff, n, i, a);
   const uint32_t* w = reinterpret_cast<const uint32_t*>(&a);
   LB_UNROLL for (int k = 0; k < 12; k++) sig_aos[(size_t)12 * i + k] = make_uint4(w[4 * k], w[4 * k + 1], w[4 * k + 2], w[4 * k + 3]);
@@ -540,22 +514,16 @@ __global__ void __launch_bounds__(64) k_decompress_sigs_row(uint32_t n, const ui
   sig_status[i] = st;
 }
 #endif  // LB_KG
-// The same with 16 lanes per field element (4 per wave): the lanes of a row run the same item and
-// share its square roots' exponentiations as row products (lb_row.h r1_pow_const), for batches
-// with few distinct roots on a device running alone (latency: 1.5 -> ~0.6 ms per call).
+// k_hash_map with one wave per field element: its lanes run the same item and share the map's Fp2
+// arithmetic and its square roots' exponentiations as row products (lb_row.h), for batches with few
+// distinct roots on a device running alone (latency: 1.5 -> ~0.6 ms per call).
 #if LB_KG(13)
 __global__ void __launch_bounds__(64) k_hash_map_row(uint32_t n, uint32_t nu, const uint32_t* __restrict__ uniq_set,
                                                      const uint8_t* __restrict__ msgs, uint32_t* __restrict__ q) {
-#if LB_H2C_FOLD
-  // two items per wave, a row PAIR each: map_to_curve_g2_fold with row products (rfp2 / rfp) and
-  // the exponentiations on the pair (r2_pow_rf)
-#if LBR_FP2_W4
-  const uint32_t t = blockIdx.x;  // one item per wave (rfp2 products on its four rows)
-  if (t >= 2 * nu) return;        // (whole wave)
-#else
-  const uint32_t t = (blockIdx.x * 64 + threadIdx.x) >> 5;
-  if (blockIdx.x * 2 >= 2 * nu) return;  // (whole wave)
-#endif
+  // one item per wave: map_to_curve_g2_fold with row products (rfp2 products on the wave's four
+  // rows, rfp on a row pair) and the exponentiations on the pair (r2_pow_rf)
+  const uint32_t t = blockIdx.x;
+  if (t >= 2 * nu) return;  // (whole wave)
   const uint32_t tc = t < 2 * nu ? t : 2 * nu - 1;
   const uint32_t which = tc < nu ? 0u : 1u;
   const uint32_t u = which ? tc - nu : tc;
@@ -568,23 +536,7 @@ __global__ void __launch_bounds__(64) k_hash_map_row(uint32_t n, uint32_t nu, co
   }
   const g2j r = map_to_curve_g2_fold_t<rfp2, rfp>(hash_to_field_u(M, (int)which),
                                                 [](const rfp& a, const uint32_t* e, int top) { return r2_pow_rf(a, e, top); });
-  if (t < 2 * nu && (threadIdx.x & (LBR_FP2_W4 ? 63 : 31)) == 0) soa_st(q, 2 * n, which * n + u, r);
-#else
-  const uint32_t t = (blockIdx.x * 64 + threadIdx.x) >> 4;
-  if (blockIdx.x * 4 >= 2 * nu) return;  // (whole wave)
-  const uint32_t tc = t < 2 * nu ? t : 2 * nu - 1;  // rows past the end recompute the last item
-  const uint32_t which = tc < nu ? 0u : 1u;
-  const uint32_t u = which ? tc - nu : tc;
-  const uint4* m4 = reinterpret_cast<const uint4*>(msgs + (size_t)32 * uniq_set[u]);
-  uint32_t M[8];
-  LB_UNROLL for (int i = 0; i < 2; i++) {
-    const uint4 v = m4[i];
-    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-    LB_UNROLL for (int k = 0; k < 4; k++) M[4 * i + k] = __builtin_bswap32(w[k]);
-  }
-  const g2j r = map_to_curve_g2_i<true>(hash_to_field_u(M, (int)which));
-  if (t < 2 * nu && (threadIdx.x & 15) == 0) soa_st(q, 2 * n, which * n + u, r);
-#endif
+  if (t < 2 * nu && (threadIdx.x & 63) == 0) soa_st(q, 2 * n, which * n + u, r);
 }
 #endif  // LB_KG
 
@@ -1030,11 +982,7 @@ __global__ void __launch_bounds__(LB_INV_TPB, LB_MINW_G1) k_pk_blind(uint32_t n,
       const g1a pk = soa_ld<g1a>(pk_aff, n, i);
       const g1a t2{fp_mul(pk.x, fp_load(LB_GLV_BETA)), pk.y};
       const g1a t3{fp_mul(pk.x, fp_load(LB_GLV_BETA2)), fp_neg(pk.y)};
-#if LB_G1_INL
       rj = jac_as<fp>(jac_mul_glv_i<fpi, true>(aff_as<fpi>(pk), aff_as<fpi>(t2), aff_as<fpi>(t3), scalars[i]));
-#else
-      rj = jac_mul_glv_i<fp, true>(pk, t2, t3, scalars[i]);
-#endif
     }
     aos_st(rpk, i, rj);
     return;
@@ -1078,11 +1026,7 @@ __global__ void __launch_bounds__(LB_INV_TPB, LB_MINW_G1) k_pk_blind(uint32_t n,
     // r * PK with r = lo + hi * lambda: t2 = [lambda]PK = (beta x, y), t3 = PK + t2 = (beta^2 x, -y)
     const g1a t2{fp_mul(pk.x, fp_load(LB_GLV_BETA)), pk.y};
     const g1a t3{fp_mul(pk.x, fp_load(LB_GLV_BETA2)), fp_neg(pk.y)};
-#if LB_G1_INL
     rj = jac_as<fp>(jac_mul_glv_i<fpi, true>(aff_as<fpi>(pk), aff_as<fpi>(t2), aff_as<fpi>(t3), scalars[i]));
-#else
-    rj = jac_mul_glv_i<fp, true>(pk, t2, t3, scalars[i]);
-#endif
   } else {
     rj = jac_infinity<fp>();
   }
@@ -1339,9 +1283,6 @@ __global__ void __launch_bounds__(64) k_sig_blind_w4(uint32_t n, const uint32_t*
 // out-of-line product calls per step, f, T, the lines and the temporaries spilled 6.7 KB per
 // lane to the private segment, which the runtime reserves per HIP queue for the device's whole
 // wave capacity (the per-device engine cap).
-#ifndef LB_MILLER_LANE_REG
-#define LB_MILLER_LANE_REG 0
-#endif
 typedef __attribute__((address_space(3))) uint32_t lds_w;
 template <int NL>  // slots [0, NL) in LDS (2: f; 3: f and the temporary), the rest in global memory
 struct lane_lds {
@@ -1410,14 +1351,6 @@ __global__ void __launch_bounds__(LB_TPB, 1) k_miller_lane(uint32_t n, uint32_t 
                                                            const uint32_t* __restrict__ gp_inf,
                                                            const uint32_t* __restrict__ h_aff,
                                                            uint32_t* __restrict__ treeP, uint32_t* __restrict__ tpark) {
-#if LB_MILLER_LANE_REG  // A/B builds only: the round-3 register-resident kernel (6.7 KB private segment)
-  const uint32_t u = lb_tid();
-  if (u >= *n_u) return;
-  fp12 f = fp12_one();
-  if (!gp_inf[u]) f = miller_loop_inl(soa_ld<g1a>(gp_aff, n, u), soa_ld<g2a>(h_aff, n, u));
-  soa_st(treeP, 2 * m, m + u, f);
-  (void)tpark;
-#else
   static_assert(LB_TPB == 64, "one wave per block: 64 lanes of LDS slots");
   __shared__ uint32_t lds[NL * 72 * 64];
   const uint32_t u = lb_tid();
@@ -1465,7 +1398,6 @@ __global__ void __launch_bounds__(LB_TPB, 1) k_miller_lane(uint32_t n, uint32_t 
     const uint32_t* w = reinterpret_cast<const uint32_t*>(&v);
     LB_UNROLL for (int i = 0; i < 72; i++) treeP[(size_t)(72 * h + i) * (2 * m) + m + u] = w[i];
   }
-#endif
 }
 #endif  // LB_KG
 
@@ -2055,11 +1987,7 @@ __global__ void __launch_bounds__(LB_INV_TPB, LB_MINW) k_sig_blind(uint32_t n, c
     const fp2 zi{fp_mul(s.z.c0, ni), fp_neg(fp_mul(s.z.c1, ni))};
     const fp2 zi2 = fp2_sqr(zi);
     const g2a t3{fp2_mul(s.x, zi2), fp2_mul(fp2_mul(s.y, zi2), zi)};
-#if LB_G2_INL_SB
     r = jac_as<fp2>(jac_mul_glv_i<fp2i, true>(aff_as<fp2i>(t1), aff_as<fp2i>(t2), aff_as<fp2i>(t3), scalars[i]));
-#else
-    r = jac_mul_glv_i<fp2, true>(t1, t2, t3, scalars[i]);
-#endif
   }
   soa_st(terms, n, i, r);
 }

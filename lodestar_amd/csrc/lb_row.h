@@ -41,7 +41,7 @@
 #define LBR_N_AREAS 8
 #define LBR_PT (LBR_PERSIST + 12 * LBR_N_AREAS)  // Miller loop: P (2), Q (4), T (6)
 #define LBR_XS (LBR_PT + 16)                     // staging slots for import / export (16)
-#define LBR_ROWX (LBR_XS + 16)                   // one operand slot per row
+#define LBR_ROWX (LBR_XS + 16)                   // one slot per row (no user left; they keep the LDS size as it was)
 #define LBR_SLOTS (LBR_ROWX + LBR_NROWS)
 #define LBR_SLOT_WORDS (16 * LBR_SLOTS)
 #define LBR_MISC 8  // words after the slots: [0] first staged program word, [1] flag, [2] scratch
@@ -79,19 +79,12 @@ __device__ __forceinline__ int64_t r_dpp64(int64_t v) {
 }
 #define LBR_SHR(n) (0x110 + (n))  // lane k <- lane k - n of the row (0 below the row)
 #define LBR_SHL(n) (0x100 + (n))  // lane k <- lane k + n of the row (0 above the row)
-// broadcast lane 13 of each row (ds_swizzle bit mode: lane' = (lane & 0x10) | 13 within 32)
 // lane I of the row to every lane of the row (DPP row_newbcast: a VALU move, no LDS round trip)
 template <int I>
 __device__ __forceinline__ int r_bcast(int v) {
   return __builtin_amdgcn_mov_dpp(v, 0x150 + I, 0xF, 0xF, false);
 }
-__device__ __forceinline__ int r_bcast13(int v) {
-#ifdef LBR_SWIZZLE_BCAST
-  return __builtin_amdgcn_ds_swizzle(v, 0x10 | (13 << 5));
-#else
-  return r_bcast<13>(v);
-#endif
-}
+__device__ __forceinline__ int r_bcast13(int v) { return r_bcast<13>(v); }
 // a distributed element (lane k: limb k) replicated in every lane of the row
 __device__ __forceinline__ void r_rep(int v, int (&x)[14]) {
   x[0] = r_bcast<0>(v); x[1] = r_bcast<1>(v); x[2] = r_bcast<2>(v); x[3] = r_bcast<3>(v);
@@ -243,15 +236,6 @@ __device__ __forceinline__ int r_operand(const lds_i32* S, const lds_i32* rec, i
   return r_norm<true>(acc, k);
 }
 
-__device__ __forceinline__ void r_load_rep(const lds_i32* S, int slot, int (&x)[14]) {
-  const lds_i32x4* q = (const lds_i32x4*)(S + 16 * slot);
-  const i32x4 a = q[0], b = q[1], c = q[2], d = q[3];
-  x[0] = a.x; x[1] = a.y; x[2] = a.z; x[3] = a.w;
-  x[4] = b.x; x[5] = b.y; x[6] = b.z; x[7] = b.w;
-  x[8] = c.x; x[9] = c.y; x[10] = c.z; x[11] = c.w;
-  x[12] = d.x; x[13] = d.y;
-}
-
 // base of the staged program image as seen from LDS (words below `first` are never used)
 __device__ __forceinline__ const lds_i32* r_progs(int32_t* S) {
   const lds_i32* s = r_lds(S);
@@ -348,10 +332,6 @@ __device__ void r_exec_tail(lds_i32* S, const lds_i32* prog, int pos, int h0, in
   }
 }
 
-#ifndef LBR_EXEC_ATTR
-#define LBR_EXEC_ATTR __attribute__((noinline))
-#endif
-#ifndef LBR_EXEC_V1
 // Run one program (offset `off` in the image): inputs already in IN, outputs left in the temps
 // the header lists.  r_exec_inl is inlined once into r_run's loop (lb_row.h, end): a call of the
 // out-of-line r_exec costs ~0.9 us of callee-saved scratch round trips, on the order of a phase.
@@ -429,78 +409,7 @@ __device__ __forceinline__ void r_exec_inl(int32_t* S_generic, int off) {
     h1 = nh1;
   }
 }
-__device__ LBR_EXEC_ATTR void r_exec(int32_t* S_generic, int off) { r_exec_inl(S_generic, off); }
-#else
-__device__ __attribute__((noinline)) void r_exec(int32_t* S_generic, int off) {
-  lds_i32* S = r_lds(S_generic);
-  const lds_i32* prog = r_progs(S_generic) + off;
-  const int k = r_limb(), row = r_row(), pk = r_plimb(k);
-  const int nph = __builtin_amdgcn_readfirstlane(prog[0]), nout = __builtin_amdgcn_readfirstlane(prog[1]);
-  int pos = 2 + nout;
-  for (int ph = 0; ph < nph; ph++) {
-    const int h0 = __builtin_amdgcn_readfirstlane(prog[pos]), h1 = __builtin_amdgcn_readfirstlane(prog[pos + 1]);
-    pos += 2;
-    const int kind = h0 & 0xff, flags = (h0 >> 8) & 0xff, n = h0 >> 16;
-    const int nx = h1 & 0xffff, ny = h1 >> 16;
-    if (kind == 0) {
-      const int rs = 1 + nx + ny;
-      for (int base = 0; base < n; base += LBR_NROWS) {
-        const int t = base + row;
-        if (t < n) {
-          const lds_i32* rec = prog + pos + t * rs;
-          const int dst = rec[0];
-#ifdef LBR_SUB_HOOK
-          LBR_SUB_HOOK(1, dst);
-#endif
-          const int y = (flags & 2) ? S[16 * (rec[1 + nx] & 0xffff) + k] : r_operand(S, rec + 1 + nx, ny, k, flags & 8, pk);
-#ifdef LBR_SUB_HOOK
-          LBR_SUB_HOOK(2, y);
-#endif
-          int x[14];
-#ifdef LBR_LDS_REP
-          int xs;
-          if (flags & 1) {
-            xs = rec[1] & 0xffff;
-          } else {
-            xs = LBR_ROWX + row;
-            S[16 * xs + k] = r_operand(S, rec + 1, nx, k, flags & 4, pk);
-          }
-          r_load_rep(S, xs, x);
-#else
-          r_rep((flags & 1) ? S[16 * (rec[1] & 0xffff) + k] : r_operand(S, rec + 1, nx, k, flags & 4, pk), x);
-#endif
-#ifdef LBR_SUB_HOOK
-          LBR_SUB_HOOK(3, x[13]);
-#endif
-          const int rv = rp_mul(x, y, k);
-#ifdef LBR_SUB_HOOK
-          LBR_SUB_HOOK(4, rv);
-#endif
-          S[16 * dst + k] = rv;
-        }
-      }
-      pos += n * rs;
-    } else {
-      // ny: row offset (a linear phase merged into the product phase before it runs on the rows
-      // after the products')
-      const int rs = 1 + nx, rr = (row - ny + 4 * LBR_NROWS) % LBR_NROWS;
-      for (int base = 0; base < n; base += LBR_NROWS) {
-        const int t = base + rr;
-        if (t < n) {
-          const lds_i32* rec = prog + pos + t * rs;
-          S[16 * rec[0] + k] = r_sum<3>(S, rec + 1, nx, k, pk);
-        }
-      }
-      pos += n * rs;
-    }
-    if (kind != 0 || !(flags & 16)) r_sync();  // flag 16: the next (linear) phase reads nothing of this one
-#ifdef LBR_PHASE_HOOK
-    LBR_PHASE_HOOK(ph, kind, n);
-#endif
-  }
-}
-__device__ __forceinline__ void r_exec_inl(int32_t* S_generic, int off) { r_exec(S_generic, off); }
-#endif  // LBR_EXEC_V1
+__device__ __attribute__((noinline)) void r_exec(int32_t* S_generic, int off) { r_exec_inl(S_generic, off); }
 
 // ---------------------------------------------------------------- element moves (limb-parallel)
 // dst[e] = src(e) for e < n (src(e) a slot index; every source read before any write)
@@ -681,9 +590,6 @@ __device__ void r_init(int32_t* S_generic, int nprog = LBR_PROGS_FE, int first =
 // products, each operand a sum of <= 8 input slots (a: 0..11, b: 12..23); phase 2, rows 0..11: the
 // outputs, <= 36 product terms each (tools/gen_mul12_fast.py -> lb_mul12_tab.h, checked against
 // the oracle's tower product).  dst may equal a or b.
-#ifndef LBR_MUL12_FAST
-#define LBR_MUL12_FAST 1
-#endif
 __device__ __forceinline__ void r_mul12_fast(int32_t* S_generic, int dst, int a, int b) {
   lds_i32* S = r_lds(S_generic);
   const int k = r_limb(), row = r_row();
@@ -709,15 +615,7 @@ __device__ __forceinline__ void r_mul12_fast(int32_t* S_generic, int dst, int a,
   r_sync();
 }
 
-__device__ void r_mul(int32_t* S, int dst, int a, int b) {
-  if (LBR_MUL12_FAST) {
-    r_mul12_fast(S, dst, a, b);
-    return;
-  }
-  r_gather(S, LBR_IN, 24, [&](int e) { return e < 12 ? a + e : b + e - 12; });
-  r_exec(S, LBR_MUL12);
-  r_out(S, LBR_MUL12, 0, 12, dst);
-}
+__device__ void r_mul(int32_t* S, int dst, int a, int b) { r_mul12_fast(S, dst, a, b); }
 __device__ void r_sqr(int32_t* S, int dst, int a) {
   r_copy(S, LBR_IN, a, 12);
   r_exec(S, LBR_SQR12);
@@ -735,9 +633,6 @@ __device__ void r_sqr(int32_t* S, int dst, int a) {
 //     c10 = 3 xi t2.r1 + 2 a10, c11 = 3 t0.r1 + 2 a11, c12 = 3 t1.r1 + 2 a12
 // (tools/gen_row_programs.py cyclotomic_sqr; slot k = c{k/6}.c{(k%6)/2}.c{k%2}).  Two barriers per
 // squaring; dst may equal src (output k reads only input k).
-#ifndef LBR_CSQR_FAST
-#define LBR_CSQR_FAST 1
-#endif
 __device__ __forceinline__ void r_csqr_fast(int32_t* S_generic, int dst, int src) {
   lds_i32* S = r_lds(S_generic);
   const int k = r_limb(), row = r_row();
@@ -785,9 +680,6 @@ __device__ __forceinline__ void r_csqr_fast(int32_t* S_generic, int dst, int src
 // level 2 (Karatsuba) over combinations of P; phase 3, rows 0..5: the outputs.  Each row's integer
 // coefficients come from tools/gen_pdbl_fast.py (lb_pdbl_tab.h), which checks the three phases
 // against the oracle's doubling.  dst may equal src.
-#ifndef LBR_PDBL_FAST
-#define LBR_PDBL_FAST 1
-#endif
 __device__ __forceinline__ void r_pdbl_fast(int32_t* S_generic, int dst, int src) {
   lds_i32* S = r_lds(S_generic);
   const int k = r_limb(), row = r_row();
@@ -825,15 +717,7 @@ __device__ __forceinline__ void r_pdbl_fast(int32_t* S_generic, int dst, int src
 }
 
 // a^2 for a in the cyclotomic subgroup (Granger-Scott: 18 products instead of 36)
-__device__ void r_csqr(int32_t* S, int dst, int a) {
-  if (LBR_CSQR_FAST) {
-    r_csqr_fast(S, dst, a);
-    return;
-  }
-  r_copy(S, LBR_IN, a, 12);
-  r_exec(S, LBR_CSQR12);
-  r_out(S, LBR_CSQR12, 0, 12, dst);
-}
+__device__ void r_csqr(int32_t* S, int dst, int a) { r_csqr_fast(S, dst, a); }
 __device__ void r_frob(int32_t* S, int dst, int a) {
   r_copy(S, LBR_IN, a, 12);
   r_exec(S, LBR_FROB);
@@ -1019,44 +903,24 @@ __device__ __forceinline__ rfp2 f_add(const rfp2& a, const rfp2& b) { return rfp
 __device__ __forceinline__ rfp2 f_sub(const rfp2& a, const rfp2& b) { return rfp2{f_sub(a.c0, b.c0), f_sub(a.c1, b.c1)}; }
 __device__ __forceinline__ rfp2 f_neg(const rfp2& a) { return rfp2{f_neg(a.c0), f_neg(a.c1)}; }
 __device__ __forceinline__ rfp2 f_dbl(const rfp2& a) { return rfp2{f_dbl(a.c0), f_dbl(a.c1)}; }
-// LBR_FP2_W4 (default): every rfp2 user runs one item per WAVE (the four rows hold the same
-// values), so the Karatsuba products take one row product on rows 0..2 (w4_mul) instead of three
-// in sequence on each row
+// Every rfp2 user runs one item per WAVE (the four rows hold the same values), so the Karatsuba
+// products take one row product on rows 0..2 (w4_mul) instead of three in sequence on each row.
+// The operand sums (a0 + a1)(b0 + b1) by carry rounds only (|sum| < 4p, a valid rp_mul operand).
 __device__ __forceinline__ rfp2 f_mul(const rfp2& a, const rfp2& b) {
-#if LBR_FP2_W4
-  {
-    const int k = r_limb();
-    const rfp x[3] = {a.c0, a.c1, rfp{r_norm<true>((int64_t)a.c0.v + a.c1.v, k)}};
-    const rfp y[3] = {b.c0, b.c1, rfp{r_norm<true>((int64_t)b.c0.v + b.c1.v, k)}};
-    rfp t[3];
-    w4_mul<3>(x, y, t);
-    return rfp2{rf_red((int64_t)t[0].v - t[1].v), rf_red((int64_t)t[2].v - t[0].v - t[1].v)};
-  }
-#endif
-  const rfp t0 = f_mul(a.c0, b.c0), t1 = f_mul(a.c1, b.c1);
   const int k = r_limb();
-  // (a0 + a1)(b0 + b1): operand sums by carry rounds only (|sum| < 4p, a valid rp_mul operand)
-  int x[14];
-  r_rep(r_norm<true>((int64_t)a.c0.v + a.c1.v, k), x);
-  const int t2 = rp_mul(x, r_norm<true>((int64_t)b.c0.v + b.c1.v, k), k);
-  return rfp2{rf_red((int64_t)t0.v - t1.v), rf_red((int64_t)t2 - t0.v - t1.v)};
+  const rfp x[3] = {a.c0, a.c1, rfp{r_norm<true>((int64_t)a.c0.v + a.c1.v, k)}};
+  const rfp y[3] = {b.c0, b.c1, rfp{r_norm<true>((int64_t)b.c0.v + b.c1.v, k)}};
+  rfp t[3];
+  w4_mul<3>(x, y, t);
+  return rfp2{rf_red((int64_t)t[0].v - t[1].v), rf_red((int64_t)t[2].v - t[0].v - t[1].v)};
 }
 __device__ __forceinline__ rfp2 f_sqr(const rfp2& a) {
   const int k = r_limb();
-#if LBR_FP2_W4
-  {
-    const rfp x[2] = {rfp{r_norm<true>((int64_t)a.c0.v + a.c1.v, k)}, a.c0};
-    const rfp y[2] = {rfp{r_norm<true>((int64_t)a.c0.v - a.c1.v, k)}, a.c1};
-    rfp t[2];
-    w4_mul<2>(x, y, t);
-    return rfp2{t[0], f_dbl(t[1])};
-  }
-#endif
-  int x[14];
-  r_rep(r_norm<true>((int64_t)a.c0.v + a.c1.v, k), x);
-  const int t0 = rp_mul(x, r_norm<true>((int64_t)a.c0.v - a.c1.v, k), k);
-  const rfp t1 = f_mul(a.c0, a.c1);
-  return rfp2{rfp{t0}, f_dbl(t1)};
+  const rfp x[2] = {rfp{r_norm<true>((int64_t)a.c0.v + a.c1.v, k)}, a.c0};
+  const rfp y[2] = {rfp{r_norm<true>((int64_t)a.c0.v - a.c1.v, k)}, a.c1};
+  rfp t[2];
+  w4_mul<2>(x, y, t);
+  return rfp2{t[0], f_dbl(t[1])};
 }
 __device__ __forceinline__ bool f_is_zero(const rfp2& a) { return f_is_zero(a.c0) && f_is_zero(a.c1); }
 __device__ __forceinline__ rfp2 f_select(bool c, const rfp2& a, const rfp2& b) {
@@ -1409,9 +1273,6 @@ static_assert(r_ops_fe_tail(LBR_A(0), LBR_A(0)).n <= LBR_MAX_OPS && r_ops_hash_f
 // (tools/gen_row_compiled.py -> lb_row_compiled.h), so a phase is straight-line code; a row reads
 // its own record (dst, operand pairs) from a per-row table; the program's input slots (IN) are
 // mapped to the operation's sources instead of copied in (one copy phase and barrier fewer).
-#ifndef LBR_ML_COMPILED
-#define LBR_ML_COMPILED 1
-#endif
 struct rc_dbl_step {
   static constexpr int NPH = LBC_DBL_STEP_NPH, RS = LBC_DBL_STEP_RS, NOUT = LBC_DBL_STEP_NOUT;
   static constexpr int ph(int p, int f) { return LBC_DBL_STEP_PH[p][f]; }
@@ -1510,17 +1371,17 @@ __device__ __attribute__((noinline)) void r_run(int32_t* S_generic, const r_opl*
       r_copy(S_generic, dst, a, b);
       continue;
     }
-    if (LBR_PDBL_FAST && (kind == RK_PDBL || kind == RK_PDBL2 || kind == RK_PDBL4)) {
+    if (kind == RK_PDBL || kind == RK_PDBL2 || kind == RK_PDBL4) {
       const int nd = kind == RK_PDBL ? 1 : (kind == RK_PDBL2 ? 2 : 4);
       r_pdbl_fast(S_generic, dst, a);
       for (int q = 1; q < nd; q++) r_pdbl_fast(S_generic, dst, dst);
       continue;
     }
-    if (LBR_MUL12_FAST && kind == RK_MUL) {
+    if (kind == RK_MUL) {
       r_mul12_fast(S_generic, dst, a, b);
       continue;
     }
-    if (LBR_CSQR_FAST && (kind == RK_CSQR || kind == RK_CSQR2)) {
+    if (kind == RK_CSQR || kind == RK_CSQR2) {
       r_csqr_fast(S_generic, dst, a);
       if (kind == RK_CSQR2) r_csqr_fast(S_generic, dst, dst);
       continue;
@@ -1530,6 +1391,7 @@ __device__ __attribute__((noinline)) void r_run(int32_t* S_generic, const r_opl*
       r_sync();
       continue;
     }
+    // (RK_MUL, RK_CSQR*, RK_PDBL* were taken above: their cases only keep r_run's code as it was)
     int prog, na, nb, nout;
     switch (kind) {
       case RK_MUL: prog = LBR_MUL12; na = 12; nb = 12; nout = 12; break;
@@ -1622,12 +1484,10 @@ __device__ void r_pow_xabs(int32_t* S, int dst, int a) {
 __device__ void r_final_exp(int32_t* S, int dst, int f) {
   const int T0 = LBR_A(1), A0 = LBR_A(2), B0 = LBR_A(3), C0 = LBR_A(4), X0 = LBR_A(5), Y0 = LBR_A(6);
   r_inv(S, Y0, f, A0, B0, C0);
-#ifndef LBR_NO_OPLIST
   if (dst == LBR_A(0) && f == LBR_A(0)) {
     r_run(S, &LBR_OPS_FE_A0, LBR_OPS_FE_A0.n);
     return;
   }
-#endif
   r_conj(S, X0, f);
   r_mul(S, T0, X0, Y0);
   r_frob2(S, X0, T0);
@@ -1672,14 +1532,11 @@ __device__ void r_miller(int32_t* S_generic, int dst) {
     }
     r_sync();
   }
-#ifndef LBR_NO_OPLIST
   if (dst == LBR_A(0) || dst == LBR_A(7)) {
-    if (LBR_ML_COMPILED) r_run_ml(S_generic, dst == LBR_A(0) ? &LBR_OPS_ML_A0 : &LBR_OPS_ML_A7, LBR_OPS_ML_A0.n);
-    else r_run(S_generic, dst == LBR_A(0) ? &LBR_OPS_ML_A0 : &LBR_OPS_ML_A7, LBR_OPS_ML_A0.n);
+    r_run_ml(S_generic, dst == LBR_A(0) ? &LBR_OPS_ML_A0 : &LBR_OPS_ML_A7, LBR_OPS_ML_A0.n);
     r_conj(S_generic, dst, dst);
     return;
   }
-#endif
   for (int i = 62; i >= 0; i--) {
     r_gather(S_generic, LBR_IN, 20, [&](int e) { return e < 12 ? dst + e : (e < 18 ? TT + e - 12 : PP + e - 18); });
     r_exec(S_generic, LBR_DBL_STEP);

@@ -150,22 +150,15 @@ def from_row(l):
 
 # ------------------------------------------------------------ programs
 class RowProg(G.Prog):
-    """(A/B: ROW_PLAIN=1) every product operand one slot with coefficient 1: sums materialised by a
-    linear task first.  Measured slower than operand sums inside the product phase (one phase
-    more per operation), so the default keeps the wave programs' operand sums."""
-
-    def mul(self, x, y):
-        if os.environ.get("ROW_PLAIN") == "1":
-            return super().mul(self.mat(x), self.mat(y))
-        return super().mul(x, y)
+    """Product operands keep the wave programs' operand sums: every operand one slot with
+    coefficient 1 (sums materialised by a linear task first) measured slower, one phase more per
+    operation."""
 
     def mat(self, lin, force=False):
         """Linear tasks of the same stage are inlined into the sum instead of read as slots (one
         level, i.e. one phase and barrier, instead of a chain); tasks left unread are dropped by
-        encode.  (A/B: ROW_NO_FLATTEN=1.)"""
-        if os.environ.get("ROW_NO_FLATTEN") != "1":
-            lin = self._flatten(lin)
-        return super().mat(lin, force)
+        encode."""
+        return super().mat(self._flatten(lin), force)
 
     def _flatten(self, lin):
         st = self._avail(lin)
@@ -452,15 +445,14 @@ def encode(pg):
     def reads(lin, slot):
         return slot in lin.d
     deferred = {}
-    if os.environ.get("ROW_NO_DEFER") != "1":
-        for s in range(nst):
-            nxt = [p for p in pg.prods if p[0] == s + 1]
-            if not nxt:
-                continue
-            same = [l for l in pg.lins if l[0] == s]
-            deferred[s + 1] = [l for l in same if l[1] == 0
-                               and not any(reads(p[2], l[2]) or reads(p[3], l[2]) for p in nxt)
-                               and not any(reads(o[3], l[2]) for o in same)]
+    for s in range(nst):
+        nxt = [p for p in pg.prods if p[0] == s + 1]
+        if not nxt:
+            continue
+        same = [l for l in pg.lins if l[0] == s]
+        deferred[s + 1] = [l for l in same if l[1] == 0
+                           and not any(reads(p[2], l[2]) or reads(p[3], l[2]) for p in nxt)
+                           and not any(reads(o[3], l[2]) for o in same)]
     moved = {id(l) for ls in deferred.values() for l in ls}
     phases = []
     for s in range(nst + 1):

@@ -15,16 +15,6 @@ __device__ int g_ph_n;
     g_ph[g_ph_n][2] = n;                                             \
     g_ph_n++;                                                        \
   }
-// sub-phase points of the first product of a phase (thread 0), after the value v is ready
-#define LBR_SUB_HOOK(tag, v)                                                        \
-  if (threadIdx.x == 0 && g_ph_n < 64) {                                             \
-    asm volatile("" ::"v"(v));                                                       \
-    __builtin_amdgcn_s_waitcnt(0);                                                   \
-    g_ph[g_ph_n][0] = __builtin_readcyclecounter();                                  \
-    g_ph[g_ph_n][1] = 10 + (tag);                                                    \
-    g_ph[g_ph_n][2] = 0;                                                             \
-    g_ph_n++;                                                                        \
-  }
 #endif
 #ifdef UB_TL
 // a timeline of r_exec_inl (lb_row.h LBR_TL points): thread 0 of each wave adds the s_memtime
@@ -383,8 +373,7 @@ int main() {
       printf("%s: %llu cycles total;", nm[op], tt[1] - tt[0]);
       unsigned long long prev = tt[0];
       for (int i = 0; i < np; i++) {
-        if (ph[i][1] >= 10) printf(" s%llu:%llu", ph[i][1] - 10, ph[i][0] - prev);
-        else printf(" %s%llu:%llu |", ph[i][1] ? "L" : "P", ph[i][2], ph[i][0] - prev);
+        printf(" %s%llu:%llu |", ph[i][1] ? "L" : "P", ph[i][2], ph[i][0] - prev);
         prev = ph[i][0];
       }
       printf("\n");
