@@ -127,6 +127,7 @@ KZG_BATCH_HARNESS = os.path.join(ROOT, "build", "lb_kzg_batch_harness.so")
 KZG_BLOB_HARNESS = os.path.join(ROOT, "build", "lb_kzg_blob_harness.so")
 KZG_CELLS_HARNESS = os.path.join(ROOT, "build", "lb_kzg_cells_harness.so")
 KZG_FK20_HARNESS = os.path.join(ROOT, "build", "lb_kzg_fk20_harness.so")
+SEARCH_HARNESS = os.path.join(ROOT, "build", "lb_search_harness.so")
 
 
 def build_harness(force=False, verbose=True):
@@ -168,6 +169,13 @@ def build_kzg_fk20_harness(force=False, verbose=True):
     points, of the FK20 call on the CPU (tests/test_kzg_fk20_cpu.py)"""
     return _build_so(os.path.join(HDIR, "lb_kzg_fk20_harness.cpp"), KZG_FK20_HARNESS,
                      [os.path.join(HDIR, "kzg_fk20_lanes.h"), FR_VIEWS], ("-O2", "-std=c++17"), force, verbose)
+
+
+def build_search_harness(force=False, verbose=True):
+    """the invalid-set search's planner and interpreter (csrc/lb_search_plan.h) against a model device on
+    the CPU (tests/test_search_plan_cpu.py; tests/test_gpu_parity.py compares the device's trace with it)"""
+    return _build_so(os.path.join(HDIR, "lb_search_harness.cpp"), SEARCH_HARNESS,
+                     [os.path.join(HDIR, "search_model.h")], ("-O2", "-std=c++17"), force, verbose)
 
 
 def build_cpu_pool(force=False, verbose=True):
@@ -225,6 +233,7 @@ def build_all(force=False):
     build_kzg_blob_harness(force)
     build_kzg_cells_harness(force)
     build_kzg_fk20_harness(force)
+    build_search_harness(force)
     build_cpu_pool(force)
     build_ubench(force)
 

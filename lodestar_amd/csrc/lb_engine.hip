@@ -24,6 +24,7 @@
 #include "lb_kernels.h"
 #include "lb_engine_impl.h"  // dbuf, lb_engine, LB_HIP, run_simple: shared with lb_kzg_host.hip (the KZG calls)
 #include "lb_kdecl.h"  // kernels of the other translation units (split build)
+#include "lb_search_plan.h"  // the invalid-set search's planner and interpreter (device-free)
 
 #define LB_ABI_VERSION 1
 
@@ -317,7 +318,6 @@ int32_t lb_engine_create_ex(int32_t device, uint32_t flags, lb_engine** out) {
     delete e;
     return LB_ERR_DEVICE;
   }
-  hipEventCreateWithFlags(&e->ev_g1, hipEventDisableTiming);
   hipEventCreateWithFlags(&e->ev_s, hipEventDisableTiming);
   hipEventCreateWithFlags(&e->ev_fork, hipEventDisableTiming);
   hipEventCreateWithFlags(&e->ev_dec, hipEventDisableTiming);
@@ -380,8 +380,8 @@ void lb_engine_destroy(lb_engine* e) {
   if (!e) return;
   hipSetDevice(e->device);
   hipStreamSynchronize(e->stream);
-  dbuf* bufs[] = {&e->scalars, &e->sig_aff, &e->sig_inf, &e->sig_status, &e->q, &e->h_aff, &e->rpk, &e->rsig,
-                  &e->pk_status, &e->ml, &e->treeP, &e->treeS, &e->job_status, &e->nodes, &e->verdict, &e->parts,
+  dbuf* bufs[] = {&e->scalars, &e->sig_aff, &e->sig_inf, &e->sig_status, &e->q, &e->h_aff, &e->rpk,
+                  &e->pk_status, &e->treeP, &e->treeS, &e->job_status, &e->verdict, &e->parts,
                   &e->ok, &e->chunk_acc, &e->chunk_status, &e->fS, &e->table, &e->comb, &e->msg_tab,
                   &e->rep_of, &e->uid_of, &e->uniq_set, &e->n_u, &e->set_uid, &e->gcnt, &e->gpos, &e->goff,
                   &e->gch, &e->chunk_beg, &e->chunk_end, &e->members, &e->set_live, &e->gacc, &e->gp_aff,
@@ -395,7 +395,6 @@ void lb_engine_destroy(lb_engine* e) {
     if (e->ev0[i]) hipEventDestroy(e->ev0[i]);
     if (e->ev1[i]) hipEventDestroy(e->ev1[i]);
   }
-  hipEventDestroy(e->ev_g1);
   hipEventDestroy(e->ev_s);
   hipEventDestroy(e->ev_fork);
   hipEventDestroy(e->ev_dec);
@@ -1201,89 +1200,14 @@ static int32_t run_pipeline(lb_engine* e, lb_batch* b, const uint64_t* scalars, 
 // ---------------------------------------------------------------- invalid-set search
 // After a failing root check: find the failing SETS (a job fails iff one of its live sets does;
 // per-job verdicts then equal the reference's per-job re-verification, worker.ts:76-98, up to
-// the 2^-64 soundness of the blinding).  Nodes are ranges of the members array (sets sorted by
-// signing root): subtrees of the root product tree (P from the tree), then parts of one root
-// (P = one Miller loop of the part's sum r_i PK_i with that root's H(m)).  A failing node
-// carries its FE value y.  Two moves (lb_kernels.h k_search_check / k_search_test):
-//   direct:   each child c of a node gets its own check, y_c = FE(X_c);
-//   weighted: one FE of prod_c X_c^(c+1) names the failing child when exactly one fails.
-// A failing node descends by a weighted test (one wave for up to 64 children); if the test finds
-// two or more failing children, they are checked directly, each failing child in the same round
-// getting a weighted test over its own children.  The root starts with direct checks, so one
-// round settles two levels.  Costs: a few waves and range MSMs over the failing ranges per
-// round; about four rounds for a batch of ~10^5 sets with a handful of invalid ones.
-namespace {
-struct snode {
-  uint32_t kind;  // 0: node `key` of the root product tree at depth d (d == L: the leaf of root key - mu);
-                  // 1: part of root `key`; 2: the single set `key`, checked unblinded
-  uint32_t key, lo, len, d;
-};
-struct fnode {
-  snode s;
-  bool multi;  // the last weighted test over its children found no single failing child
-  std::vector<uint32_t> y;  // FE value (144 words, the k_root_check / k_search_check layout)
-};
-struct search_ctx {
-  uint32_t n, nu, mu, L;
-  std::vector<uint32_t> goff, members;
-  bool rs = false;  // e->s_root holds the per-root sums S_u
-};
-enum {
-  SX_KIND, SX_KEY, SX_LO, SX_LEN, SX_MIDX, SX_VERDICT, SX_Y, SX_PK,  // direct checks
-  SX_MPRE, SX_MLO, SX_MMODE, SX_MWA, SX_MWB, SX_S,                     // MSM instances
-  SX_TMODE, SX_TF, SX_TV0, SX_TU, SX_TMIDX, SX_TYIDX, SX_TLO, SX_TLEN, SX_TPER, SX_TOUT, SX_TPK, SX_YUP,
-  SX_ML, SX_BLO, SX_BHI, SX_BO, SX_COUNT
-};
+// the 2^-64 soundness of the blinding).  What a round launches and what its results mean is
+// device-free code in lb_search_plan.h (the nodes, the two moves, the planner and the
+// interpreter); here are the device's part of a launch set (search_round), the per-root sums
+// (search_root_sums) and the loop over rounds (search_invalid).  Costs: a few waves and range
+// MSMs over the failing ranges per round; about four rounds for a batch of ~10^5 sets with a
+// handful of invalid ones.
 static_assert(SX_COUNT <= 32, "lb_engine::sx");
-struct test_job {
-  snode node;
-  std::vector<snode> ch;
-  bool fresh;    // y from the host (a node failing in an earlier round); else from direct check `d`
-  uint32_t src;  // fresh: index into F; else index into D
-  int32_t spec = -1;    // a look-ahead test of child `spec_k` of fresh test `spec` (y: the parent's)
-  uint32_t spec_k = 0;
-};
-}  // namespace
-
-// children of a failing node: direct checks fan out to depth max(d + 1, min(d + 7, L - 6)) so a
-// weighted test of each failing child can reach the leaves; weighted tests to depth d + 6 (<= 64
-// children); a root's members in <= 64 parts for direct checks (one FE each), in <= kWtParts
-// parts for a weighted test (one FE whatever f: a root of up to 1024 sets names its failing set
-// in one round)
-static constexpr uint32_t kWtParts = LB_WT_MAX;
-static uint32_t parts_per(uint32_t len, bool direct) {
-  const uint32_t f = direct ? 64u : kWtParts;
-  return (len + f - 1) / f;
-}
-// look-ahead tests over the parts of a fresh test's roots (device idle), for nodes of at most this many sets
-static constexpr uint32_t kSpecMaxSets = 16384;
-static void search_children(const search_ctx& x, const snode& a, bool direct, std::vector<snode>& out) {
-  out.clear();
-  if (a.kind == 2u || a.len <= 1) return;
-  auto parts = [&](uint32_t u, uint32_t lo, uint32_t len) {
-    const uint32_t per = parts_per(len, direct);
-    for (uint32_t q = 0; q < len; q += per) {
-      const uint32_t l = per < len - q ? per : len - q;
-      if (l == 1 && direct) out.push_back({2u, x.members[lo + q], lo + q, 1u, 0u});
-      else out.push_back({1u, u, lo + q, l, 0u});
-    }
-  };
-  if (a.kind == 1u) return parts(a.key, a.lo, a.len);
-  if (a.d == x.L) return parts(a.key - x.mu, a.lo, a.len);
-  const int d = (int)a.d, L = (int)x.L;
-  // direct children: subtrees of 64 roots (their weighted tests can name one failing root); a
-  // node of <= 64 roots whose weighted test matched nothing (>= 2 failing roots) is checked root by
-  // root in ONE round (halving it instead took up to six rounds for two wrong roots in a subtree)
-  int dd = direct ? (d >= L - 6 ? L : std::max(d + 1, std::min(d + 7, L - 6))) : d + 6;
-  if (dd > L) dd = L;
-  const uint32_t k = (uint32_t)(dd - d), span = (uint32_t)(L - dd);
-  for (uint32_t v = a.key << k; v < (a.key + 1) << k; v++) {
-    const uint32_t ulo = (v - (1u << dd)) << span;
-    if (ulo >= x.nu) break;
-    const uint32_t uhi = std::min(x.nu, ulo + (1u << span));
-    out.push_back({0u, v, x.goff[ulo], x.goff[uhi] - x.goff[ulo], (uint32_t)dd});
-  }
-}
+static_assert(kWtParts == LB_WT_MAX, "lb_search_plan.h kWtParts");
 
 template <class T>
 static hipError_t sx_up(lb_engine* e, int k, const std::vector<T>& v, hipStream_t s) {
@@ -1292,101 +1216,43 @@ static hipError_t sx_up(lb_engine* e, int k, const std::vector<T>& v, hipStream_
   return r;
 }
 
-// One launch set: direct checks D, then weighted tests (fresh ones first).  Outputs the direct
-// verdicts and FE values (144 words each) and each test's matched child (1-based, 0: none).
-static int32_t search_round(lb_engine* e, const search_ctx& x, const std::vector<fnode>& F, const std::vector<snode>& D,
-                            const std::vector<test_job>& tests, uint32_t n_fresh, std::vector<int32_t>& verdict,
-                            std::vector<uint32_t>& ydir, std::vector<int32_t>& tout) {
+// stages run once per search round: their elapsed times join acc_ms (after the round's synchronisation)
+static void stage_accumulate(lb_engine* e, std::initializer_list<int> stages) {
+  if (!e->profiling) return;
+  for (int k : stages) {
+    float ms = 0.f;
+    if (e->used[k] && hipEventElapsedTime(&ms, e->ev0[k], e->ev1[k]) == hipSuccess) e->acc_ms[k] += ms;
+    e->used[k] = false;
+  }
+}
+
+// the bucket MSM's count (scatter = false) or scatter pass over the round's T positions, W windows
+template <int W>
+static void smsm_pass(lb_engine* e, hipStream_t s, bool scatter, uint32_t T, uint32_t cm, const smsm_args& ma) {
+  if (!scatter)
+    hipLaunchKernelGGL(k_smsm_count<W>, dim3(nblk(T)), dim3(LB_TPB), 0, s, T, cm, ma, e->members.as<uint32_t>(),
+                       e->set_uid.as<uint32_t>(), e->scalars.as<uint64_t>(), e->set_live.as<uint32_t>(),
+                       e->sig_inf.as<uint32_t>(), e->bcnt.as<uint32_t>());
+  else
+    hipLaunchKernelGGL(k_smsm_scatter<W>, dim3(nblk(T)), dim3(LB_TPB), 0, s, T, cm, ma, e->members.as<uint32_t>(),
+                       e->set_uid.as<uint32_t>(), e->scalars.as<uint64_t>(), e->set_live.as<uint32_t>(),
+                       e->sig_inf.as<uint32_t>(), e->boff.as<uint32_t>(), e->bcursor.as<uint32_t>(),
+                       e->bmembers.as<uint32_t>());
+}
+
+// One launch set on the device: the columns of `tab` up, the range sums S of its MSM instances,
+// the direct checks, then the weighted tests (fresh ones first).  Outputs the direct verdicts and
+// FE values (144 words each) and each test's matched child (1-based, 0: none).
+static int32_t search_round(lb_engine* e, const search_ctx& x, const launch_set& ls, const search_tab& tab,
+                            std::vector<int32_t>& verdict, std::vector<uint32_t>& ydir, std::vector<int32_t>& tout) {
   hipStream_t s1 = e->stream;
-  const uint32_t c = (uint32_t)D.size(), nt = (uint32_t)tests.size(), n = x.n;
-  std::vector<uint32_t> dk(c), dkey(c), dlo(c), dlen(c), dm(c, 0);
-  std::vector<uint32_t> mlo, mpre{0}, mmode, mwa, mwb;
-  // the same instances over whole roots (root-level form), while every instance is one
-  std::vector<uint32_t> rlo, rpre{0};
-  bool root_level = x.rs;
-  auto msm = [&](uint32_t lo, uint32_t len, uint32_t mode, uint32_t wa, uint32_t wb, const snode* whole) {
-    mlo.push_back(lo);
-    mpre.push_back(mpre.back() + len);
-    mmode.push_back(mode);
-    mwa.push_back(wa);
-    mwb.push_back(wb);
-    if (whole && whole->kind == 0u) {
-      const uint32_t span = x.L - whole->d, ulo = (whole->key - (1u << whole->d)) << span;
-      const uint32_t uhi = std::min(x.nu, ulo + (1u << span));
-      rlo.push_back(ulo);
-      rpre.push_back(rpre.back() + (uhi - ulo));
-    } else {
-      root_level = false;
-    }
-    return (uint32_t)mlo.size() - 1;
-  };
-  for (uint32_t j = 0; j < c; j++) {
-    dk[j] = D[j].kind;
-    dkey[j] = D[j].key;
-    dlo[j] = D[j].lo;
-    dlen[j] = D[j].len;
-    if (D[j].kind != 2u) dm[j] = msm(D[j].lo, D[j].len, 0u, 1u, 0u, &D[j]);
-  }
-  std::vector<uint32_t> tmode(nt), tf(nt), tv0(nt), tu(nt), tm(nt), tyi(nt), tlo(nt), tlen(nt), tper(nt);
-  std::vector<uint32_t> yup((size_t)144 * (n_fresh ? n_fresh : 1));
-  for (uint32_t t = 0; t < nt; t++) {
-    const test_job& T = tests[t];
-    const snode& a = T.node;
-    const snode& c0 = T.ch[0];
-    tf[t] = (uint32_t)T.ch.size();
-    tlo[t] = a.lo;
-    tlen[t] = a.len;
-    tyi[t] = T.src;
-    if (c0.kind == 0u) {  // subtrees of 2^span roots from root ulo0
-      const uint32_t span = x.L - c0.d, ulo0 = (c0.key - (1u << c0.d)) << span;
-      tmode[t] = 1u;
-      tv0[t] = c0.key;
-      tm[t] = msm(a.lo, a.len, 1u, ulo0, span, &a);
-    } else {  // parts of one root
-      const uint32_t per = parts_per(a.len, false);
-      tmode[t] = 2u;
-      tu[t] = c0.key;
-      tper[t] = per;
-      tm[t] = msm(a.lo, a.len, 2u, per, 0u, nullptr);
-    }
-    if (T.fresh) {
-      tyi[t] = t;  // fresh tests come first: y_up element t
-      for (int q = 0; q < 144; q++) yup[(size_t)q * n_fresh + t] = F[T.src].y[q];
-    }
-  }
-  // root-level round: every instance covers whole roots and the per-set form would take the
-  // bucket MSM; the instances then run over the per-root sums S_u (k_rsm_terms)
-  const bool rs_path = root_level && !mlo.empty() && mpre.back() > e->search_small_max;
-  if (rs_path) {
-    mlo.swap(rlo);
-    mpre.swap(rpre);
-  }
-  // weight-1 instances only: 32-bit GLV halves, 4 windows instead of 6
-  const bool w4 = std::all_of(mmode.begin(), mmode.end(), [](uint32_t m) { return m == 0u; });
+  const uint32_t c = (uint32_t)ls.D.size(), nt = (uint32_t)ls.tests.size(), n_fresh = ls.n_fresh, n = x.n;
+  const bool rs_path = tab.rs_path, w4 = tab.w4;
   const uint32_t nwin = w4 ? (uint32_t)LB_MSM_W : (uint32_t)LB_SMSM_W;
-  const uint32_t cm = (uint32_t)mlo.size(), T = mpre.back(), nb = cm * nwin * LB_MSM_B;
+  const uint32_t cm = tab.cm, T = tab.T, nb = cm * nwin * LB_MSM_B;
   const uint32_t schunk = e->search_chunk;
   const uint32_t bcap = (2 * nwin * T) / schunk + nb;
-  LB_HIP(sx_up(e, SX_KIND, dk, s1));
-  LB_HIP(sx_up(e, SX_KEY, dkey, s1));
-  LB_HIP(sx_up(e, SX_LO, dlo, s1));
-  LB_HIP(sx_up(e, SX_LEN, dlen, s1));
-  LB_HIP(sx_up(e, SX_MIDX, dm, s1));
-  LB_HIP(sx_up(e, SX_MPRE, mpre, s1));
-  LB_HIP(sx_up(e, SX_MLO, mlo, s1));
-  LB_HIP(sx_up(e, SX_MMODE, mmode, s1));
-  LB_HIP(sx_up(e, SX_MWA, mwa, s1));
-  LB_HIP(sx_up(e, SX_MWB, mwb, s1));
-  LB_HIP(sx_up(e, SX_TMODE, tmode, s1));
-  LB_HIP(sx_up(e, SX_TF, tf, s1));
-  LB_HIP(sx_up(e, SX_TV0, tv0, s1));
-  LB_HIP(sx_up(e, SX_TU, tu, s1));
-  LB_HIP(sx_up(e, SX_TMIDX, tm, s1));
-  LB_HIP(sx_up(e, SX_TYIDX, tyi, s1));
-  LB_HIP(sx_up(e, SX_TLO, tlo, s1));
-  LB_HIP(sx_up(e, SX_TLEN, tlen, s1));
-  LB_HIP(sx_up(e, SX_TPER, tper, s1));
-  LB_HIP(sx_up(e, SX_YUP, yup, s1));
+  for (int k : kSxUploads) LB_HIP(sx_up(e, k, tab.col[k], s1));
   const uint32_t N = c + nt;
   LB_HIP(e->sx[SX_VERDICT].ensure((c ? c : 1) * 4));
   LB_HIP(e->sx[SX_Y].ensure((size_t)(N ? N : 1) * 576));
@@ -1398,23 +1264,17 @@ static int32_t search_round(lb_engine* e, const search_ctx& x, const std::vector
   auto U = [&](int k) { return e->sx[k].as<uint32_t>(); };
   {
     stage_scope sc(e, ST_FALLBACK, s1);
+    const smsm_args ma{U(SX_MPRE), U(SX_MLO), U(SX_MMODE), U(SX_MWA), U(SX_MWB)};
     if (cm && T && (rs_path || T <= e->search_small_max)) {
       // small or root-level round: per-position terms + per-instance segmented sums (no bucket MSM)
-      std::vector<uint32_t> blo, bhi, bo{0};
-      for (uint32_t j = 0; j < cm; j++) {
-        for (uint32_t p = mpre[j]; p < mpre[j + 1]; p += 64) {
-          blo.push_back(p);
-          bhi.push_back(std::min(p + 64, mpre[j + 1]));
-        }
-        bo.push_back((uint32_t)blo.size());
-      }
+      std::vector<uint32_t> blo, bhi, bo;
+      blocks64(tab.col[SX_MPRE].data(), cm, blo, bhi, bo);
       const uint32_t nbk = (uint32_t)blo.size();
       LB_HIP(sx_up(e, SX_BLO, blo, s1));
       LB_HIP(sx_up(e, SX_BHI, bhi, s1));
       LB_HIP(sx_up(e, SX_BO, bo, s1));
       LB_HIP(e->s_terms.ensure((size_t)T * sizeof(g2j)));
       LB_HIP(e->s_part.ensure((size_t)(nbk ? nbk : 1) * sizeof(g2j)));
-      const smsm_args ma{U(SX_MPRE), U(SX_MLO), U(SX_MMODE), U(SX_MWA), U(SX_MWB)};
       if (rs_path)
         hipLaunchKernelGGL(k_rsm_terms, dim3(nblk(T)), dim3(LB_TPB), 0, s1, T, cm, ma, e->s_root.as<uint32_t>(), x.nu,
                            e->s_terms.as<uint32_t>());
@@ -1445,32 +1305,12 @@ static int32_t search_round(lb_engine* e, const search_ctx& x, const std::vector
       LB_HIP(e->bsum.ensure((size_t)nb * sizeof(g2j)));
       LB_HIP(hipMemsetAsync(e->bcnt.p, 0, (size_t)nb * 4, s1));
       LB_HIP(hipMemsetAsync(e->bcursor.p, 0, (size_t)nb * 4, s1));
-      const smsm_args ma{U(SX_MPRE), U(SX_MLO), U(SX_MMODE), U(SX_MWA), U(SX_MWB)};
-      if (T) {
-        if (w4)
-          hipLaunchKernelGGL(k_smsm_count<LB_MSM_W>, dim3(nblk(T)), dim3(LB_TPB), 0, s1, T, cm, ma,
-                             e->members.as<uint32_t>(), e->set_uid.as<uint32_t>(), e->scalars.as<uint64_t>(),
-                             e->set_live.as<uint32_t>(), e->sig_inf.as<uint32_t>(), e->bcnt.as<uint32_t>());
-        else
-          hipLaunchKernelGGL(k_smsm_count<LB_SMSM_W>, dim3(nblk(T)), dim3(LB_TPB), 0, s1, T, cm, ma,
-                             e->members.as<uint32_t>(), e->set_uid.as<uint32_t>(), e->scalars.as<uint64_t>(),
-                             e->set_live.as<uint32_t>(), e->sig_inf.as<uint32_t>(), e->bcnt.as<uint32_t>());
-      }
+      const auto pass = w4 ? smsm_pass<LB_MSM_W> : smsm_pass<LB_SMSM_W>;
+      if (T) pass(e, s1, false, T, cm, ma);
       hipLaunchKernelGGL(k_msg_scan, dim3(1), dim3(1024), 0, s1, nullptr, nb, schunk, e->bcnt.as<uint32_t>(),
                          e->boff.as<uint32_t>(), e->bch.as<uint32_t>(), e->bchunk_beg.as<uint32_t>(),
                          e->bchunk_end.as<uint32_t>(), nullptr);
-      if (T) {
-        if (w4)
-          hipLaunchKernelGGL(k_smsm_scatter<LB_MSM_W>, dim3(nblk(T)), dim3(LB_TPB), 0, s1, T, cm, ma,
-                             e->members.as<uint32_t>(), e->set_uid.as<uint32_t>(), e->scalars.as<uint64_t>(),
-                             e->set_live.as<uint32_t>(), e->sig_inf.as<uint32_t>(), e->boff.as<uint32_t>(),
-                             e->bcursor.as<uint32_t>(), e->bmembers.as<uint32_t>());
-        else
-          hipLaunchKernelGGL(k_smsm_scatter<LB_SMSM_W>, dim3(nblk(T)), dim3(LB_TPB), 0, s1, T, cm, ma,
-                             e->members.as<uint32_t>(), e->set_uid.as<uint32_t>(), e->scalars.as<uint64_t>(),
-                             e->set_live.as<uint32_t>(), e->sig_inf.as<uint32_t>(), e->boff.as<uint32_t>(),
-                             e->bcursor.as<uint32_t>(), e->bmembers.as<uint32_t>());
-      }
+      if (T) pass(e, s1, true, T, cm, ma);
       hipLaunchKernelGGL(k_msm_chunks, dim3(nblk(bcap)), dim3(LB_TPB), 0, s1, e->bch.as<uint32_t>(),
                          e->bchunk_beg.as<uint32_t>(), e->bchunk_end.as<uint32_t>(), e->bmembers.as<uint32_t>(),
                          e->sig_aos.as<uint4>(), bcap, e->bacc.as<uint32_t>(), nb);
@@ -1515,12 +1355,7 @@ static int32_t search_round(lb_engine* e, const search_ctx& x, const std::vector
   }
   if (nt) LB_HIP(hipMemcpyAsync(tout.data(), e->sx[SX_TOUT].p, (size_t)nt * 4, hipMemcpyDeviceToHost, s1));
   LB_HIP(hipStreamSynchronize(s1));
-  if (e->profiling)
-    for (int k : {(int)ST_FALLBACK, (int)ST_BISECT}) {
-      float ms = 0.f;
-      if (e->used[k] && hipEventElapsedTime(&ms, e->ev0[k], e->ev1[k]) == hipSuccess) e->acc_ms[k] += ms;
-      e->used[k] = false;
-    }
+  stage_accumulate(e, {ST_FALLBACK, ST_BISECT});
   return LB_OK;
 }
 
@@ -1531,17 +1366,9 @@ static int32_t search_round(lb_engine* e, const search_ctx& x, const std::vector
 static int32_t search_root_sums(lb_engine* e, const search_ctx& x) {
   hipStream_t s1 = e->stream;
   const uint32_t n = x.n, nu = x.nu;
-  std::vector<uint32_t> idx;  // blo[nbk] | bhi[nbk] | bo[nu + 1]
-  std::vector<uint32_t> blo, bhi, bo{0};
-  for (uint32_t u = 0; u < nu; u++) {
-    for (uint32_t p = x.goff[u]; p < x.goff[u + 1]; p += 64) {
-      blo.push_back(p);
-      bhi.push_back(std::min(p + 64, x.goff[u + 1]));
-    }
-    bo.push_back((uint32_t)blo.size());
-  }
-  const uint32_t nbk = (uint32_t)blo.size();
-  idx.insert(idx.end(), blo.begin(), blo.end());
+  std::vector<uint32_t> idx, bhi, bo;  // idx: blo[nbk] | bhi[nbk] | bo[nu + 1]
+  blocks64(x.goff.data(), nu, idx, bhi, bo);
+  const uint32_t nbk = (uint32_t)idx.size();
   idx.insert(idx.end(), bhi.begin(), bhi.end());
   idx.insert(idx.end(), bo.begin(), bo.end());
   LB_HIP(e->rs_idx.ensure(idx.size() * 4));
@@ -1563,17 +1390,12 @@ static int32_t search_root_sums(lb_engine* e, const search_ctx& x) {
   }
   LB_HIP(hipGetLastError());
   LB_HIP(hipStreamSynchronize(s1));
-  if (e->profiling) {
-    float ms = 0.f;
-    if (e->used[ST_FALLBACK] && hipEventElapsedTime(&ms, e->ev0[ST_FALLBACK], e->ev1[ST_FALLBACK]) == hipSuccess)
-      e->acc_ms[ST_FALLBACK] += ms;
-    e->used[ST_FALLBACK] = false;
-  }
+  stage_accumulate(e, {ST_FALLBACK});
   return LB_OK;
 }
 
 static int32_t search_invalid(lb_engine* e, lb_batch* b, uint32_t mu, int32_t* out_job) {
-  const uint32_t n = b->n_sets, nj = b->n_jobs;
+  const uint32_t n = b->n_sets;
   search_ctx x;
   x.n = n;
   x.mu = mu;
@@ -1594,158 +1416,30 @@ static int32_t search_invalid(lb_engine* e, lb_batch* b, uint32_t mu, int32_t* o
     if (st != LB_OK) return st;
     x.rs = true;
   }
-  std::vector<fnode> F{root};
+  std::vector<fnode> F{root}, work;
   std::vector<uint32_t> bad_pos;
-  auto condemn = [&](const snode& a) {
-    for (uint32_t q = 0; q < a.len; q++) bad_pos.push_back(a.lo + q);
-  };
   const bool trace = std::getenv("LB_SEARCH_TRACE") != nullptr;
-  const size_t kMaxMsm = 1024;  // MSM instances per launch set (1280 buckets each)
-  std::vector<snode> ch;
   for (int round = 1; !F.empty(); round++) {
-    if (round > 64) {  // depth is bounded far below this; fail closed if it is ever exceeded
-      for (const fnode& f : F) condemn(f.s);
-      break;
-    }
     std::vector<fnode> next;
-    // settle single-child chains and terminals on the host
-    std::vector<fnode> work;
-    for (fnode& f : F) {
-      while (true) {
-        if (f.s.len <= 1) {
-          bad_pos.push_back(f.s.lo);
-          break;
-        }
-        search_children(x, f.s, f.multi, ch);
-        if (ch.size() == 1) {
-          f.s = ch[0];
-          f.multi = false;
-          continue;
-        }
-        if (ch.empty()) condemn(f.s);
-        else work.push_back(f);
-        break;
-      }
-    }
+    search_settle(x, round, F, work, bad_pos);
     const bool spec_on = device_alone(e);
     for (size_t a = 0; a < work.size();) {
-      // a launch set: whole failing nodes until the MSM instance budget is reached
-      std::vector<fnode> Fs;
-      std::vector<snode> D;
-      std::vector<uint32_t> d_owner;  // D index -> Fs index
-      std::vector<test_job> fresh, spec, ahead;
-      size_t inst = 0;
-      while (a < work.size() && (Fs.empty() || inst < kMaxMsm)) {
-        const fnode& f = work[a++];
-        const uint32_t fi = (uint32_t)Fs.size();
-        Fs.push_back(f);
-        if (!f.multi) {
-          test_job t{f.s, {}, true, fi};
-          search_children(x, f.s, false, t.ch);
-          // a weighted test over <= 64 ROOTS: in the same round, a weighted test over each root's
-          // parts, matched against the node's own y (if the node's test names root k, root k is the
-          // node's one failing child and y_k = y).  The named root's test then names the set, one
-          // round earlier; the other roots' tests are discarded.  Only while the device runs no
-          // other batch: under load their Miller loops and final exponentiations cost more than
-          // the round they save (profiles/r3_search_spec_ab.txt).
-          if (spec_on && !t.ch.empty() && t.ch[0].kind == 0u && t.ch[0].d == x.L && f.s.len <= kSpecMaxSets)
-            for (uint32_t k = 0; k < (uint32_t)t.ch.size(); k++) {
-              test_job g{t.ch[k], {}, true, fi};
-              search_children(x, t.ch[k], false, g.ch);
-              if (g.ch.size() < 2) continue;
-              g.spec = (int32_t)fresh.size();
-              g.spec_k = k;
-              spec.push_back(std::move(g));
-              inst++;
-            }
-          fresh.push_back(std::move(t));
-          inst++;
-          continue;
-        }
-        std::vector<snode> dch;
-        search_children(x, f.s, true, dch);
-        for (const snode& c : dch) {
-          const uint32_t di = (uint32_t)D.size();
-          D.push_back(c);
-          d_owner.push_back(fi);
-          inst += c.kind != 2u;
-          test_job t{c, {}, false, di};
-          search_children(x, c, false, t.ch);
-          if (t.ch.size() >= 2 && !(r1_plain && round == 1)) {
-            ahead.push_back(std::move(t));
-            inst++;
-          }
-        }
-      }
-      std::vector<test_job> tests(fresh);
-      const uint32_t n_own = (uint32_t)fresh.size();
-      tests.insert(tests.end(), spec.begin(), spec.end());  // fresh too: y from the host
-      const uint32_t n_fresh = (uint32_t)tests.size();
-      tests.insert(tests.end(), ahead.begin(), ahead.end());
+      const launch_set ls = search_launch_set(x, work, a, spec_on, r1_plain, round);
       std::vector<int32_t> verdict, tout;
       std::vector<uint32_t> ydir;
       const auto t0 = std::chrono::steady_clock::now();
-      const int32_t st = search_round(e, x, Fs, D, tests, n_fresh, verdict, ydir, tout);
+      const search_tab tab = search_tables(x, ls.Fs, ls.D, ls.tests, ls.n_fresh, e->search_small_max);
+      const int32_t st = search_round(e, x, ls, tab, verdict, ydir, tout);
       if (st != LB_OK) return st;
       if (trace)
         std::fprintf(stderr, "[lb search] round %d: %zu failing nodes, %zu direct checks, %zu weighted tests: %.3f ms\n",
-                     round, Fs.size(), D.size(), tests.size(),
+                     round, ls.Fs.size(), ls.D.size(), ls.tests.size(),
                      std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
-      // fresh tests: the named child (or, by its look-ahead test, the named child's named part),
-      // or the node again with its children to check directly
-      std::vector<int32_t> spec_of;  // (own test, child) -> look-ahead test
-      std::vector<uint32_t> spec_base(n_own + 1, 0);
-      for (uint32_t t = n_own; t < n_fresh; t++) spec_base[tests[t].spec + 1]++;
-      for (uint32_t t = 0; t < n_own; t++) spec_base[t + 1] += spec_base[t];
-      for (uint32_t t = n_own; t < n_fresh; t++) spec_of.push_back((int32_t)t);  // grouped by own test, child order
-      for (uint32_t t = 0; t < n_own; t++) {
-        const fnode& f = Fs[tests[t].src];
-        const int k = tout[t];
-        if (k < 1 || (size_t)k > tests[t].ch.size()) {
-          next.push_back({f.s, true, f.y});
-          continue;
-        }
-        int32_t st = -1;
-        for (uint32_t q = spec_base[t]; q < spec_base[t + 1]; q++)
-          if (tests[spec_of[q]].spec_k == (uint32_t)(k - 1)) st = spec_of[q];
-        if (st < 0) {
-          next.push_back({tests[t].ch[k - 1], false, f.y});
-          continue;
-        }
-        const int k2 = tout[st];
-        if (k2 >= 1 && (size_t)k2 <= tests[st].ch.size()) next.push_back({tests[st].ch[k2 - 1], false, f.y});
-        else next.push_back({tests[t].ch[k - 1], true, f.y});
-      }
-      // direct checks: each failing child goes on by its weighted test
-      std::vector<int> any_fail(Fs.size(), 0);
-      std::vector<int32_t> ahead_of(D.size(), -1);
-      for (uint32_t t = n_fresh; t < tests.size(); t++) ahead_of[tests[t].src] = (int32_t)t;
-      for (uint32_t j = 0; j < D.size(); j++) {
-        if (verdict[j]) continue;
-        any_fail[d_owner[j]] = 1;
-        std::vector<uint32_t> yc(144);  // y_out is SoA with stride c: gather this node's 144 words
-        for (int q = 0; q < 144; q++) yc[q] = ydir[(size_t)q * (D.size() + tests.size()) + j];
-        const int32_t t = ahead_of[j];
-        if (t < 0) {
-          next.push_back({D[j], false, yc});  // terminal or a single child: settled next round
-          continue;
-        }
-        const int k = tout[t];
-        if (k >= 1 && (size_t)k <= tests[t].ch.size()) next.push_back({tests[t].ch[k - 1], false, yc});
-        else next.push_back({D[j], true, yc});
-      }
-      // fail closed: a multi node none of whose children fails (impossible for exact arithmetic)
-      for (size_t fi = 0; fi < Fs.size(); fi++)
-        if (Fs[fi].multi && !any_fail[fi]) condemn(Fs[fi].s);
+      search_interpret(ls, verdict, ydir, tout, next, bad_pos);
     }
     F.swap(next);
   }
-  // failing sets -> their jobs (set_live makes every failing set belong to a live job)
-  for (uint32_t pos : bad_pos) {
-    const uint32_t i = x.members[pos];
-    const uint32_t j = (uint32_t)(std::upper_bound(b->job_off.begin(), b->job_off.end(), i) - b->job_off.begin()) - 1;
-    if (j < nj && out_job[j] == 1) out_job[j] = 0;
-  }
+  search_jobs(x, bad_pos, b->job_off, b->n_jobs, out_job);
   return LB_OK;
 }
 

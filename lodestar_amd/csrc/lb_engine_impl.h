@@ -1,5 +1,6 @@
-// What the two host units of the library share (lb_engine.hip: the BLS pipeline, the invalid-set
-// search and the small helper calls; lb_kzg_host.hip: the KZG calls): the device buffer, the engine
+// What the two host units of the library share (lb_engine.hip: the BLS pipeline, the device side
+// and the loop of the invalid-set search, whose planning is the device-free lb_search_plan.h, and
+// the small helper calls; lb_kzg_host.hip: the KZG calls): the device buffer, the engine
 // and its KZG state, the HIP error macro and the generic "inputs up, one launch, outputs back"
 // runner.  Host-only and not part of the public ABI (include/lodestar_bls.h).  Nothing here sits
 // in an anonymous namespace: lb_engine must be one type in both units.
@@ -108,15 +109,15 @@ struct lb_engine {
   hipStream_t stream = nullptr;   // s1
   hipStream_t stream2 = nullptr;  // s2
   hipStream_t stream3 = nullptr;  // s3: pubkey aggregation + blinding, beside the signature decode
-  hipEvent_t ev_g1 = nullptr, ev_s = nullptr, ev_fork = nullptr, ev_dec = nullptr, ev_pk = nullptr;
+  hipEvent_t ev_s = nullptr, ev_fork = nullptr, ev_dec = nullptr, ev_pk = nullptr;
   hipEvent_t ev_pkst = nullptr;  // the pubkey statuses (k_pk_blind mode 1), before the ladder
   // small batches alone (round 6): the decoded signatures (s2) -> r_i sig_i on s3 beside the
   // subgroup check (ev_sdec), and the terms ready for the sum on s2 (ev_sblind)
   hipEvent_t ev_sdec = nullptr, ev_sblind = nullptr;
   std::mutex mu;
   // workspace
-  dbuf scalars, sig_aff, sig_inf, sig_status, q, h_aff, rpk, rsig, pk_status, ml, treeP, treeS, job_status,
-      nodes, verdict, parts, ok, chunk_acc, chunk_status, fS;
+  dbuf scalars, sig_aff, sig_inf, sig_status, q, h_aff, rpk, pk_status, treeP, treeS, job_status, verdict,
+      parts, ok, chunk_acc, chunk_status, fS;
   // message grouping (k_msg_*, k_gsum_*)
   dbuf msg_tab, rep_of, uid_of, uniq_set, n_u, set_uid, gcnt, gpos, goff, gch, chunk_beg, chunk_end, members,
       set_live, gacc, gp_aff, gp_inf, chunk_root;
@@ -139,7 +140,7 @@ struct lb_engine {
   // k_msm_horner_g8); LB_MSM_G8=0: the lone-lane kernels (k_msm_buckets, k_msm_reduce)
   bool msm_g8 = true;
   // invalid-set search (search_invalid): node descriptors and per-node results
-  dbuf sx[32];   // search round buffers (search_invalid: SX_*)
+  dbuf sx[32];   // search round buffers (lb_search_plan.h SX_*)
   dbuf pk_aff;  // affine aggregate pubkey per set (single-set checks of the search)
   dbuf y_root;  // FE value of the root check (the search starts from it)
   uint64_t msg_key = 0;  // keyed probe hash (CSPRNG)

@@ -2062,7 +2062,7 @@ __global__ void __launch_bounds__(8 * LB_SUM_G8_GROUPS) k_g2_sum_g8(uint32_t n, 
 // both 32-bit GLV halves of r_i w stay below 2^(32 + LB_WT_BITS) <= 2^48: LB_SMSM_W = 6 windows
 // of 8 bits, instance j owning buckets [j LB_SMSM_NB, (j+1) LB_SMSM_NB).  A round of weight-1
 // instances only (the first round's direct checks) takes LB_MSM_W = 4 windows (32-bit halves).
-#define LB_WT_MAX 1024  // children of a weighted test over parts of one root (lb_engine.hip kWtParts)
+#define LB_WT_MAX 1024  // children of a weighted test over parts of one root (lb_search_plan.h kWtParts)
 #define LB_WT_BITS 11
 #define LB_SMSM_W 6
 #define LB_SMSM_NB (LB_SMSM_W * LB_MSM_B)

@@ -642,6 +642,65 @@ def test_search_term_forms_trace_the_same_rounds(monkeypatch, capfd):
     assert traces[0] and traces[0] == traces[1], traces
 
 
+_TRACE_BATCHES = {}
+
+
+def _trace_batch(engine, name):
+    """(jobs, each set's root numbered by first occurrence, the planted sets) of the named batch, made once"""
+    if name not in _TRACE_BATCHES:
+        n_sets, n_msgs, seed, pick = {"one": (96, 70, 41, lambda r: [50]),
+                                      # two sets of the root that has the most
+                                      "same_root": (300, 2, 42, lambda r: np.nonzero(r == np.bincount(r).argmax())[0][[3, -2]]),
+                                      # roots 2 and 45 share the first 64-root subtree, the last root is in another
+                                      "subtree": (200, 130, 43, lambda r: [np.nonzero(r == u)[0][0] for u in (2, 45, r.max())])}[name]
+        valid = make_shared_batch(engine, n_sets, n_msgs, seed=seed)
+        seen = {}
+        roots = np.array([seen.setdefault(j[0].signing_root, len(seen)) for j in valid], dtype=np.uint32)
+        assert name != "subtree" or roots.max() >= 64
+        bad = sorted(int(i) for i in pick(roots))
+        _TRACE_BATCHES[name] = (make_shared_batch(engine, n_sets, n_msgs, seed=seed, invalid=bad), roots, bad)
+    return _TRACE_BATCHES[name]
+
+
+@pytest.mark.parametrize("alone", ["0", "1"])
+@pytest.mark.parametrize("name,knobs", [("one", {}), ("same_root", {}), ("subtree", {}),
+                                        ("subtree", {"LB_SEARCH_SMALL_MAX": "0"}),
+                                        ("subtree", {"LB_SEARCH_SMALL_MAX": "0", "LB_SEARCH_BLOCKS": "0"})])
+def test_search_trace_matches_plan_model(engine, monkeypatch, capfd, name, knobs, alone):
+    """The search's planner and interpreter are device-free (lb_search_plan.h) and run on the CPU against a
+    model device (tests/harness/search_model.h, tests/test_search_plan_cpu.py).  Here the model predicts
+    the device: with the roots in input order (LB_ROOT_SHUFFLE=0) and the look-ahead tests pinned on or
+    off (LB_ALONE), every LB_SEARCH_TRACE line's failing nodes, direct checks and weighted tests equal the
+    model's for the same layout.  96 sets over 70 roots with one wrong set (subtree descent); 300 sets over
+    2 roots with two wrong sets in one root (parts of a root, a multi node); 200 sets over 130 roots with
+    three wrong sets, two of them in one 64-root subtree -- also through the bucket MSM after a plain first
+    round (LB_SEARCH_SMALL_MAX=0) and over the per-root sums (and LB_SEARCH_BLOCKS=0)."""
+    import re
+    import test_search_plan_cpu as SP
+    from lodestar_amd.engine import Engine
+    jobs, roots, bad = _trace_batch(engine, name)
+    monkeypatch.setenv("LB_ROOT_SHUFFLE", "0")
+    monkeypatch.setenv("LB_SEARCH_TRACE", "1")
+    monkeypatch.setenv("LB_ALONE", alone)
+    for k, v in knobs.items():
+        monkeypatch.setenv(k, v)
+    capfd.readouterr()
+    with Engine(0) as e:
+        codes = e.verify_jobs(jobs)
+    err = capfd.readouterr().err
+    assert [i for i, c in enumerate(codes) if c != 1] == bad
+    got = [[int(v) for v in m.groups()] for m in re.finditer(
+        r"\[lb search\] round (\d+): (\d+) failing nodes, (\d+) direct checks, (\d+) weighted tests", err)]
+    # the forms search_invalid picks from the engine's knobs
+    n, nu, small_max = len(roots), int(roots.max()) + 1, int(knobs.get("LB_SEARCH_SMALL_MAX", 32768))
+    large = nu > 1 and n > small_max
+    r1_plain = large and knobs.get("LB_SEARCH_BLOCKS", "1") != "0"
+    flags = (SP.SPEC if alone == "1" else 0) | (SP.R1_PLAIN if r1_plain else 0) | (SP.RS if large and not r1_plain else 0)
+    found, trace, _ = SP.run(SP.load(), roots, bad, flags=flags, small_max=small_max)
+    assert sorted(found) == bad
+    assert got == [row[:4] for row in trace], (got, trace)
+
+
 def test_aggregate_signatures_golden(engine):
     """bls.Signature.aggregate on the GPU against the oracle's golden
     groups: sums (with duplicates, cancellation to infinity, infinity members), the first bad
