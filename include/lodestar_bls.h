@@ -365,6 +365,23 @@ int32_t lb_kzg_verify_blob_proof_batch(lb_engine* e, uint32_t n_groups,
  * zeroed, the other blobs are unaffected.  Returns LB_OK whenever the call ran (n_blobs == 0: at once,
  * nothing read); LB_ERR_ARGUMENT for no 4096-point setup, a needed pointer that is NULL or
  * n_blobs > 128.  It pairs against nothing: a setup loaded with two G2 points will do.
+ *
+ * lb_kzg_recover_cells_and_proofs (ckzg.recoverCellsAndKzgProofs) for n_blobs <= 128 blobs: blob b is
+ * given by cells cell_offsets[b] .. cell_offsets[b + 1] - 1 of the flat arrays, any 64 .. 128 of its
+ * 128 cells with their indices strictly ascending.  out_cells[b] = all 128 cells and out_proofs48[b] =
+ * all 128 proofs, the bytes lb_kzg_compute_cells_and_proofs gives for the blob: the scalar-field
+ * erasure decode runs as 64 independent decodes of size 128 per blob on the device, every output
+ * cell is recomputed from the recovered coefficients (none is copied from the input), and the proofs
+ * come from the same FK20 pass.  out_status[b] = LB_OK, LB_BAD_SCALAR for a cell element >= r, or
+ * LB_VERIFY_FAIL when the given cells lie on no polynomial of degree < 4096 (possible only with more
+ * than 64 cells; this is STRICTER than c-kzg, which returns cells of some other polynomial there);
+ * LB_BAD_SCALAR comes first.  A rejected blob's cells and proofs are zeroed, the other blobs are
+ * unaffected.  Returns LB_OK whenever the call ran (n_blobs == 0: at once, nothing read);
+ * LB_ERR_ARGUMENT, with nothing launched, for no 4096-point setup, a needed pointer that is NULL,
+ * n_blobs > 128, cell_offsets[0] != 0, decreasing offsets, a blob with fewer than 64 or more than 128
+ * cells, an index >= 128 or indices of a blob that do not strictly ascend (the spec's sorted and
+ * no-duplicates checks).  One stream synchronisation (after the FK20 table's first build); it pairs
+ * against nothing: a setup loaded with two G2 points will do.
  */
 int32_t lb_kzg_compute_cells(lb_engine* e, uint32_t n_blobs, const uint8_t* blobs, /* n_blobs x 131072 B */
                              uint8_t* out_cells,                                  /* n_blobs x 128 x 2048 B */
@@ -383,6 +400,13 @@ int32_t lb_kzg_compute_cells_and_proofs(lb_engine* e, uint32_t n_blobs, const ui
                                         uint8_t* out_cells,    /* n x 128 x 2048 B */
                                         uint8_t* out_proofs48, /* n x 128 x 48 B   */
                                         int32_t* out_status);  /* n */
+int32_t lb_kzg_recover_cells_and_proofs(lb_engine* e, uint32_t n_blobs,
+                                        const uint32_t* cell_offsets, /* n_blobs + 1 prefix sums over the given cells */
+                                        const uint32_t* cell_indices, /* one per given cell, < 128 */
+                                        const uint8_t* cells,         /* cell_offsets[n] x 2048 B */
+                                        uint8_t* out_cells,           /* n x 128 x 2048 B */
+                                        uint8_t* out_proofs48,        /* n x 128 x 48 B   */
+                                        int32_t* out_status);         /* n */
 
 /*
  * Synthetic-data helpers for tests and the benchmark (not on the verification path):

@@ -83,6 +83,7 @@ SIGNATURES = {
     "lb_kzg_compute_cell_proofs": (ctypes.c_int32, [_vp, _u8p, ctypes.c_uint32, _u32p, _u8p, _i32p]),
     "lb_kzg_verify_cell_proof_batch": (ctypes.c_int32, [_vp, ctypes.c_uint32, _u32p, _u8p, _u32p, _u8p, _u8p, _i32p]),
     "lb_kzg_compute_cells_and_proofs": (ctypes.c_int32, [_vp, ctypes.c_uint32, _u8p, _u8p, _u8p, _i32p]),
+    "lb_kzg_recover_cells_and_proofs": (ctypes.c_int32, [_vp, ctypes.c_uint32, _u32p, _u32p, _u8p, _u8p, _u8p, _i32p]),
     "lb_sk_to_pk": (ctypes.c_int32, [_vp, ctypes.c_uint32, _u8p, _u8p, _u8p]),
     "lb_sign": (ctypes.c_int32, [_vp, ctypes.c_uint32, _u8p, _u8p, _u8p]),
     "lb_pubkey_table_append": (ctypes.c_int32, [_vp, ctypes.c_uint32, _u8p, ctypes.c_uint32, ctypes.c_int32, _i32p,

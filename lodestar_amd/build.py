@@ -127,6 +127,7 @@ KZG_BATCH_HARNESS = os.path.join(ROOT, "build", "lb_kzg_batch_harness.so")
 KZG_BLOB_HARNESS = os.path.join(ROOT, "build", "lb_kzg_blob_harness.so")
 KZG_CELLS_HARNESS = os.path.join(ROOT, "build", "lb_kzg_cells_harness.so")
 KZG_FK20_HARNESS = os.path.join(ROOT, "build", "lb_kzg_fk20_harness.so")
+KZG_RECOVER_HARNESS = os.path.join(ROOT, "build", "lb_kzg_recover_harness.so")
 SEARCH_HARNESS = os.path.join(ROOT, "build", "lb_search_harness.so")
 
 
@@ -169,6 +170,14 @@ def build_kzg_fk20_harness(force=False, verbose=True):
     points, of the FK20 call on the CPU (tests/test_kzg_fk20_cpu.py)"""
     return _build_so(os.path.join(HDIR, "lb_kzg_fk20_harness.cpp"), KZG_FK20_HARNESS,
                      [os.path.join(HDIR, "kzg_fk20_lanes.h"), FR_VIEWS], ("-O2", "-std=c++17"), force, verbose)
+
+
+def build_kzg_recover_harness(force=False, verbose=True):
+    """the slot map, the vanishing polynomial's values, the column decode and the blob's elements from
+    its coefficients of the recovery call, and its argument check, on the CPU (tests/test_kzg_recover_cpu.py)"""
+    return _build_so(os.path.join(HDIR, "lb_kzg_recover_harness.cpp"), KZG_RECOVER_HARNESS,
+                     [os.path.join(HDIR, "kzg_recover_lanes.h"), os.path.join(HDIR, "kzg_fk20_lanes.h"), FR_VIEWS],
+                     ("-O2", "-std=c++17"), force, verbose)
 
 
 def build_search_harness(force=False, verbose=True):
@@ -233,6 +242,7 @@ def build_all(force=False):
     build_kzg_blob_harness(force)
     build_kzg_cells_harness(force)
     build_kzg_fk20_harness(force)
+    build_kzg_recover_harness(force)
     build_search_harness(force)
     build_cpu_pool(force)
     build_ubench(force)

@@ -8,6 +8,7 @@
 #pragma once
 #include "lb_fr.h"
 #include "lb_kernels.h"
+#include "lb_recover.h"
 
 #define LB_FR_N 4096u        // FIELD_ELEMENTS_PER_BLOB
 #define LB_FR_LOGN 12
@@ -340,5 +341,112 @@ __global__ void __launch_bounds__(64) k_fr_cell_quotient(uint32_t n_cells, const
   const fr_gtable W{tab + (size_t)8 * LB_FR_CELL_TAB_WINV};
   fr_cell_quotient_lane(fr_gpoly{coef}, LB_FR_N, W(fr_cell_h64_index(cell_index[c] & (LB_FR_CELLS - 1u))), threadIdx.x,
                         q_le + (size_t)c * LB_FR_N * 8);
+}
+#endif  // LB_KG
+
+// ------------------------------------------------------------------ cell recovery (lb_recover.h)
+// lb_kzg_recover_cells_and_proofs: from k_fr_cell_interp's output (unit weights) to the blob's
+// coefficients.  fk: the table of fk_tables, tab: the table of fr_cell_tables; the shift s is w = tab's
+// w^1, so s^k and s^-k are its w^j and w^-m entries.  mask: LB_RC_MASK_WORDS words per blob, bit i set
+// where cell i is given (built by the host from the validated indices).
+// 128 slots in LDS, limb-major (fr_lds_vec), with the arithmetic fk_fft_stage asks of its accessor
+struct fr_lds_slots : fr_lds_vec {
+  __device__ __forceinline__ fr add(const fr& u, const fr& v) const { return fr_add(u, v); }
+  __device__ __forceinline__ fr sub(const fr& u, const fr& v) const { return fr_sub(u, v); }
+};
+// w^k v by one field product; tw: 64 Montgomery values
+struct fr_gmulw {
+  const uint32_t* tw;
+  __device__ __forceinline__ fr operator()(const fr& v, uint32_t k) const { return fr_mul(v, fr_ldg(tw + (size_t)8 * k)); }
+};
+
+// One wave per blob: Zev[m] = Z(w128^m) and 1 / Zc[m] = 1 / Z(w w128^m), m < 128, for the vanishing
+// polynomial Z of the blob's missing cells, at zev / zcinv + (128 b + m) * 8 (Montgomery).
+#if LB_KG(16)
+__global__ void __launch_bounds__(64) k_fr_recover_zero(uint32_t n_blobs, const uint32_t* __restrict__ mask, const uint32_t* __restrict__ fk,
+                                                        const uint32_t* __restrict__ tab, uint32_t* __restrict__ zev,
+                                                        uint32_t* __restrict__ zcinv) {
+  const uint32_t b = blockIdx.x;
+  if (b >= n_blobs) return;
+  uint32_t mk[LB_RC_MASK_WORDS];
+  LB_UNROLL for (uint32_t w = 0; w < LB_RC_MASK_WORDS; w++) mk[w] = mask[b * LB_RC_MASK_WORDS + w];
+  rc_zero_lane(mk, fr_gtable{fk + (size_t)8 * LB_FK_TAB_FWD_MONT}, fr_ldg(tab + (size_t)8 * (LB_FR_CELL_TAB_SCALE + 1u)), threadIdx.x,
+               zev + (size_t)b * LB_FK_N * 8, zcinv + (size_t)b * LB_FK_N * 8);
+}
+#endif  // LB_KG
+
+// One wave per (blob, column): blockIdx.x = 64 b + r, two points per lane as in k_fr_fk_cols.  cells:
+// the call's n_cells interpolated cells (64 Montgomery values each), blob b's being off[b] ..
+// off[b + 1] - 1 in ascending cell order (a position past n_cells reads cell n_cells - 1: nothing is
+// indexed out of the buffer).  The column's 64 coefficients go to coef + (4096 b + 64 k + r) * 8
+// (Montgomery, k_fr_fk_cols' and k_fr_ntt4096's input); a non-zero upper half stores LB_VERIFY_FAIL
+// into status[b] (zeroed by the caller; plain stores of one code as in k_fr_blob_load).
+#if LB_KG(16)
+__global__ void __launch_bounds__(64) k_fr_recover_cols(uint32_t n_blobs, const uint32_t* __restrict__ cells, uint32_t n_cells,
+                                                        const uint32_t* __restrict__ off, const uint32_t* __restrict__ mask,
+                                                        const uint32_t* __restrict__ zev, const uint32_t* __restrict__ zcinv,
+                                                        const uint32_t* __restrict__ fk, const uint32_t* __restrict__ tab,
+                                                        uint32_t* __restrict__ coef, int32_t* __restrict__ status) {
+  __shared__ uint32_t lds[LB_FK_N * 8];
+  const uint32_t b = blockIdx.x / LB_FK_COLS, r = blockIdx.x % LB_FK_COLS, t = threadIdx.x;
+  if (b >= n_blobs || !n_cells) return;
+  fr_lds_slots V{{lds, LB_FK_N}};
+  const fr_gmulw FW{fk + (size_t)8 * LB_FK_TAB_FWD_MONT}, IW{fk + (size_t)8 * LB_FK_TAB_INV_MONT};
+  uint32_t mk[LB_RC_MASK_WORDS];
+  LB_UNROLL for (uint32_t w = 0; w < LB_RC_MASK_WORDS; w++) mk[w] = mask[b * LB_RC_MASK_WORDS + w];
+  const uint32_t last = n_cells - 1u;
+  const auto C = [cells, last](uint32_t k, uint32_t j) { return fr_ldg(cells + ((size_t)min(k, last) * LB_FR_CELL + j) * 8); };
+  rc_col_load(V, C, mk, off[b], fr_gtable{zev + (size_t)b * LB_FK_N * 8}, r, t);
+  __syncthreads();
+  for (int s = 0; s < LB_FK_LOG; s++) {
+    fk_fft_stage(V, s, IW, t);
+    __syncthreads();
+  }
+  fr v[2];
+  rc_take(V, fr_gtable{tab + (size_t)8 * LB_FR_CELL_TAB_SCALE}, t, v);
+  __syncthreads();
+  rc_put(V, t, v);
+  __syncthreads();
+  for (int s = 0; s < LB_FK_LOG; s++) {
+    fk_fft_stage(V, s, FW, t);
+    __syncthreads();
+  }
+  rc_take(V, fr_gtable{zcinv + (size_t)b * LB_FK_N * 8}, t, v);
+  __syncthreads();
+  rc_put(V, t, v);
+  __syncthreads();
+  for (int s = 0; s < LB_FK_LOG; s++) {
+    fk_fft_stage(V, s, IW, t);
+    __syncthreads();
+  }
+  const fr inv_n = fr_ldg(fk + (size_t)8 * LB_FK_TAB_SCALE_MONT);
+  if (rc_col_store(V, fr_gtable{tab + (size_t)8 * LB_FR_CELL_TAB_WINV}, fr_sqr(inv_n), r, t, coef + (size_t)b * LB_FR_N * 8))
+    status[b] = LB_VERIFY_FAIL;
+}
+#endif  // LB_KG
+
+// One workgroup per blob, the shape of k_fr_intt4096 (1024 lanes, LB_FR_INTT_LDS bytes of dynamic
+// LDS): the blob's 4096 monomial coefficients (coef, Montgomery) -> its 4096 big-endian elements, the
+// evaluations in bit-reversed order, at out_blobs + b * 131072.  Twelve forward stages, no coset
+// scale (lb_recover.h rc_blob_load); k_fr_coset_ntt4096 takes the result for the cells' first half.
+#if LB_KG(16)
+__global__ void __launch_bounds__(LB_FR_WG) k_fr_ntt4096(const uint32_t* __restrict__ coef, const uint32_t* __restrict__ tab,
+                                                         uint8_t* __restrict__ out_blobs) {
+  extern __shared__ uint32_t lb_fr_lds[];
+  fr_lds_poly A{lb_fr_lds};
+  const fr_gpoly C{coef + (size_t)blockIdx.x * LB_FR_N * 8};
+  const fr_gtable T{tab + (size_t)8 * LB_FR_CELL_TAB_FWD};
+  rc_blob_load(A, C, threadIdx.x, LB_FR_WG);
+  __syncthreads();
+  for (int s = 0; s < LB_FR_LOGN; s++) {
+    fr_ntt_stage(A, LB_FR_LOGN, s, T, threadIdx.x, LB_FR_WG);
+    __syncthreads();
+  }
+  uint32_t* out = reinterpret_cast<uint32_t*>(out_blobs + (size_t)blockIdx.x * LB_FR_N * 32);
+  for (uint32_t k = threadIdx.x; k < LB_FR_N; k += LB_FR_WG) {
+    uint32_t w[8];
+    fr_to_be_words(w, fr_coset_value(A, k));
+    fr_stg(out + (size_t)8 * k, fr_from_words(w));
+  }
 }
 #endif  // LB_KG

@@ -30,6 +30,24 @@ static inline void kzg_fold_status(uint32_t n, const int32_t* first, const int32
   }
 }
 
+// lb_kzg_recover_cells_and_proofs' argument check: off[0 .. n] splits idx into n blobs' given cells,
+// each blob has 64 .. 128 of them, every index is below 128 and a blob's indices strictly ascend (the
+// spec's sorted and no-duplicates checks).  mask: 4 words per blob, zeroed by the caller; bit
+// (i mod 32) of word 4 b + i div 32 is set where blob b's cell i is given (lb_recover.h rc_present).
+static inline bool kzg_recover_plan(uint32_t n, const uint32_t* off, const uint32_t* idx, uint32_t* mask) {
+  if (!kzg_offsets_ok(n, off, n * 128u)) return false;
+  for (uint32_t b = 0; b < n; b++) {
+    const uint32_t lo = off[b], cnt = off[b + 1] - lo;
+    if (cnt < 64u || cnt > 128u) return false;
+    for (uint32_t k = 0; k < cnt; k++) {
+      const uint32_t i = idx[lo + k];
+      if (i >= 128u || (k && i <= idx[lo + k - 1])) return false;
+      mask[4 * b + (i >> 5)] |= 1u << (i & 31u);
+    }
+  }
+  return true;
+}
+
 // 32 little-endian bytes as a field element's words: plain form, not range-checked (fr_lt_mod)
 static inline fr kzg_fr_from_le32(const uint8_t* b) {
   fr a;

@@ -929,6 +929,40 @@ int32_t kzg_fk_table(lb_engine* e) {
 }
 }  // namespace
 
+namespace {
+// The device buffers of FK20's steps 2 - 4 for n blobs, and those steps: from the blobs' Montgomery
+// coefficients (d_coef) to their 128 compressed proofs each (d_proofs).  Shared by
+// lb_kzg_compute_cells_and_proofs and lb_kzg_recover_cells_and_proofs.  Does not synchronise.
+struct kzg_fk_ws {
+  uint32_t* col_scalars;
+  uint32_t* terms;
+  uint32_t* sums;  // E[r], then the proofs as Jacobian points
+  uint32_t* h;
+  uint8_t* proofs;
+  kzg_fk_ws(kzg_bufs& w, size_t n)
+      : col_scalars(w.get<uint32_t>(n * LB_FK_POINTS * sizeof(fr))), terms(w.get<uint32_t>(n * LB_FK_POINTS * sizeof(g1j))),
+        sums(w.get<uint32_t>(n * LB_FK_N * sizeof(g1j))), h(w.get<uint32_t>(n * LB_FK_N * sizeof(g1j))),
+        proofs(w.get<uint8_t>(n * LB_FK_N * 48)) {}
+};
+int32_t kzg_fk_proofs(lb_engine* e, const kzg_fk_ws& f, uint32_t n, const uint32_t* d_coef) {
+  const uint32_t np = n * LB_FK_N, nt = n * LB_FK_POINTS;
+  // 2. the 64 column transforms per blob -> the scalars C_i[r] / 128 in the table's order
+  hipLaunchKernelGGL(k_fr_fk_cols, dim3(n * LB_FK_COLS), dim3(64), 0, e->stream, n, d_coef, e->kzg.fk_tw.as<uint32_t>(),
+                     f.col_scalars);
+  // 3. every ladder of the call in one launch, then E[r]: entry 128 b + r of f.sums
+  hipLaunchKernelGGL(k_g1_jac_terms, dim3(nblk(nt)), dim3(LB_TPB), 0, e->stream, nt, e->kzg.fk_x.as<uint32_t>(), LB_FK_POINTS,
+                     f.col_scalars, f.terms);
+  hipLaunchKernelGGL(k_g1_sum64, dim3(np), dim3(64), 0, e->stream, nt, f.terms, np, f.sums);
+  LB_HIP(hipGetLastError());
+  // 4. h = IDFT(E) (scaled already); the proofs = DFT(h[0 .. 63], O ...): h[64 .. 127] are dropped by the load
+  kzg_fk_fft(e, n, f.sums, np, LB_FK_N, 1, LB_FK_N, LB_FK_TAB_INV, f.h, np, LB_FK_N, 1);
+  kzg_fk_fft(e, n, f.h, np, LB_FK_N, 1, LB_FK_LIVE, LB_FK_TAB_FWD, f.sums, np, LB_FK_N, 1);
+  hipLaunchKernelGGL(k_g1_fk_out48, dim3(np / 64), dim3(64), 0, e->stream, np, f.sums, f.proofs);
+  LB_HIP(hipGetLastError());
+  return LB_OK;
+}
+}  // namespace
+
 // compute_cells_and_kzg_proofs for n_blobs blobs with ONE synchronisation (after the table's first
 // build): a blob with an element >= r still runs, on the reduced element, and is zeroed afterwards.
 extern "C" int32_t lb_kzg_compute_cells_and_proofs(lb_engine* e, uint32_t n_blobs, const uint8_t* blobs, uint8_t* out_cells,
@@ -936,7 +970,7 @@ extern "C" int32_t lb_kzg_compute_cells_and_proofs(lb_engine* e, uint32_t n_blob
   if (!kzg_ready(e) || n_blobs > kMaxFkBlobs) return LB_ERR_ARGUMENT;
   if (!n_blobs) return LB_OK;
   if (!blobs || !out_cells || !out_proofs48 || !out_status) return LB_ERR_ARGUMENT;
-  const uint32_t n = n_blobs, np = n * LB_FK_N, nt = n * LB_FK_POINTS;
+  const uint32_t n = n_blobs;
   const size_t proof_bytes = (size_t)LB_FK_N * 48;
   std::lock_guard<std::mutex> lk(e->mu);
   LB_HIP(hipSetDevice(e->device));
@@ -945,34 +979,98 @@ extern "C" int32_t lb_kzg_compute_cells_and_proofs(lb_engine* e, uint32_t n_blob
   const kzg_blobs d(w, n);
   uint32_t* d_coef = w.get<uint32_t>(n * kBlobBytes);
   uint8_t* d_cells = w.get<uint8_t>(n * LB_FR_EXT_BYTES);
-  uint32_t* d_col_scalars = w.get<uint32_t>((size_t)nt * sizeof(fr));
-  uint32_t* d_terms = w.get<uint32_t>((size_t)nt * sizeof(g1j));
-  uint32_t* d_sums = w.get<uint32_t>((size_t)np * sizeof(g1j));  // E[r], then the proofs as Jacobian points
-  uint32_t* d_h = w.get<uint32_t>((size_t)np * sizeof(g1j));
-  uint8_t* d_proofs = w.get<uint8_t>(n * proof_bytes);
+  const kzg_fk_ws fk(w, n);
   LB_HIP(w.error());
   // 1. decode, coefficients, and the cells by the path of lb_kzg_compute_cells
   LB_TRY(kzg_decode_async(e, d, n, blobs));
   LB_TRY(kzg_intt(e, n, d.polys, d_coef, nullptr));
   LB_TRY(kzg_coset_ntt(e, n, d_coef, d.bytes, d_cells));
-  // 2. the 64 column transforms per blob -> the scalars C_i[r] / 128 in the table's order
-  hipLaunchKernelGGL(k_fr_fk_cols, dim3(n * LB_FK_COLS), dim3(64), 0, e->stream, n, d_coef, e->kzg.fk_tw.as<uint32_t>(),
-                     d_col_scalars);
-  // 3. every ladder of the call in one launch, then E[r]: entry 128 b + r of d_sums
-  hipLaunchKernelGGL(k_g1_jac_terms, dim3(nblk(nt)), dim3(LB_TPB), 0, e->stream, nt, e->kzg.fk_x.as<uint32_t>(), LB_FK_POINTS,
-                     d_col_scalars, d_terms);
-  hipLaunchKernelGGL(k_g1_sum64, dim3(np), dim3(64), 0, e->stream, nt, d_terms, np, d_sums);
-  LB_HIP(hipGetLastError());
-  // 4. h = IDFT(E) (scaled already); the proofs = DFT(h[0 .. 63], O ...): h[64 .. 127] are dropped by the load
-  kzg_fk_fft(e, n, d_sums, np, LB_FK_N, 1, LB_FK_N, LB_FK_TAB_INV, d_h, np, LB_FK_N, 1);
-  kzg_fk_fft(e, n, d_h, np, LB_FK_N, 1, LB_FK_LIVE, LB_FK_TAB_FWD, d_sums, np, LB_FK_N, 1);
-  hipLaunchKernelGGL(k_g1_fk_out48, dim3(np / 64), dim3(64), 0, e->stream, np, d_sums, d_proofs);
-  LB_HIP(hipGetLastError());
+  // 2. - 4. FK20 from the coefficients
+  LB_TRY(kzg_fk_proofs(e, fk, n, d_coef));
   std::vector<int32_t> blob_status(n, LB_OK);
   LB_HIP(hipMemcpyAsync(out_cells, d_cells, n * LB_FR_EXT_BYTES, hipMemcpyDeviceToHost, e->stream));
-  LB_HIP(hipMemcpyAsync(out_proofs48, d_proofs, n * proof_bytes, hipMemcpyDeviceToHost, e->stream));
+  LB_HIP(hipMemcpyAsync(out_proofs48, fk.proofs, n * proof_bytes, hipMemcpyDeviceToHost, e->stream));
   LB_HIP(hipMemcpyAsync(blob_status.data(), d.status, (size_t)n * 4, hipMemcpyDeviceToHost, e->stream));
   LB_HIP(hipStreamSynchronize(e->stream));
   kzg_fold_status(n, blob_status.data(), nullptr, out_status, out_cells, LB_FR_EXT_BYTES, out_proofs48, proof_bytes);
+  return LB_OK;
+}
+
+// recover_cells_and_kzg_proofs for n_blobs blobs with ONE synchronisation (after the table's first
+// build).  The host validates the indices and builds each blob's present-cell mask; everything else
+// is on the device: decode (k_fr_cell_load), the cells' interpolation polynomials (k_fr_cell_interp,
+// unit weights), the erasure decode (lb_recover.h: k_fr_recover_zero, k_fr_recover_cols) into the
+// blobs' coefficients, then every cell from those coefficients (k_fr_ntt4096, k_fr_coset_ntt4096)
+// and FK20.  A blob with an element >= r or with inconsistent cells still runs and is zeroed afterwards.
+extern "C" int32_t lb_kzg_recover_cells_and_proofs(lb_engine* e, uint32_t n_blobs, const uint32_t* cell_offsets,
+                                                   const uint32_t* cell_indices, const uint8_t* cells, uint8_t* out_cells,
+                                                   uint8_t* out_proofs48, int32_t* out_status) {
+  if (!kzg_ready(e) || n_blobs > kMaxFkBlobs) return LB_ERR_ARGUMENT;
+  if (!n_blobs) return LB_OK;
+  if (!cell_offsets || !cell_indices || !cells || !out_cells || !out_proofs48 || !out_status) return LB_ERR_ARGUMENT;
+  const uint32_t n = n_blobs;
+  std::vector<uint32_t> mask((size_t)n * LB_RC_MASK_WORDS, 0);
+  if (!kzg_recover_plan(n, cell_offsets, cell_indices, mask.data())) return LB_ERR_ARGUMENT;
+  const uint32_t nc = cell_offsets[n];
+  const size_t proof_bytes = (size_t)LB_FK_N * 48;
+  std::vector<fr> ones(nc, fr_one());  // the host arrays live until the synchronisation
+  std::lock_guard<std::mutex> lk(e->mu);
+  LB_HIP(hipSetDevice(e->device));
+  LB_TRY(kzg_fk_table(e));
+  kzg_bufs w;
+  uint8_t* d_in = w.get<uint8_t>((size_t)nc * LB_FR_CELL_BYTES);
+  uint32_t* d_cell_fr = w.get<uint32_t>((size_t)nc * LB_FR_CELL_BYTES);  // the cells as Montgomery Fr, then I_k in place
+  int32_t* d_cell_status = w.get<int32_t>((size_t)nc * 4);
+  uint32_t* d_cell_idx = w.get<uint32_t>((size_t)nc * 4);
+  uint32_t* d_weights = w.get<uint32_t>((size_t)nc * sizeof(fr));
+  uint32_t* d_off = w.get<uint32_t>((size_t)(n + 1) * 4);
+  uint32_t* d_mask = w.get<uint32_t>(mask.size() * 4);
+  uint32_t* d_zev = w.get<uint32_t>((size_t)n * LB_FK_N * sizeof(fr));
+  uint32_t* d_zcinv = w.get<uint32_t>((size_t)n * LB_FK_N * sizeof(fr));
+  int32_t* d_fit_status = w.get<int32_t>((size_t)n * 4);
+  uint32_t* d_coef = w.get<uint32_t>(n * kBlobBytes);
+  uint8_t* d_blob_bytes = w.get<uint8_t>(n * kBlobBytes);
+  uint8_t* d_cells = w.get<uint8_t>(n * LB_FR_EXT_BYTES);
+  const kzg_fk_ws fk(w, n);
+  LB_HIP(w.error());
+  // 1. the cells go up and are decoded; 2. their interpolation polynomials, in place
+  LB_HIP(hipMemcpyAsync(d_in, cells, (size_t)nc * LB_FR_CELL_BYTES, hipMemcpyHostToDevice, e->stream));
+  LB_HIP(hipMemcpyAsync(d_cell_idx, cell_indices, (size_t)nc * 4, hipMemcpyHostToDevice, e->stream));
+  LB_HIP(hipMemcpyAsync(d_weights, ones.data(), (size_t)nc * sizeof(fr), hipMemcpyHostToDevice, e->stream));
+  LB_HIP(hipMemcpyAsync(d_off, cell_offsets, (size_t)(n + 1) * 4, hipMemcpyHostToDevice, e->stream));
+  LB_HIP(hipMemcpyAsync(d_mask, mask.data(), mask.size() * 4, hipMemcpyHostToDevice, e->stream));
+  LB_HIP(hipMemsetAsync(d_cell_status, 0, (size_t)nc * 4, e->stream));
+  LB_HIP(hipMemsetAsync(d_fit_status, 0, (size_t)n * 4, e->stream));
+  const uint32_t n_elems = nc * LB_FR_CELL;
+  hipLaunchKernelGGL(k_fr_cell_load, dim3((n_elems + 255) / 256), dim3(256), 0, e->stream, n_elems, d_in, d_cell_fr, d_cell_status);
+  hipLaunchKernelGGL(k_fr_cell_interp, dim3(nc), dim3(64), 0, e->stream, nc, d_cell_fr, d_cell_idx, d_weights,
+                     e->kzg.cell_tab.as<uint32_t>());
+  LB_HIP(hipGetLastError());
+  // 3. per blob the vanishing polynomial's values, per (blob, column) the decode -> the coefficients
+  hipLaunchKernelGGL(k_fr_recover_zero, dim3(n), dim3(64), 0, e->stream, n, d_mask, e->kzg.fk_tw.as<uint32_t>(),
+                     e->kzg.cell_tab.as<uint32_t>(), d_zev, d_zcinv);
+  hipLaunchKernelGGL(k_fr_recover_cols, dim3(n * LB_FK_COLS), dim3(64), 0, e->stream, n, d_cell_fr, nc, d_off, d_mask, d_zev, d_zcinv,
+                     e->kzg.fk_tw.as<uint32_t>(), e->kzg.cell_tab.as<uint32_t>(), d_coef, d_fit_status);
+  LB_HIP(hipGetLastError());
+  // 4. every cell from the coefficients: the blob's bytes, then the path of lb_kzg_compute_cells
+  LB_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_fr_ntt4096), hipFuncAttributeMaxDynamicSharedMemorySize,
+                             (int)LB_FR_INTT_LDS));
+  hipLaunchKernelGGL(k_fr_ntt4096, dim3(n), dim3(LB_FR_WG), LB_FR_INTT_LDS, e->stream, d_coef, e->kzg.cell_tab.as<uint32_t>(),
+                     d_blob_bytes);
+  LB_HIP(hipGetLastError());
+  LB_TRY(kzg_coset_ntt(e, n, d_coef, d_blob_bytes, d_cells));
+  // 5. FK20 from the coefficients
+  LB_TRY(kzg_fk_proofs(e, fk, n, d_coef));
+  std::vector<int32_t> cell_status(nc, LB_OK), scalar_status(n, LB_OK), fit_status(n, LB_OK);
+  LB_HIP(hipMemcpyAsync(out_cells, d_cells, n * LB_FR_EXT_BYTES, hipMemcpyDeviceToHost, e->stream));
+  LB_HIP(hipMemcpyAsync(out_proofs48, fk.proofs, n * proof_bytes, hipMemcpyDeviceToHost, e->stream));
+  LB_HIP(hipMemcpyAsync(cell_status.data(), d_cell_status, (size_t)nc * 4, hipMemcpyDeviceToHost, e->stream));
+  LB_HIP(hipMemcpyAsync(fit_status.data(), d_fit_status, (size_t)n * 4, hipMemcpyDeviceToHost, e->stream));
+  LB_HIP(hipStreamSynchronize(e->stream));
+  // an element >= r comes before the cells' inconsistency
+  for (uint32_t b = 0; b < n; b++)
+    for (uint32_t k = cell_offsets[b]; k < cell_offsets[b + 1]; k++)
+      if (cell_status[k] != LB_OK) scalar_status[b] = LB_BAD_SCALAR;
+  kzg_fold_status(n, scalar_status.data(), fit_status.data(), out_status, out_cells, LB_FR_EXT_BYTES, out_proofs48, proof_bytes);
   return LB_OK;
 }

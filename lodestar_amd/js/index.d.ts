@@ -113,6 +113,18 @@ export interface CKzg {
    * would throw, per blob.
    */
   computeCellsAndKzgProofsMany(blobs: Uint8Array[]): ([Uint8Array[], Uint8Array[]] | Error)[];
+  /**
+   * c-kzg recoverCellsAndKzgProofs: [all 128 cells, all 128 proofs] of the blob that the given 64 .. 128
+   * cells (with their strictly ascending indices) belong to, on the GPU.  Throws BLST_BAD_SCALAR for a
+   * cell element >= r and BLST_VERIFY_FAIL where more than 64 cells lie on no one polynomial of degree
+   * < 4096 (stricter than c-kzg).
+   */
+  recoverCellsAndKzgProofs(cellIndices: number[], cells: Uint8Array[]): [Uint8Array[], Uint8Array[]];
+  /**
+   * recoverCellsAndKzgProofs for many blobs in one pass: [cells, proofs], or the Error the single call
+   * would throw, per blob.
+   */
+  recoverCellsAndKzgProofsMany(groups: KzgRecoverGroup[]): ([Uint8Array[], Uint8Array[]] | Error)[];
   /** c-kzg verifyCellKzgProofBatch: one commitment, cell index, cell and proof per cell; on the GPU. */
   verifyCellKzgProofBatch(commitments: Uint8Array[], cellIndices: number[], cells: Uint8Array[], proofs: Uint8Array[]): boolean;
   /**
@@ -126,6 +138,8 @@ export interface CKzg {
 }
 /** One verifyCellKzgProofBatch call: one entry of each array per cell. */
 export type KzgCellGroup = {commitments: Uint8Array[]; cellIndices: number[]; cells: Uint8Array[]; proofs: Uint8Array[]};
+/** One recoverCellsAndKzgProofs call: 64 .. 128 cells of one blob and their indices, ascending. */
+export type KzgRecoverGroup = {cellIndices: number[]; cells: Uint8Array[]};
 export type KzgSidecar = {blobs: Uint8Array[]; commitments: Uint8Array[]; proof: Uint8Array};
 /** One verifyBlobKzgProofBatch call: one proof per blob. */
 export type KzgBlobGroup = {blobs: Uint8Array[]; commitments: Uint8Array[]; proofs: Uint8Array[]};

@@ -395,13 +395,13 @@ function verifyKzgProof(commitment, zBytes, yBytes, proof) {
 }
 
 // ------------------------------------------------------------------ cells (EIP-7594, PeerDAS)
-// c-kzg computeCells, computeCellsAndKzgProofs and verifyCellKzgProofBatch(commitments, cellIndices,
-// cells, proofs), always on the GPU (kzgComputeCells -> lb_kzg_compute_cells, kzgComputeCellsAndProofs
-// -> lb_kzg_compute_cells_and_proofs: FK20, kzgVerifyCellProofBatch -> lb_kzg_verify_cell_proof_batch),
-// in either field mode.  The batch's combiner (computeCellBatchR:
+// c-kzg computeCells, computeCellsAndKzgProofs, recoverCellsAndKzgProofs(cellIndices, cells) and
+// verifyCellKzgProofBatch(commitments, cellIndices, cells, proofs), always on the GPU (kzgComputeCells ->
+// lb_kzg_compute_cells, kzgComputeCellsAndProofs -> lb_kzg_compute_cells_and_proofs: FK20,
+// kzgRecoverCellsAndProofs -> lb_kzg_recover_cells_and_proofs, kzgVerifyCellProofBatch ->
+// lb_kzg_verify_cell_proof_batch), in either field mode.  The batch's combiner (computeCellBatchR:
 // the commitments deduplicated in order of first appearance) hashes only the caller's bytes; like
 // the other transcripts its byte parity with c-kzg is unpinned, and no verdict depends on it.
-// recoverCellsAndKzgProofs is not here.
 const BYTES_PER_CELL = 2048;
 const CELLS_PER_EXT_BLOB = 128;
 const CELL_DOMAIN = Buffer.from("RCKZGCBATCH__V1_", "ascii");
@@ -467,6 +467,56 @@ function computeCellsAndKzgProofs(blob) {
   if (res instanceof Error) throw res;
   return res;
 }
+// groups: {cellIndices, cells}[], one blob each: any 64 .. 128 of its cells with their strictly ascending
+// indices.  One entry per blob: [cells, proofs] (all 128 of each), or the Error the single call would
+// throw -- returned, not thrown: BLST_BAD_SCALAR for a cell element >= r, BLST_VERIFY_FAIL where more
+// than 64 cells lie on no one polynomial of degree < 4096 (stricter than c-kzg).  Malformed input
+// throws before anything is sent; more than 128 blobs go in passes.
+function checkRecoverGroup(g) {
+  if (!g || !Array.isArray(g.cellIndices) || !Array.isArray(g.cells)) throw Error("cellIndices and cells: arrays");
+  if (g.cellIndices.length !== g.cells.length) throw Error("cellIndices / cells length mismatch");
+  if (g.cells.length < CELLS_PER_EXT_BLOB / 2 || g.cells.length > CELLS_PER_EXT_BLOB) throw Error("cell count not in 64 .. 128");
+  g.cells.forEach(checkCell);
+  g.cellIndices.forEach(checkCellIndex);
+  for (let k = 1; k < g.cellIndices.length; k++) {
+    if (g.cellIndices[k] <= g.cellIndices[k - 1]) throw Error("cell indices not strictly ascending");
+  }
+}
+function recoverCellsAndKzgProofsMany(groups) {
+  groups.forEach(checkRecoverGroup);
+  requireSetup();
+  const res = [];
+  for (let lo = 0; lo < groups.length; lo += MAX_BLOBS_PER_CELLS_AND_PROOFS_CALL) {
+    const part = groups.slice(lo, lo + MAX_BLOBS_PER_CELLS_AND_PROOFS_CALL);
+    const offsets = new Uint32Array(part.length + 1);
+    part.forEach((g, k) => (offsets[k + 1] = offsets[k] + g.cells.length));
+    const idx = new Uint32Array(offsets[part.length]);
+    const flat = new Uint8Array(BYTES_PER_CELL * offsets[part.length]);
+    part.forEach((g, k) => {
+      idx.set(g.cellIndices, offsets[k]);
+      g.cells.forEach((c, i) => flat.set(c, BYTES_PER_CELL * (offsets[k] + i)));
+    });
+    const {cells, proofs, status} = addon.kzgRecoverCellsAndProofs(engine, offsets, idx, flat);
+    part.forEach((_, b) => {
+      if (status[b] !== 0) {
+        res.push(Error(addon.errorName(status[b])));
+        return;
+      }
+      const c0 = b * CELLS_PER_EXT_BLOB * BYTES_PER_CELL;
+      const p0 = b * CELLS_PER_EXT_BLOB * 48;
+      res.push([
+        Array.from({length: CELLS_PER_EXT_BLOB}, (_x, i) => cells.slice(c0 + BYTES_PER_CELL * i, c0 + BYTES_PER_CELL * (i + 1))),
+        Array.from({length: CELLS_PER_EXT_BLOB}, (_x, i) => proofs.slice(p0 + 48 * i, p0 + 48 * (i + 1))),
+      ]);
+    });
+  }
+  return res;
+}
+function recoverCellsAndKzgProofs(cellIndices, cells) {
+  const res = recoverCellsAndKzgProofsMany([{cellIndices, cells}])[0];
+  if (res instanceof Error) throw res;
+  return res;
+}
 // groups: {commitments, cellIndices, cells, proofs}[], one of each per cell.  One entry per group:
 // true, false, or the Error the single call would throw -- returned, not thrown.  Malformed input
 // throws before anything is sent.
@@ -513,6 +563,8 @@ module.exports = {
   computeCells,
   computeCellsAndKzgProofs,
   computeCellsAndKzgProofsMany,
+  recoverCellsAndKzgProofs,
+  recoverCellsAndKzgProofsMany,
   verifyCellKzgProofBatch,
   verifyCellKzgProofBatchMany,
   BYTES_PER_CELL,

@@ -32,8 +32,10 @@ Cells (EIP-7594, "PeerDAS", the Fulu fork; c-kzg `computeCells`, `verifyCellKzgP
 blob's polynomial over the 8192-point domain in 128 cells of 64 values, each cell with its own proof.
 `Kzg.compute_cells`, `Kzg.compute_cell_kzg_proofs` (the direct per-cell route, one multi-scalar
 multiplication per cell), `Kzg.compute_cells_and_kzg_proofs(_many)` (c-kzg `computeCellsAndKzgProofs`:
-all 128 proofs of a blob by FK20) and `Kzg.verify_cell_kzg_proof_batch(_many)` always run on the GPU
-(`lb_kzg_compute_cells`, `lb_kzg_compute_cell_proofs`, `lb_kzg_compute_cells_and_proofs`,
+all 128 proofs of a blob by FK20), `Kzg.recover_cells_and_kzg_proofs(_many)` (c-kzg
+`recoverCellsAndKzgProofs`: all cells and proofs of a blob from any 64 of its cells) and
+`Kzg.verify_cell_kzg_proof_batch(_many)` always run on the GPU (`lb_kzg_compute_cells`,
+`lb_kzg_compute_cell_proofs`, `lb_kzg_compute_cells_and_proofs`, `lb_kzg_recover_cells_and_proofs`,
 `lb_kzg_verify_cell_proof_batch`), whatever `field` is.
 `compute_cell_batch_r` restates the batch's combiner; like the other transcripts its byte parity
 with c-kzg is UNPINNED, and the verdicts do not depend on its exact bytes: a valid batch passes for
@@ -630,6 +632,62 @@ class Kzg:
             raise res
         return res
 
+    def recover_cells_and_kzg_proofs_many(self, groups: Sequence[Tuple[Sequence[int], Sequence[bytes]]]) -> list:
+        """recover_cells_and_kzg_proofs for many blobs (one group = one blob's cell indices and cells)
+        in passes of up to 128 over the GPU (`lb_kzg_recover_cells_and_proofs`), whatever `field` is.
+        One entry per blob: the pair (128 cells, 128 proofs), or the KzgError the single call would
+        raise -- returned, not raised: BLST_BAD_SCALAR for a cell element >= r, and a failed check
+        where more than 64 cells lie on no one polynomial of degree < 4096 (stricter than c-kzg).
+        Malformed input raises ValueError before anything is sent: a wrong cell length, indices and
+        cells of different lengths, fewer than 64 or more than 128 cells, an index outside 0 .. 127,
+        indices that do not strictly ascend."""
+        what = "recoverCellsAndKzgProofs"
+        flat = []
+        for g_idx, g_cells in groups:
+            idx = [int(i) for i in g_idx]
+            if len(idx) != len(g_cells):
+                raise ValueError(f"{what}: {len(idx)} cell indices for {len(g_cells)} cells")
+            if not CELLS_PER_EXT_BLOB // 2 <= len(idx) <= CELLS_PER_EXT_BLOB:
+                raise ValueError(f"{what}: {len(idx)} cells, not {CELLS_PER_EXT_BLOB // 2} .. {CELLS_PER_EXT_BLOB}")
+            if any(len(c) != BYTES_PER_CELL for c in g_cells):
+                raise ValueError(f"{what}: {BYTES_PER_CELL}-byte cells")
+            if any(not 0 <= i < CELLS_PER_EXT_BLOB for i in idx):
+                raise ValueError(f"{what}: cell indices below {CELLS_PER_EXT_BLOB}")
+            if any(a >= b for a, b in zip(idx, idx[1:])):
+                raise ValueError(f"{what}: cell indices strictly ascending")
+            flat.append((idx, [bytes(c) for c in g_cells]))
+        u8, u32, i32 = ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_int32)
+        res: list = []
+        for lo in range(0, len(flat), MAX_BLOBS_PER_CELLS_AND_PROOFS_CALL):
+            part = flat[lo: lo + MAX_BLOBS_PER_CELLS_AND_PROOFS_CALL]
+            n = len(part)
+            off = np.cumsum([0] + [len(idx) for idx, _ in part]).astype(np.uint32)
+            ci = np.asarray([i for idx, _ in part for i in idx], np.uint32)
+            src = np.frombuffer(b"".join(c for _, g_cells in part for c in g_cells), np.uint8)
+            cells = np.zeros(n * CELLS_PER_EXT_BLOB * BYTES_PER_CELL, np.uint8)
+            proofs = np.zeros(n * CELLS_PER_EXT_BLOB * 48, np.uint8)
+            status = np.zeros(n, np.int32)
+            self._check(self.lib.lb_kzg_recover_cells_and_proofs(
+                self.engine.h, n, off.ctypes.data_as(u32), ci.ctypes.data_as(u32), src.ctypes.data_as(u8), cells.ctypes.data_as(u8),
+                proofs.ctypes.data_as(u8), status.ctypes.data_as(i32)), f"{what}Many")
+            craw, praw = cells.tobytes(), proofs.tobytes()
+            for b in range(n):
+                if status[b] != 0:
+                    res.append(KzgError(f"{what}: {self._N.error_name(int(status[b]))}"))
+                    continue
+                c0, p0 = b * CELLS_PER_EXT_BLOB * BYTES_PER_CELL, b * CELLS_PER_EXT_BLOB * 48
+                res.append(([craw[c0 + BYTES_PER_CELL * i: c0 + BYTES_PER_CELL * (i + 1)] for i in range(CELLS_PER_EXT_BLOB)],
+                            [praw[p0 + 48 * i: p0 + 48 * (i + 1)] for i in range(CELLS_PER_EXT_BLOB)]))
+        return res
+
+    def recover_cells_and_kzg_proofs(self, cell_indices: Sequence[int], cells: Sequence[bytes]) -> Tuple[List[bytes], List[bytes]]:
+        """c-kzg recoverCellsAndKzgProofs: (all 128 cells, all 128 proofs) of the blob that any 64 .. 128
+        of its cells, given with their strictly ascending indices, belong to"""
+        res = self.recover_cells_and_kzg_proofs_many([(cell_indices, cells)])[0]
+        if isinstance(res, KzgError):
+            raise res
+        return res
+
     def verify_cell_kzg_proof_batch_many(self, groups: Sequence[Tuple[Sequence[bytes], Sequence[int], Sequence[bytes], Sequence[bytes]]]) -> list:
         """verify_cell_kzg_proof_batch for many groups (one group = one call's commitments, cell
         indices, cells, proofs, one of each per cell) in one pass over the GPU
@@ -678,6 +736,8 @@ class Kzg:
     computeCells = compute_cells
     computeCellsAndKzgProofs = compute_cells_and_kzg_proofs
     computeCellsAndKzgProofsMany = compute_cells_and_kzg_proofs_many
+    recoverCellsAndKzgProofs = recover_cells_and_kzg_proofs
+    recoverCellsAndKzgProofsMany = recover_cells_and_kzg_proofs_many
     verifyCellKzgProofBatch = verify_cell_kzg_proof_batch
     verifyCellKzgProofBatchMany = verify_cell_kzg_proof_batch_many
     computeBlobKzgProof = compute_blob_kzg_proof

@@ -58,6 +58,8 @@
  *   kzgComputeCellsAndProofs(engine, blobs) -> {cells: Uint8Array (n x 128 x 2048 B), proofs: Uint8Array
  *     (n x 128 x 48 B), status: Int32Array (n)}: every blob's cells and all their proofs (FK20), at most
  *     128 blobs; a rejected blob's outputs are zeroed, nothing is thrown for it
+ *   kzgRecoverCellsAndProofs(engine, cellOffsets: Uint32Array, cellIndices: Uint32Array, cells) -> the same
+ *     object: every blob's cells and proofs from 64 .. 128 of its cells, at most 128 blobs
  *   kzgVerifyCellProofBatch(engine, cellOffsets: Uint32Array, commitments, cellIndices: Uint32Array,
  *     cells, proofs) -> Int32Array: many verifyCellKzgProofBatch groups in one pass, 1 / 0 / -code
  *   (the KZG calls are synchronous, as c-kzg's are; lodestar_amd/js/kzg.js builds the ckzg
@@ -970,6 +972,44 @@ static napi_value kzg_compute_cells_and_proofs(napi_env env, napi_callback_info 
   return obj;
 }
 
+/* All cells and proofs of n <= 128 blobs from 64 .. 128 cells each (lb_kzg_recover_cells_and_proofs): blob
+ * k is given by cells cellOffsets[k] .. cellOffsets[k + 1] - 1 of the flat arrays.  Flat arrays and one
+ * status per blob, as the C call gives them; nothing is thrown for a rejected blob. */
+static napi_value kzg_recover_cells_and_proofs(napi_env env, napi_callback_info info) {
+  size_t argc = 4;
+  napi_value argv[4];
+  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  engine_box* b = NULL;
+  tview of, ix, ce;
+  if (argc < 4 || napi_get_value_external(env, argv[0], (void**)&b) != napi_ok || !b || !b->e ||
+      !get_view(env, argv[1], &of) || !of.present || of.type != napi_uint32_array || of.n < 1 || of.n > 129 ||
+      !get_view(env, argv[2], &ix) || !ix.present || ix.type != napi_uint32_array ||
+      !get_view(env, argv[3], &ce) || !ce.present || ce.type != napi_uint8_array || ce.n != ix.n * LB_CELL_BYTES ||
+      ((const uint32_t*)of.data)[of.n - 1] != ix.n) {
+    napi_throw_type_error(env, NULL,
+                          "kzgRecoverCellsAndProofs(engine, cellOffsets: Uint32Array of n + 1 prefix sums ending in c, n <= 128, "
+                          "cellIndices: Uint32Array of c, cells: Uint8Array of c x 2048 bytes)");
+    return NULL;
+  }
+  const uint32_t n = (uint32_t)(of.n - 1);
+  napi_value ab_c, ab_p, ab_s, out_c, out_p, out_s, obj;
+  void *pc, *pp, *ps;
+  NAPI_CALL(env, napi_create_arraybuffer(env, (size_t)n * 128 * LB_CELL_BYTES, &pc, &ab_c));
+  NAPI_CALL(env, napi_create_arraybuffer(env, (size_t)n * 128 * 48, &pp, &ab_p));
+  NAPI_CALL(env, napi_create_arraybuffer(env, (size_t)n * 4, &ps, &ab_s));
+  const int32_t r = lb_kzg_recover_cells_and_proofs(b->e, n, (const uint32_t*)of.data, (const uint32_t*)ix.data,
+                                                    (const uint8_t*)ce.data, (uint8_t*)pc, (uint8_t*)pp, (int32_t*)ps);
+  if (r != LB_OK) return throw_code(env, r);
+  NAPI_CALL(env, napi_create_typedarray(env, napi_uint8_array, (size_t)n * 128 * LB_CELL_BYTES, ab_c, 0, &out_c));
+  NAPI_CALL(env, napi_create_typedarray(env, napi_uint8_array, (size_t)n * 128 * 48, ab_p, 0, &out_p));
+  NAPI_CALL(env, napi_create_typedarray(env, napi_int32_array, n, ab_s, 0, &out_s));
+  NAPI_CALL(env, napi_create_object(env, &obj));
+  NAPI_CALL(env, napi_set_named_property(env, obj, "cells", out_c));
+  NAPI_CALL(env, napi_set_named_property(env, obj, "proofs", out_p));
+  NAPI_CALL(env, napi_set_named_property(env, obj, "status", out_s));
+  return obj;
+}
+
 /* Many verifyCellKzgProofBatch groups in one pass (lb_kzg_verify_cell_proof_batch): group k owns
  * cells cellOffsets[k] .. cellOffsets[k + 1] - 1 of the flat per-cell arrays.  One int32 per group:
  * 1, 0, or -code, as the C call gives them; nothing is thrown for a group that rejects. */
@@ -1057,6 +1097,7 @@ static napi_value init(napi_env env, napi_value exports) {
       {"kzgVerifyBlobProofBatch", NULL, kzg_verify_blob_proof_batch, NULL, NULL, NULL, napi_default, NULL},
       {"kzgComputeCells", NULL, kzg_compute_cells, NULL, NULL, NULL, napi_default, NULL},
       {"kzgComputeCellsAndProofs", NULL, kzg_compute_cells_and_proofs, NULL, NULL, NULL, napi_default, NULL},
+      {"kzgRecoverCellsAndProofs", NULL, kzg_recover_cells_and_proofs, NULL, NULL, NULL, napi_default, NULL},
       {"kzgVerifyCellProofBatch", NULL, kzg_verify_cell_proof_batch, NULL, NULL, NULL, napi_default, NULL},
   };
   napi_define_properties(env, exports, sizeof(props) / sizeof(props[0]), props);

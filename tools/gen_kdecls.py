@@ -50,7 +50,7 @@ GROUPS = {
     # KZG scalar field (lb_kzg_field.h), beside the KZG group kernels of group 7
     16: ["k_fr_blob_load", "k_fr_aggregate", "k_fr_intt4096", "k_fr_eval_quotient", "k_fr_aggregate_seg",
          "k_fr_eval_many", "k_fr_eval_quotient_many", "k_fr_cell_load", "k_fr_coset_ntt4096", "k_fr_cell_interp",
-         "k_fr_cell_sum", "k_fr_cell_quotient"],
+         "k_fr_cell_sum", "k_fr_cell_quotient", "k_fr_recover_zero", "k_fr_recover_cols", "k_fr_ntt4096"],
     # FK20 (lb_kzg_fk20.h): the G1 transform, the table, the column transforms, the proofs' way out
     17: ["k_g1_fk_gather", "k_g1_fft128", "k_fr_fk_cols", "k_g1_jac_terms", "k_g1_fk_out48"],
 }
