@@ -462,6 +462,150 @@ LB_HD void g2_add_lean(g2j& p, const g2j& q) {
   p.y = fp2_sub(lean2_mul<kInl>(rr, fp2_sub(V, p.x)), fp2_dbl(lean2_mul<kInl>(S1, J)));
 }
 
+// ---- The psi-ladder in 28-bit limbs end to end (lb_field.h, fp2_28): the same formulas as
+// g2_dbl_lean and the mixed addition of k_sig_subgroup, every product fed by the limbs of the
+// previous one.  A ladder state is normalised (limbs 0..12 below 2^28) with
+//   X <= 30 p,  Y <= 12 p,  Z <= 3 p                                    (LB_L28_VX / VY / VZ)
+// per component.  The comments give each value's bound in units of p, a product's as
+// 1 + S / 2520 with S the sum of its operand products (for the Fp2 forms the larger of c0's and
+// c1's: c0 = a0 b0 + a1 (K - b1) <= a (b + C), the square's (2 a)(a + C)), and <C, S> of a
+// subtraction or product is sized to the bounds of what it subtracts: C above its value, 2^S -
+// 2^(S-28) above its limbs.  fp2_28_norm stands where a limb bound would otherwise break the
+// column condition of the next product, 14 (La Lb + Lc Ld) + 14 x 2^56 + 2^37 < 2^64 (the widest
+// here: a first operand of 4 x 2^28 against 2^28 and 2^29), or overflow a word.  The LB_FP28_CHECK host build
+// re-derives every bound here on the worst case and aborts where one fails.
+#define LB_L28_VX 30.0
+#define LB_L28_VY 12.0
+#define LB_L28_VZ 3.0
+struct g2j28 {
+  fp2_28 x, y, z;
+};
+#if defined(LB_FP28_CHECK)
+// the state's tracked bounds are within the invariant; continue from the invariant itself
+static inline void fp28_chk_assume(fp28& a, double vb) {
+  for (int k = 0; k < 13; k++) LB_CHK_ASSERT(a.ub[k] <= 0x0fffffffu);
+  LB_CHK_ASSERT(a.vb <= vb && a.ub[13] <= fp28_chk_top(vb));
+  fp28_chk_set(a, vb);
+}
+static inline void g2j28_chk_assume(g2j28& p) {
+  fp28_chk_assume(p.x.c0, LB_L28_VX), fp28_chk_assume(p.x.c1, LB_L28_VX);
+  fp28_chk_assume(p.y.c0, LB_L28_VY), fp28_chk_assume(p.y.c1, LB_L28_VY);
+  fp28_chk_assume(p.z.c0, LB_L28_VZ), fp28_chk_assume(p.z.c1, LB_L28_VZ);
+}
+#endif
+LB_HD g2j28 g2j28_from_aff(const fp2& x, const fp2& y) {  // below 1.0004 p each
+  return g2j28{fp2_28_from_fp2(x), fp2_28_from_fp2(y), fp2_28{fp28_one(), fp28_zero()}};
+}
+LB_HD g2j28 g2j28_infinity() {
+  return g2j28{fp2_28{fp28_one(), fp28_zero()}, fp2_28{fp28_one(), fp28_zero()}, fp2_28{fp28_zero(), fp28_zero()}};
+}
+// Z == 0 (mod p): the state is redundant, so the test converts down (fp28_is_zero); any value
+// below 2^392 is allowed, the state's 3 p is far inside
+LB_HD bool g2j28_is_inf(const g2j28& p) { return fp2_28_is_zero(p.z); }
+LB_HD g2j g2j28_to_g2j(const g2j28& p) {
+  g2j r;
+  r.x = fp2_28_to_fp2(p.x);
+  r.y = fp2_28_to_fp2(p.y);
+  r.z = fp2_28_to_fp2(p.z);
+  return r;
+}
+// dbl-2009-l in the statement order of g2_dbl_lean
+LB_HD void g2_dbl_lean28(g2j28& p) {
+  LB_CHK(g2j28_chk_assume(p);)
+  p.z = fp2_28_norm(fp2_28_muls<2>(fp2_28_mul<13, 28>(p.z, p.y)));  // 2 Y Z: 3 (12 + 13) -> 1.03; 2.06
+  const fp2_28 B = fp2_28_sqr<13, 28>(p.y);                         // 24 x 25 -> 1.24
+  const fp2_28 C = fp2_28_sqr<2, 28>(B);                            // 2.5 x 3.3 -> 1.004
+  const fp2_28 A = fp2_28_sqr<31, 28>(p.x);                         // 60 x 61 -> 2.46
+  fp2_28 D = fp2_28_sqr<32, 28>(fp2_28_norm(fp2_28_add(p.x, B)));   // X + B <= 31.3: 62.5 x 63.3 -> 2.57
+  D = fp2_28_norm(fp2_28_muls<2>(fp2_28_sub<4, 29>(D, fp2_28_add(A, C))));  // 2 (2.57 + 4) = 13.2; limbs 2^31
+  const fp2_28 E = fp2_28_norm(fp2_28_muls<3>(A));                  // 7.4
+  p.x = fp2_28_norm(fp2_28_sub<27, 29>(fp2_28_sqr<8, 28>(E), fp2_28_muls<2>(D)));  // 1.09 + 27 = 28.1
+  p.y = fp2_28_norm(fp2_28_sub<9, 31>(fp2_28_mul<8, 28>(fp2_28_sub<29, 28>(D, p.x), E),  // 42.2 (7.4 + 8) -> 1.26
+                                      fp2_28_muls<8>(C)));                              // + 9 = 10.3
+}
+// p + q, q affine and read through ld (ld(0) = x, ld(24) = y, 12-word Montgomery form), p finite:
+// madd-2007-bl with Z3 = 2 Z1 H as k_sig_subgroup had it.  Returns 0; or 1 for p == q, 2 for
+// p == -q, and then p is spent (the ladder replaces it in both cases).  q's coordinates enter as
+// the limbs of a 2^8 (up to 256 p) and meet Z1Z1 and Z1^3 (about 1 p) at once.
+// Five Fp2 values (140 registers) beside a product's 70 are what 256 registers hold, and the
+// formulas want six where q.y and then Y J meet the rest, so Y, and later 2 Y J, wait in the
+// caller's parking slot pk (put / get of one fp2_28: LDS in the kernel): the statement order below
+// is the live-range order, at most five values across any product.
+#if defined(__HIPCC__)
+#define LB_HDM __host__ __device__ __forceinline__
+#else
+#define LB_HDM inline
+#endif
+struct g2_park28 {  // the host's slot
+  fp2_28 v;
+  LB_HDM void put(const fp2_28& a) { v = a; }
+  LB_HDM fp2_28 get() const { return v; }
+};
+template <class Ld, class Pk>
+LB_HD int g2_madd_lean28(g2j28& p, Ld&& ld, Pk&& pk) {
+  LB_CHK(g2j28_chk_assume(p);)
+  pk.put(p.y);
+  const fp2_28 Z1Z1 = fp2_28_sqr<4, 28>(p.z);                                                      // 6 x 7 -> 1.02
+  const fp2_28 H = fp2_28_norm(fp2_28_sub<31, 28>(fp2_28_mul<2, 28>(fp2_28_from_fp2_shift(ld(0)), Z1Z1), p.x));  // 256 x 3.02 -> 1.31; 32.4
+  const fp2_28 t = fp2_28_mul<2, 28>(p.z, Z1Z1);                                                   // 1.004; Z1Z1 dead
+  const fp2_28 S2 = fp2_28_mul<2, 28>(fp2_28_from_fp2_shift(ld(24)), t);                           // 1.31; t dead
+  const fp2_28 rr = fp2_28_norm(fp2_28_muls<2>(fp2_28_sub<13, 28>(S2, pk.get())));                 // 2 (1.31 + 13) = 28.7
+  if (fp2_28_is_zero(H)) return fp2_28_is_zero(rr) ? 1 : 2;
+  p.z = fp2_28_norm(fp2_28_muls<2>(fp2_28_mul<4, 28>(H, p.z)));         // 32.4 x 7 -> 1.09; 2.2
+  const fp2_28 I = fp2_28_muls<4>(fp2_28_sqr<33, 28>(H));               // 64.7 x 65.4 -> 2.68; 10.8, limbs 2^30
+  const fp2_28 J = fp2_28_mul<33, 28>(I, H);                            // 10.8 x 65.4 -> 1.28; H dead
+  const fp2_28 V = fp2_28_mul<31, 28>(I, p.x);                          // 10.8 x 61 -> 1.27; X, I dead
+  pk.put(fp2_28_muls<2>(fp2_28_mul<2, 28>(pk.get(), J)));               // 2 Y J: 12 x 3.3 -> 1.02; 2.04
+  p.x = fp2_28_norm(fp2_28_sub<5, 30>(fp2_28_sqr<29, 28>(rr), fp2_28_add(J, fp2_28_muls<2>(V))));  // 57.4 x 57.7 -> 2.32; 7.32; J dead
+  const fp2_28 Y3 = fp2_28_mul<29, 28>(fp2_28_sub<8, 28>(V, p.x), rr);                             // 9.3 x 57.7 -> 1.22
+  p.y = fp2_28_norm(fp2_28_sub<3, 29>(Y3, pk.get()));                                              // 4.22
+  return 0;
+}
+// Scott's test psi(P) == [x]P for an affine P that is not infinity, P read through ld wherever it
+// is used (k_sig_subgroup re-reads it from memory, never holding it across the doublings).  The
+// exceptional additions (acc == +-P: points of small order outside G2) reuse the loop's one
+// doubling: acc = P, and the next pass's doubling yields acc + P = 2P for the same bit (redo).
+// The verdict is that of g2_aff_in_subgroup_i for every input: each decision is a test modulo p.
+template <class Ld, class Pk>
+LB_HD bool g2_aff_in_subgroup28(Ld&& ld, Pk&& pk) {
+  g2j28 acc = g2j28_from_aff(ld(0), ld(24));
+  bool redo = false;
+#pragma clang loop unroll(disable)
+  for (int b = 62; b >= 0;) {
+    g2_dbl_lean28(acc);
+    if (redo) {
+      redo = false;
+      b--;
+      continue;
+    }
+    if ((LB_X_ABS >> b) & 1ull) {
+      if (g2j28_is_inf(acc)) {
+        acc = g2j28_from_aff(ld(0), ld(24));
+        b--;
+        continue;
+      }
+      const int e = g2_madd_lean28(acc, ld, pk);
+      if (e == 1) {  // acc == P
+        acc = g2j28_from_aff(ld(0), ld(24));
+        redo = true;
+        continue;
+      }
+      if (e == 2) {  // acc == -P
+        acc = g2j28_infinity();
+        b--;
+        continue;
+      }
+    }
+    b--;
+  }
+  if (g2j28_is_inf(acc)) return false;  // psi(P) is finite
+  const g2j a = g2j28_to_g2j(acc);
+  const fp2 z2 = lean2_sqr<true>(a.z);
+  if (!fp2_eq(lean2_mul<true>(lean2_mul<true>(fp2_conj(ld(0)), fp2_load(LB_PSI_CX)), z2), a.x)) return false;
+  const fp2 py = lean2_mul<true>(fp2_conj(ld(24)), fp2_load(LB_PSI_CY));
+  return fp2_eq(lean2_mul<true>(lean2_mul<true>(py, z2), a.z), fp2_neg(a.y));
+}
+
 // The loop is kept rolled, and the base point is re-read from memory (`src`, the caller's
 // copy) at the five additions instead of being held across the 63 doublings.
 LB_HD bool g2_aff_in_subgroup_i(const g2a& a) {

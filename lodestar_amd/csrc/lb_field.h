@@ -342,8 +342,34 @@ LB_HD fp fp_sqr_inl(const fp& a) {
 // products: for inputs below 2^390 the output (ab + mp) / R' is below 2^388 + p, so every limb stays
 // below 2^28 and the column bounds of fp_mul28 / fp_sqr28 hold.  The end converts back with one
 // product by R mod p (r R / R' = r / 2^8 = x^e R), repacks and reduces once.
+// Host test builds (-DLB_FP28_CHECK, tests/native/fp2_28_check.cpp) verify the two bounds this form
+// rests on.  (1) On the actual values: no 64-bit column overflows (checked against a 128-bit sum)
+// and a product's top limb stays below 2^28.  (2) For the Fp2 layer below, on the worst case: every
+// fp28 carries an upper bound per limb (ub) and on its value in units of p (vb); the operations
+// propagate them and assert the column, borrow and value conditions on the bounds themselves, so a
+// run of straight-line formulas proves them for every input, not for the inputs of the run.
+#if defined(LB_FP28_CHECK)
+#include <stdio.h>
+#include <stdlib.h>
+#define LB_CHK(...) __VA_ARGS__
+#define LB_CHK_ASSERT(c)                                                                \
+  do {                                                                                  \
+    if (!(c)) {                                                                         \
+      fprintf(stderr, "fp28 bound violated: %s (%s:%d)\n", #c, __FILE__, __LINE__);     \
+      abort();                                                                          \
+    }                                                                                   \
+  } while (0)
+// acc + x * y stays below 2^64
+#define LB_COL_CHK(acc, x, y) \
+  LB_CHK_ASSERT((unsigned __int128)(acc) + (unsigned __int128)(x) * (y) <= (unsigned __int128)~0ull)
+#else
+#define LB_CHK(...)
+#define LB_CHK_ASSERT(c) ((void)0)
+#define LB_COL_CHK(acc, x, y) ((void)0)
+#endif
 struct fp28 {
   uint32_t l[14];
+  LB_CHK(uint64_t ub[14]; double vb;)
 };
 LB_HD fp28 fp28_mul_raw(const fp28& a, const fp28& b) {
   const uint32_t P28[14] = {LB_P28_0, LB_P28_1, LB_P28_2, LB_P28_3, LB_P28_4,  LB_P28_5,  LB_P28_6,
@@ -351,16 +377,25 @@ LB_HD fp28 fp28_mul_raw(const fp28& a, const fp28& b) {
   uint64_t acc[28];
   LB_UNROLL for (int k = 0; k < 28; k++) acc[k] = 0;
   LB_UNROLL for (int i = 0; i < 14; i++) {
-    LB_UNROLL for (int j = 0; j < 14; j++) acc[i + j] += (uint64_t)a.l[i] * b.l[j];
+    LB_UNROLL for (int j = 0; j < 14; j++) {
+      LB_COL_CHK(acc[i + j], a.l[i], b.l[j]);
+      acc[i + j] += (uint64_t)a.l[i] * b.l[j];
+    }
     const uint32_t m = ((uint32_t)acc[i] * LB_PINV28) & 0x0fffffffu;
-    LB_UNROLL for (int j = 0; j < 14; j++) acc[i + j] += (uint64_t)m * P28[j];
+    LB_UNROLL for (int j = 0; j < 14; j++) {
+      LB_COL_CHK(acc[i + j], m, P28[j]);
+      acc[i + j] += (uint64_t)m * P28[j];
+    }
+    LB_COL_CHK(acc[i + 1], acc[i] >> 28, 1u);
     acc[i + 1] += acc[i] >> 28;
   }
   fp28 r;
   LB_UNROLL for (int k = 0; k < 13; k++) {
     r.l[k] = (uint32_t)acc[14 + k] & 0x0fffffffu;
+    LB_COL_CHK(acc[15 + k], acc[14 + k] >> 28, 1u);
     acc[15 + k] += acc[14 + k] >> 28;
   }
+  LB_CHK_ASSERT(acc[27] < (1ull << 28));  // the value is below 2^392
   r.l[13] = (uint32_t)acc[27];
   return r;
 }
@@ -372,19 +407,30 @@ LB_HD fp28 fp28_sqr_raw(const fp28& a) {
   uint64_t acc[28];
   LB_UNROLL for (int k = 0; k < 28; k++) acc[k] = 0;
   LB_UNROLL for (int i = 0; i < 14; i++) {
+    LB_CHK_ASSERT(a.l[i] < (1u << 31));  // D[i] = 2 a_i fits a word
+    LB_COL_CHK(acc[2 * i], a.l[i], a.l[i]);
     acc[2 * i] += (uint64_t)a.l[i] * a.l[i];
-    LB_UNROLL for (int j = i + 1; j < 14; j++) acc[i + j] += (uint64_t)D[i] * a.l[j];
+    LB_UNROLL for (int j = i + 1; j < 14; j++) {
+      LB_COL_CHK(acc[i + j], D[i], a.l[j]);
+      acc[i + j] += (uint64_t)D[i] * a.l[j];
+    }
   }
   LB_UNROLL for (int i = 0; i < 14; i++) {
     const uint32_t m = ((uint32_t)acc[i] * LB_PINV28) & 0x0fffffffu;
-    LB_UNROLL for (int j = 0; j < 14; j++) acc[i + j] += (uint64_t)m * P28[j];
+    LB_UNROLL for (int j = 0; j < 14; j++) {
+      LB_COL_CHK(acc[i + j], m, P28[j]);
+      acc[i + j] += (uint64_t)m * P28[j];
+    }
+    LB_COL_CHK(acc[i + 1], acc[i] >> 28, 1u);
     acc[i + 1] += acc[i] >> 28;
   }
   fp28 r;
   LB_UNROLL for (int k = 0; k < 13; k++) {
     r.l[k] = (uint32_t)acc[14 + k] & 0x0fffffffu;
+    LB_COL_CHK(acc[15 + k], acc[14 + k] >> 28, 1u);
     acc[15 + k] += acc[14 + k] >> 28;
   }
+  LB_CHK_ASSERT(acc[27] < (1ull << 28));  // the value is below 2^392
   r.l[13] = (uint32_t)acc[27];
   return r;
 }
@@ -468,6 +514,306 @@ LB_HD fp fp_pow_const_28(const fp& a, const uint32_t* e, int top_bit) {
   }
   return fp_reduce_once(o, 0u);
 }
+
+// ---- Fp2 over fp28: curve formulas that stay in 28-bit limbs from product to product.
+// A value is any non-negative integer congruent to x R' (R' = 2^392), never reduced below p, in
+// limbs that may exceed 28 bits between products.  Two bounds keep this sound; with
+// R' / p = 2520.2 and p / 2^364 = 106513.1 both are stated in small numbers:
+//   value   a product's output is (S + m p) / R' with m < R', S the sum of its operand products:
+//           out < S / R' + p, that is out / p < 1 + (S / p^2) / 2520.  Operands of a few tens of p
+//           give outputs of 1..3 p, and S < 2520^2 p^2 keeps every output below 2^392.
+//   column  a 64-bit column collects 14 limb products per Fp product, 14 reduction terms below
+//           2^56 and one carry below 2^37: for limb bounds La, Lb (one product) or La Lb + Lc Ld
+//           summed (two products)   14 (La Lb + Lc Ld) + 14 (2^28 - 1)^2 + 2^37 <= 2^64 - 1,
+//           e.g. both sides of both products up to 2^29.5, or 2^31 against 2^28.
+// Linear operations work limb by limb, without carry chain, compare or select:
+//   a - b = a + K - b,  K = C p in a borrowed form: limb 0 + 2^S, limbs 1..12 + 2^S - 2^(S-28),
+//   limb 13 - 2^(S-28) (the same integer), so limbs 0..12 of K are at least 2^S - 2^(S-28) and
+//   cover any b whose limbs are below that; limb 13 of K must cover b's top limb, which bounds C
+//   from below by b's value.  The result grows by C p in value and 2^S + 2^28 per limb.
+//   fp28_norm is the one carry pass that brings limbs 0..12 back below 2^28 (the value stays).
+// The bounds are derived per call site (lb_curve.h: g2_dbl_lean28, g2_madd_lean28) and enforced by
+// the LB_FP28_CHECK host build on the worst case, see above.
+LB_HD constexpr uint32_t lb_k28_limb(uint32_t c, int s, int i) {
+  const uint32_t P28[14] = {LB_P28_0, LB_P28_1, LB_P28_2, LB_P28_3, LB_P28_4,  LB_P28_5,  LB_P28_6,
+                            LB_P28_7, LB_P28_8, LB_P28_9, LB_P28_10, LB_P28_11, LB_P28_12, LB_P28_13};
+  uint64_t carry = 0, k = 0;
+  for (int j = 0; j <= i; j++) {
+    const uint64_t t = (uint64_t)c * P28[j] + carry;
+    k = j < 13 ? (t & 0x0fffffffu) : t;
+    carry = t >> 28;
+  }
+  const uint64_t b = 1ull << s, bh = 1ull << (s - 28);
+  return (uint32_t)(i == 0 ? k + b : i < 13 ? k + b - bh : k - bh);
+}
+#define LB_K28(C, S)                                                                                          \
+  {lb_k28_limb(C, S, 0), lb_k28_limb(C, S, 1), lb_k28_limb(C, S, 2),  lb_k28_limb(C, S, 3),  lb_k28_limb(C, S, 4), \
+   lb_k28_limb(C, S, 5), lb_k28_limb(C, S, 6), lb_k28_limb(C, S, 7),  lb_k28_limb(C, S, 8),  lb_k28_limb(C, S, 9), \
+   lb_k28_limb(C, S, 10), lb_k28_limb(C, S, 11), lb_k28_limb(C, S, 12), lb_k28_limb(C, S, 13)}
+
+#if defined(LB_FP28_CHECK)
+// top-limb bound of a value below vb p whose limbs 0..12 are non-negative
+static inline uint64_t fp28_chk_top(double vb) { return (uint64_t)(vb * 106513.2) + 1; }
+// a value known to be below vb p with limbs 0..12 below 2^28
+static inline void fp28_chk_set(fp28& a, double vb) {
+  for (int k = 0; k < 13; k++) a.ub[k] = 0x0fffffffu;
+  a.ub[13] = fp28_chk_top(vb) < 0x0fffffffu ? fp28_chk_top(vb) : 0x0fffffffu;
+  a.vb = vb;
+}
+static inline void fp28_chk_in(const fp28& a) {
+  for (int k = 0; k < 14; k++) LB_CHK_ASSERT(a.l[k] <= a.ub[k]);
+}
+// worst-case columns of (a b + c d) / R' (c, d may be null) and the bounds of the result
+static inline void fp28_chk_mac(const fp28& a, const fp28& b, const fp28* c, const fp28* d, fp28& r) {
+  const uint32_t P28[14] = {LB_P28_0, LB_P28_1, LB_P28_2, LB_P28_3, LB_P28_4,  LB_P28_5,  LB_P28_6,
+                            LB_P28_7, LB_P28_8, LB_P28_9, LB_P28_10, LB_P28_11, LB_P28_12, LB_P28_13};
+  typedef unsigned __int128 u128;
+  const u128 lim = (u128)~0ull;
+  fp28_chk_in(a), fp28_chk_in(b);
+  if (c) fp28_chk_in(*c), fp28_chk_in(*d);
+  u128 col[29];
+  for (int k = 0; k < 29; k++) col[k] = 0;
+  for (int i = 0; i < 14; i++) {
+    for (int j = 0; j < 14; j++) {
+      col[i + j] += (u128)a.ub[i] * b.ub[j] + (u128)0x0fffffffu * P28[j];
+      if (c) col[i + j] += (u128)c->ub[i] * d->ub[j];
+    }
+    LB_CHK_ASSERT(col[i] <= lim);
+    col[i + 1] += col[i] >> 28;
+  }
+  for (int k = 14; k < 28; k++) {
+    LB_CHK_ASSERT(col[k] <= lim);
+    col[k + 1] += col[k] >> 28;
+  }
+  const double s = a.vb * b.vb + (c ? c->vb * d->vb : 0.0);
+  const double vb = (1.0 + s / 2520.0) * (1.0 + 1e-9);
+  LB_CHK_ASSERT(vb < 2520.0);  // below 2^392
+  fp28_chk_set(r, vb);
+}
+#endif
+
+struct fp2_28 {
+  fp28 c0, c1;
+};
+LB_HD fp28 fp28_add(const fp28& a, const fp28& b) {
+  fp28 r;
+  LB_UNROLL for (int k = 0; k < 14; k++) {
+    r.l[k] = a.l[k] + b.l[k];
+    LB_CHK(r.ub[k] = a.ub[k] + b.ub[k]; LB_CHK_ASSERT(r.ub[k] <= 0xffffffffull);)
+  }
+  LB_CHK(r.vb = a.vb + b.vb;)
+  return r;
+}
+template <int N>  // N a: 2, 3, 4, 8 by shifts and adds
+LB_HD fp28 fp28_muls(const fp28& a) {
+  fp28 r;
+  LB_UNROLL for (int k = 0; k < 14; k++) {
+    r.l[k] = N == 3 ? (a.l[k] << 1) + a.l[k] : a.l[k] << (N == 2 ? 1 : N == 4 ? 2 : 3);
+    LB_CHK(r.ub[k] = N * a.ub[k]; LB_CHK_ASSERT(r.ub[k] <= 0xffffffffull);)
+  }
+  LB_CHK(r.vb = N * a.vb;)
+  return r;
+}
+// a + K - b, K = C p borrowed at 2^S: needs b's limbs 0..12 <= 2^S - 2^(S-28) and b's top limb <=
+// K's; the value grows by at most C p.  fp28_kminus is K - b alone.
+template <uint32_t C, int S>
+LB_HD fp28 fp28_kminus(const fp28& b) {
+  constexpr uint32_t K[14] = LB_K28(C, S);
+  fp28 r;
+  LB_UNROLL for (int k = 0; k < 14; k++) {
+    r.l[k] = K[k] - b.l[k];
+    LB_CHK(LB_CHK_ASSERT(b.ub[k] <= K[k]); r.ub[k] = K[k];)
+  }
+  LB_CHK(r.vb = C;)
+  return r;
+}
+template <uint32_t C, int S>
+LB_HD fp28 fp28_sub(const fp28& a, const fp28& b) {
+  constexpr uint32_t K[14] = LB_K28(C, S);
+  fp28 r;
+  LB_UNROLL for (int k = 0; k < 14; k++) {
+    r.l[k] = a.l[k] + K[k] - b.l[k];
+    LB_CHK(LB_CHK_ASSERT(b.ub[k] <= K[k]); r.ub[k] = a.ub[k] + K[k]; LB_CHK_ASSERT(r.ub[k] <= 0xffffffffull);)
+  }
+  LB_CHK(r.vb = a.vb + C;)
+  return r;
+}
+// one carry pass: limbs 0..12 below 2^28 again, the top limb takes the rest
+LB_HD fp28 fp28_norm(const fp28& a) {
+  fp28 r;
+  uint32_t c = 0;
+  LB_CHK(uint64_t cb = 0;)
+  LB_UNROLL for (int k = 0; k < 13; k++) {
+    const uint32_t t = a.l[k] + c;
+    LB_CHK(LB_CHK_ASSERT(a.ub[k] + cb <= 0xffffffffull); cb = (a.ub[k] + cb) >> 28;)
+    r.l[k] = t & 0x0fffffffu;
+    c = t >> 28;
+  }
+  r.l[13] = a.l[13] + c;
+  LB_CHK(const uint64_t top = a.ub[13] + cb; fp28_chk_set(r, a.vb); if (top < r.ub[13]) r.ub[13] = top;)
+  return r;
+}
+// a b / R' and (a b + c d) / R': one set of 28 columns, one reduction; fenced like fp28_mul
+LB_HD fp28 fp28_mulx(const fp28& a, const fp28& b) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  __builtin_amdgcn_sched_barrier(0);
+#endif
+  fp28 r = fp28_mul_raw(a, b);
+#if defined(__HIP_DEVICE_COMPILE__)
+  __builtin_amdgcn_sched_barrier(0);
+#endif
+  LB_CHK(fp28_chk_mac(a, b, nullptr, nullptr, r);)
+  return r;
+}
+LB_HD fp28 fp28_mac2(const fp28& a, const fp28& b, const fp28& c, const fp28& d) {
+  const uint32_t P28[14] = {LB_P28_0, LB_P28_1, LB_P28_2, LB_P28_3, LB_P28_4,  LB_P28_5,  LB_P28_6,
+                            LB_P28_7, LB_P28_8, LB_P28_9, LB_P28_10, LB_P28_11, LB_P28_12, LB_P28_13};
+#if defined(__HIP_DEVICE_COMPILE__)
+  __builtin_amdgcn_sched_barrier(0);
+#endif
+  uint64_t acc[28];
+  LB_UNROLL for (int k = 0; k < 28; k++) acc[k] = 0;
+  LB_UNROLL for (int i = 0; i < 14; i++) {
+    LB_UNROLL for (int j = 0; j < 14; j++) {
+      LB_COL_CHK(acc[i + j], a.l[i], b.l[j]);
+      acc[i + j] += (uint64_t)a.l[i] * b.l[j];
+    }
+    LB_UNROLL for (int j = 0; j < 14; j++) {
+      LB_COL_CHK(acc[i + j], c.l[i], d.l[j]);
+      acc[i + j] += (uint64_t)c.l[i] * d.l[j];
+    }
+    const uint32_t m = ((uint32_t)acc[i] * LB_PINV28) & 0x0fffffffu;
+    LB_UNROLL for (int j = 0; j < 14; j++) {
+      LB_COL_CHK(acc[i + j], m, P28[j]);
+      acc[i + j] += (uint64_t)m * P28[j];
+    }
+    LB_COL_CHK(acc[i + 1], acc[i] >> 28, 1u);
+    acc[i + 1] += acc[i] >> 28;
+  }
+  fp28 r;
+  LB_UNROLL for (int k = 0; k < 13; k++) {
+    r.l[k] = (uint32_t)acc[14 + k] & 0x0fffffffu;
+    LB_COL_CHK(acc[15 + k], acc[14 + k] >> 28, 1u);
+    acc[15 + k] += acc[14 + k] >> 28;
+  }
+  LB_CHK_ASSERT(acc[27] < (1ull << 28));
+  r.l[13] = (uint32_t)acc[27];
+#if defined(__HIP_DEVICE_COMPILE__)
+  __builtin_amdgcn_sched_barrier(0);
+#endif
+  LB_CHK(fp28_chk_mac(a, b, &c, &d, r);)
+  return r;
+}
+
+// conversions.  fp28_from_fp: the 12-word Montgomery value a = x R as plain limbs (below p) times
+// 2^400 mod p: x R 2^400 / R' = x R', below 1.0004 p.  fp28_from_fp_shift: the limbs of a 2^8, no
+// product, but a value up to 256 p: for operands that meet a small partner in a product at once.
+// fp28_to_fp: one product by R mod p (r R / R' = x R, below 2 p for r below 2520 p), repacked and
+// reduced once: the canonical 12 words.
+LB_HD fp28 fp28_one() {
+  const uint32_t c[14] = {LB_R28_ONE_0, LB_R28_ONE_1, LB_R28_ONE_2, LB_R28_ONE_3, LB_R28_ONE_4,  LB_R28_ONE_5,  LB_R28_ONE_6,
+                          LB_R28_ONE_7, LB_R28_ONE_8, LB_R28_ONE_9, LB_R28_ONE_10, LB_R28_ONE_11, LB_R28_ONE_12, LB_R28_ONE_13};
+  fp28 r;
+  LB_UNROLL for (int k = 0; k < 14; k++) r.l[k] = c[k];
+  LB_CHK(fp28_chk_set(r, 1.0);)
+  return r;
+}
+LB_HD fp28 fp28_zero() {
+  fp28 r;
+  LB_UNROLL for (int k = 0; k < 14; k++) r.l[k] = 0;
+  LB_CHK(fp28_chk_set(r, 1.0);)
+  return r;
+}
+LB_HD fp28 fp28_from_fp_shift(const fp& a) {
+  fp28 r;
+  r.l[0] = (a.v[0] << 8) & 0x0fffffffu;
+  LB_UNROLL for (int k = 1; k < 14; k++) r.l[k] = lb_bits28(a.v, 28 * k - 8);
+  LB_CHK(fp28_chk_set(r, 256.0);)
+  return r;
+}
+LB_HD fp28 fp28_from_fp(const fp& a) {
+  const uint32_t c[14] = {LB_R28_IN_0, LB_R28_IN_1, LB_R28_IN_2, LB_R28_IN_3, LB_R28_IN_4,  LB_R28_IN_5,  LB_R28_IN_6,
+                          LB_R28_IN_7, LB_R28_IN_8, LB_R28_IN_9, LB_R28_IN_10, LB_R28_IN_11, LB_R28_IN_12, LB_R28_IN_13};
+  fp28 x, k;
+  LB_UNROLL for (int i = 0; i < 14; i++) x.l[i] = lb_bits28(a.v, 28 * i), k.l[i] = c[i];
+  LB_CHK(fp28_chk_set(x, 1.0); fp28_chk_set(k, 1.0);)
+  return fp28_mulx(x, k);
+}
+LB_HD fp fp28_to_fp(const fp28& a) {
+  const fp one = fp_one();
+  fp28 c;
+  LB_UNROLL for (int k = 0; k < 14; k++) c.l[k] = lb_bits28(one.v, 28 * k);
+  LB_CHK(fp28_chk_set(c, 1.0);)
+  const fp28 t = fp28_mulx(a, c);
+  LB_CHK_ASSERT(t.vb < 2.0);
+  uint32_t o[12];
+  LB_UNROLL for (int w = 0; w < 12; w++) {
+    const int l = (32 * w) / 28, s = 32 * w - 28 * l;
+    o[w] = (t.l[l] >> s) | (t.l[l + 1] << (28 - s));
+  }
+  return fp_reduce_once(o, 0u);
+}
+// a == 0 (mod p) on the redundant form, by converting down: the Montgomery reduction alone,
+// t = (a + m p) / R' < a / R' + p, is congruent to a / R' and below 2 p for every a below 2^392,
+// so t is 0 or p exactly when p divides a; t's limbs are canonical (13 masked, the rest on top).
+LB_HD bool fp28_is_zero(const fp28& a) {
+  const uint32_t P28[14] = {LB_P28_0, LB_P28_1, LB_P28_2, LB_P28_3, LB_P28_4,  LB_P28_5,  LB_P28_6,
+                            LB_P28_7, LB_P28_8, LB_P28_9, LB_P28_10, LB_P28_11, LB_P28_12, LB_P28_13};
+  LB_CHK(fp28_chk_in(a); LB_CHK_ASSERT(a.vb < 2520.0);)
+  uint64_t acc[28];
+  LB_UNROLL for (int k = 0; k < 28; k++) acc[k] = k < 14 ? a.l[k] : 0;
+  LB_UNROLL for (int i = 0; i < 14; i++) {
+    const uint32_t m = ((uint32_t)acc[i] * LB_PINV28) & 0x0fffffffu;
+    LB_UNROLL for (int j = 0; j < 14; j++) acc[i + j] += (uint64_t)m * P28[j];  // < 2^32 + 14 2^56 + 2^37
+    acc[i + 1] += acc[i] >> 28;
+  }
+  uint32_t z = 0, e = 0;
+  LB_UNROLL for (int k = 0; k < 14; k++) {
+    const uint32_t t = k < 13 ? ((uint32_t)acc[14 + k] & 0x0fffffffu) : (uint32_t)acc[27];
+    if (k < 13) acc[15 + k] += acc[14 + k] >> 28;
+    z |= t;
+    e |= t ^ P28[k];
+  }
+  return z == 0 || e == 0;
+}
+
+// Fp2 = Fp[u] / (u^2 + 1) on the form above.  C, S of a product describe its SECOND operand (the
+// K that covers b.c1, or a.c1 for the square): choose it as the operand with the smaller bounds.
+LB_HD fp2_28 fp2_28_add(const fp2_28& a, const fp2_28& b) { return fp2_28{fp28_add(a.c0, b.c0), fp28_add(a.c1, b.c1)}; }
+template <int N>
+LB_HD fp2_28 fp2_28_muls(const fp2_28& a) {
+  return fp2_28{fp28_muls<N>(a.c0), fp28_muls<N>(a.c1)};
+}
+template <uint32_t C, int S>
+LB_HD fp2_28 fp2_28_sub(const fp2_28& a, const fp2_28& b) {
+  return fp2_28{fp28_sub<C, S>(a.c0, b.c0), fp28_sub<C, S>(a.c1, b.c1)};
+}
+LB_HD fp2_28 fp2_28_norm(const fp2_28& a) { return fp2_28{fp28_norm(a.c0), fp28_norm(a.c1)}; }
+// (a0 + a1 u)(b0 + b1 u) without Karatsuba: c0 = a0 b0 + a1 (K - b1), c1 = a0 b1 + a1 b0, each
+// accumulated into one set of columns and reduced once (4 x 196 + 2 x 196 multiply-adds; no
+// additions or subtractions around the products but the 14 that form K - b1)
+template <uint32_t C, int S>
+LB_HD fp2_28 fp2_28_mul(const fp2_28& a, const fp2_28& b) {
+  const fp28 nb1 = fp28_kminus<C, S>(b.c1);
+  fp2_28 r;
+  r.c0 = fp28_mac2(a.c0, b.c0, a.c1, nb1);
+  r.c1 = fp28_mac2(a.c0, b.c1, a.c1, b.c0);
+  return r;
+}
+// c0 = (a0 + a1)(a0 + K - a1), c1 = (2 a0) a1
+template <uint32_t C, int S>
+LB_HD fp2_28 fp2_28_sqr(const fp2_28& a) {
+  fp2_28 r;
+  r.c0 = fp28_mulx(fp28_add(a.c0, a.c1), fp28_sub<C, S>(a.c0, a.c1));
+  r.c1 = fp28_mulx(fp28_muls<2>(a.c0), a.c1);
+  return r;
+}
+// (both reductions always: a branch between them would merge the limbs' register pairs of the two
+// paths and lose that their high words are zero, which the products after it pay for)
+LB_HD bool fp2_28_is_zero(const fp2_28& a) { return fp28_is_zero(a.c0) & fp28_is_zero(a.c1); }
+LB_HD fp2_28 fp2_28_from_fp2(const fp2& a) { return fp2_28{fp28_from_fp(a.c0), fp28_from_fp(a.c1)}; }
+LB_HD fp2_28 fp2_28_from_fp2_shift(const fp2& a) { return fp2_28{fp28_from_fp_shift(a.c0), fp28_from_fp_shift(a.c1)}; }
+LB_HD fp2 fp2_28_to_fp2(const fp2_28& a) { return fp2{fp28_to_fp(a.c0), fp28_to_fp(a.c1)}; }
 
 template <bool kInlMul = false>
 LB_HD fp fp_pow_const_i(fp a, const uint32_t* e, int top_bit) {

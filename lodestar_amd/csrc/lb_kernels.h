@@ -219,72 +219,37 @@ __global__ void __launch_bounds__(LB_TPB, LB_MINW_SUB) k_sig_subgroup(uint32_t n
   uint32_t i = lb_tid();
   if (i >= n) return;
   if (sig_status[i] != LB_OK || sig_inf[i]) return;
-  // Scott's test psi(P) == [x]P with [|x|]P by the register-lean ladder (lb_curve.h), its Fp
-  // products inline (no call-boundary spills).  P is
+  // Scott's test psi(P) == [x]P with [|x|]P by the ladder in 28-bit limbs (lb_curve.h
+  // g2_aff_in_subgroup28), every product inline (no call-boundary spills).  P is
   // re-read from memory coordinate by coordinate where the additions use it, through a base
-  // pointer re-derived at each read: otherwise the compiler hoists the 48 row addresses (96
-  // VGPRs) out of the ladder and spills them (696 B of private segment per lane before)
+  // pointer and a lane index re-derived at each read: otherwise the compiler hoists the 48 row
+  // addresses (96 VGPRs) out of the ladder and spills them (696 B of private segment per lane
+  // before), or keeps the lane's 64-bit offsets across it in scratch
   auto load_f2 = [&](int o) {
     const uint32_t* base = sig_aff;
-    asm volatile("" : "+s"(base));
+    uint32_t l = i;
+    asm volatile("" : "+s"(base), "+v"(l));
     fp2 a;
     uint32_t* w = reinterpret_cast<uint32_t*>(&a);
-    LB_UNROLL for (int k = 0; k < 24; k++) w[k] = __builtin_nontemporal_load(base + (size_t)(k + o) * n + i);
+    LB_UNROLL for (int k = 0; k < 24; k++) w[k] = __builtin_nontemporal_load(base + (size_t)(k + o) * n + l);
     return a;
   };
-  g2j acc = jac_from_aff(g2a{load_f2(0), load_f2(24)});
-  // the exceptional additions (acc == +-P: points of small order outside G2) reuse the loop's one
-  // doubling: acc = P, and the next pass's doubling yields acc + P = 2P for the same bit (redo)
-  bool redo = false;
-#pragma clang loop unroll(disable)
-  for (int b = 62; b >= 0;) {
-    g2_dbl_lean<true>(acc);
-    if (redo) {
-      redo = false;
-      b--;
-      continue;
+  // the mixed additions' parking slot (lb_curve.h g2_madd_lean28): one fp2_28 per lane, word k of
+  // lane l at 64 k + l (conflict-free); a lane reads only what it wrote, so no barrier
+  __shared__ uint32_t park[28 * LB_TPB];
+  struct {
+    uint32_t* s;
+    __device__ __forceinline__ void put(const fp2_28& a) {
+      LB_UNROLL for (int k = 0; k < 14; k++) s[LB_TPB * k] = a.c0.l[k], s[LB_TPB * (14 + k)] = a.c1.l[k];
     }
-    if ((LB_X_ABS >> b) & 1ull) {
-      if (jac_is_inf(acc)) {
-        acc = jac_from_aff(g2a{load_f2(0), load_f2(24)});
-        b--;
-        continue;
-      }
-      // acc + P (madd-2007-bl with Z3 = 2 Z1 H), ordered so Z1Z1 dies before the Karatsuba temporaries
-      const fp2 Z1Z1 = lean2_sqr<true>(acc.z);
-      const fp2 H = fp2_sub(lean2_mul<true>(load_f2(0), Z1Z1), acc.x);
-      const fp2 t = lean2_mul<true>(acc.z, Z1Z1);
-      const fp2 rr = fp2_dbl(fp2_sub(lean2_mul<true>(load_f2(24), t), acc.y));
-      if (fp2_is_zero(H)) {
-        if (fp2_is_zero(rr)) {  // acc == P
-          acc = jac_from_aff(g2a{load_f2(0), load_f2(24)});
-          redo = true;
-        } else {  // acc == -P
-          acc = jac_infinity<fp2>();
-          b--;
-        }
-        continue;
-      }
-      acc.z = fp2_dbl(lean2_mul<true>(acc.z, H));
-      const fp2 I = fp2_mul4(lean2_sqr<true>(H));
-      const fp2 J = lean2_mul<true>(H, I);
-      const fp2 V = lean2_mul<true>(acc.x, I);
-      const fp2 YJ = fp2_dbl(lean2_mul<true>(acc.y, J));
-      acc.x = fp2_sub(fp2_sub(lean2_sqr<true>(rr), J), fp2_dbl(V));
-      acc.y = fp2_sub(lean2_mul<true>(rr, fp2_sub(V, acc.x)), YJ);
+    __device__ __forceinline__ fp2_28 get() const {
+      fp2_28 a;
+      LB_UNROLL for (int k = 0; k < 14; k++) a.c0.l[k] = s[LB_TPB * k], a.c1.l[k] = s[LB_TPB * (14 + k)];
+      return a;
     }
-    b--;
-  }
-  bool ok = !jac_is_inf(acc);  // psi(P) is finite
-  if (ok) {
-    const fp2 z2 = lean2_sqr<true>(acc.z);
-    ok = fp2_eq(lean2_mul<true>(lean2_mul<true>(fp2_conj(load_f2(0)), fp2_load(LB_PSI_CX)), z2),
-                acc.x);
-    if (ok) {
-      const fp2 py = lean2_mul<true>(fp2_conj(load_f2(24)), fp2_load(LB_PSI_CY));
-      ok = fp2_eq(lean2_mul<true>(lean2_mul<true>(py, z2), acc.z), fp2_neg(acc.y));
-    }
-  }
+  } pk{park + threadIdx.x};
+  const bool ok = g2_aff_in_subgroup28(load_f2, pk);
+  asm volatile("" : "+v"(i));  // the status address from the index again, not kept across the ladder
   if (!ok) sig_status[i] = LB_POINT_NOT_IN_GROUP;
 }
 #endif  // LB_KG
