@@ -802,7 +802,7 @@ static hipError_t per_root_chain(lb_engine* e, uint32_t n, uint32_t nuh, uint32_
       hipLaunchKernelGGL(k_miller_wave, dim3(nuh), dim3(64), 0, s1, n, mu, nu, e->gp_aff.as<uint32_t>(),
                          e->gp_inf.as<uint32_t>(), e->h_aff.as<uint32_t>(), e->treeP.as<uint32_t>());
     } else if (shared) {
-      hipError_t r = e->park.ensure((size_t)2 * 72 * 4 * n);  // T and a temporary per root
+      hipError_t r = e->park.ensure((size_t)2 * 84 * 4 * n);  // T and a temporary per root: two slots of 3 fp2_28
       if (r != hipSuccess) return r;
       if (nuh <= e->miller_lds3_max)
         hipLaunchKernelGGL(k_miller_lane<3>, dim3(nblk(nuh)), dim3(LB_TPB), 0, s1, n, mu, nu, e->gp_aff.as<uint32_t>(),

@@ -154,7 +154,7 @@ struct lb_engine {
   uint32_t row_max = 256;
   int miller_form = 0;  // 0 by load, 1 lane, 2 g8
   // one-lane Miller loops with f and a temporary in LDS (two waves per CU) up to this many roots,
-  // f alone in LDS (one wave per SIMD) above: LB_MILLER_LDS3_MAX (lb_kernels.h k_miller_lane)
+  // f alone in LDS (three waves per CU) above: LB_MILLER_LDS3_MAX (lb_kernels.h k_miller_lane)
   uint32_t miller_lds3_max = 32768;
   // ... and hash_to_G2's cofactor clearing with 8 lanes per root (k_hash_finish_g8).  LB_HASH_G8_MAX.
   uint32_t hash_g8_max = 2048;

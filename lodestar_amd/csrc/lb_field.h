@@ -620,6 +620,7 @@ template <uint32_t C, int S>
 LB_HD fp28 fp28_kminus(const fp28& b) {
   constexpr uint32_t K[14] = LB_K28(C, S);
   fp28 r;
+  LB_CHK(if (b.ub[13] > K[13]) fprintf(stderr, "K = %u p does not cover a value of %.2f p\n", C, b.vb);)
   LB_UNROLL for (int k = 0; k < 14; k++) {
     r.l[k] = K[k] - b.l[k];
     LB_CHK(LB_CHK_ASSERT(b.ub[k] <= K[k]); r.ub[k] = K[k];)
@@ -631,6 +632,7 @@ template <uint32_t C, int S>
 LB_HD fp28 fp28_sub(const fp28& a, const fp28& b) {
   constexpr uint32_t K[14] = LB_K28(C, S);
   fp28 r;
+  LB_CHK(if (b.ub[13] > K[13]) fprintf(stderr, "K = %u p does not cover a value of %.2f p\n", C, b.vb);)
   LB_UNROLL for (int k = 0; k < 14; k++) {
     r.l[k] = a.l[k] + K[k] - b.l[k];
     LB_CHK(LB_CHK_ASSERT(b.ub[k] <= K[k]); r.ub[k] = a.ub[k] + K[k]; LB_CHK_ASSERT(r.ub[k] <= 0xffffffffull);)
@@ -814,6 +816,104 @@ LB_HD bool fp2_28_is_zero(const fp2_28& a) { return fp28_is_zero(a.c0) & fp28_is
 LB_HD fp2_28 fp2_28_from_fp2(const fp2& a) { return fp2_28{fp28_from_fp(a.c0), fp28_from_fp(a.c1)}; }
 LB_HD fp2_28 fp2_28_from_fp2_shift(const fp2& a) { return fp2_28{fp28_from_fp_shift(a.c0), fp28_from_fp_shift(a.c1)}; }
 LB_HD fp2 fp2_28_to_fp2(const fp2_28& a) { return fp2{fp28_to_fp(a.c0), fp28_to_fp(a.c1)}; }
+
+// ---- Fp6 = Fp2[v] / (v^3 - xi), xi = 1 + u, and the sparse Fp12 products of the Miller loop on
+// the form above (k_miller_lane, lb_pairing.h).  The products read their operands coefficient by
+// coefficient through a(i), b(i) and hand each finished coefficient to out(i, .), so a caller
+// whose Fp6 values live in memory slots never holds a whole one in registers: operand sums are
+// formed where they are used and a result goes straight to its slot.  Every out() value is
+// normalised.  The template constants are the C of each subtraction (its S is fixed by the limb
+// bound written beside it); the call sites in lb_pairing.h give the values they are sized for.
+struct fp6_28 {
+  fp2_28 c0, c1, c2;
+};
+// a xi = (a0 - a1) + (a0 + a1) u: one a + K - b and one limb-wise add
+template <uint32_t C, int S>
+LB_HD fp2_28 fp2_28_mul_xi(const fp2_28& a) {
+  return fp2_28{fp28_sub<C, S>(a.c0, a.c1), fp28_add(a.c0, a.c1)};
+}
+template <uint32_t C, int S>
+LB_HD fp2_28 fp2_28_kminus(const fp2_28& a) {
+  return fp2_28{fp28_kminus<C, S>(a.c0), fp28_kminus<C, S>(a.c1)};
+}
+LB_HD fp6_28 fp6_28_add(const fp6_28& a, const fp6_28& b) {
+  return fp6_28{fp2_28_add(a.c0, b.c0), fp2_28_add(a.c1, b.c1), fp2_28_add(a.c2, b.c2)};
+}
+template <uint32_t C, int S>
+LB_HD fp6_28 fp6_28_sub(const fp6_28& a, const fp6_28& b) {
+  return fp6_28{fp2_28_sub<C, S>(a.c0, b.c0), fp2_28_sub<C, S>(a.c1, b.c1), fp2_28_sub<C, S>(a.c2, b.c2)};
+}
+template <uint32_t C, int S>  // a v = (xi a2, a0, a1)
+LB_HD fp6_28 fp6_28_mul_v(const fp6_28& a) {
+  return fp6_28{fp2_28_mul_xi<C, S>(a.c2), a.c0, a.c1};
+}
+LB_HD fp6_28 fp6_28_norm(const fp6_28& a) { return fp6_28{fp2_28_norm(a.c0), fp2_28_norm(a.c1), fp2_28_norm(a.c2)}; }
+// Karatsuba a b (the product tree of fp6_mul_inl), a(i), b(i) normalised and none of them written
+// by out.  CB covers one coefficient of b, CB2 the sum of two, CT the sum of two of t0..t2, CX
+// m12 + K - (t1 + t2), CXT one of t0..t2.  6 products, 6 fp2_28_norm.
+template <uint32_t CB, uint32_t CB2, uint32_t CT, uint32_t CX, uint32_t CXT, class A, class B, class O>
+LB_HD void fp6_28_mul_to(A&& a, B&& b, O&& out) {
+  const fp2_28 t0 = fp2_28_mul<CB, 28>(a(0), b(0));
+  const fp2_28 t1 = fp2_28_mul<CB, 28>(a(1), b(1));
+  const fp2_28 t2 = fp2_28_mul<CB, 28>(a(2), b(2));
+  {  // c0 = xi ((a1 + a2)(b1 + b2) - t1 - t2) + t0: sums' limbs 2^29; x's 4 x 2^28; xi x's 13 x 2^28
+    const fp2_28 m = fp2_28_mul<CB2, 29>(fp2_28_add(a(1), a(2)), fp2_28_add(b(1), b(2)));
+    const fp2_28 x = fp2_28_sub<CT, 29>(m, fp2_28_add(t1, t2));
+    out(0, fp2_28_norm(fp2_28_add(fp2_28_mul_xi<CX, 31>(x), t0)));
+  }
+  {  // c1 = (a0 + a1)(b0 + b1) - t0 - t1 + xi t2
+    const fp2_28 m = fp2_28_mul<CB2, 29>(fp2_28_add(a(0), a(1)), fp2_28_add(b(0), b(1)));
+    out(1, fp2_28_norm(fp2_28_add(fp2_28_sub<CT, 29>(m, fp2_28_add(t0, t1)), fp2_28_mul_xi<CXT, 28>(t2))));
+  }
+  {  // c2 = (a0 + a2)(b0 + b2) - t0 - t2 + t1
+    const fp2_28 m = fp2_28_mul<CB2, 29>(fp2_28_add(a(0), a(2)), fp2_28_add(b(0), b(2)));
+    out(2, fp2_28_norm(fp2_28_add(fp2_28_sub<CT, 29>(m, fp2_28_add(t0, t2)), t1)));
+  }
+}
+// a (b0 + b1 v) (fp6_mul_01), bs = b0 + b1; b0, b1, bs normalised, a's limbs up to 2^29.  out may
+// write the slot a is read from: a(0), a(1) are read before the first out, a(2) after out(1) only.
+// CB0, CB1, CBS cover b0, b1, bs; CT covers t0 + t1; CX covers a2 b1.  5 products, 3 fp2_28_norm.
+template <uint32_t CB0, uint32_t CB1, uint32_t CBS, uint32_t CT, uint32_t CX, class A, class O>
+LB_HD void fp6_28_mul_01_to(A&& a, const fp2_28& b0, const fp2_28& b1, const fp2_28& bs, O&& out) {
+  const fp2_28 t0 = fp2_28_mul<CB0, 28>(a(0), b0);
+  const fp2_28 t1 = fp2_28_mul<CB1, 28>(a(1), b1);
+  out(1, fp2_28_norm(fp2_28_sub<CT, 29>(fp2_28_mul<CBS, 28>(fp2_28_add(a(0), a(1)), bs), fp2_28_add(t0, t1))));
+  out(0, fp2_28_norm(fp2_28_add(fp2_28_mul_xi<CX, 28>(fp2_28_mul<CB1, 28>(a(2), b1)), t0)));
+  out(2, fp2_28_add(fp2_28_mul<CB0, 28>(a(2), b0), t1));  // limbs below 2^29: the callers add and normalise
+}
+// a (b1 v) (fp6_mul_1): 3 products, 1 fp2_28_norm
+template <uint32_t CB1, uint32_t CX, class A, class O>
+LB_HD void fp6_28_mul_1_to(A&& a, const fp2_28& b1, O&& out) {
+  out(0, fp2_28_norm(fp2_28_mul_xi<CX, 28>(fp2_28_mul<CB1, 28>(a(2), b1))));
+  out(1, fp2_28_mul<CB1, 28>(a(0), b1));
+  out(2, fp2_28_mul<CB1, 28>(a(1), b1));
+}
+// fp6_28_at: coefficient i of a value; the kernel's step functions collect a product's output in one.
+// The whole-value forms after it (fp6_28_mul, _mul_01, _mul_1, and fp6_28_add / _sub / _mul_v / _norm
+// above) are host-check helpers: tests/native/miller28_check.cpp compares them with the 12-word tower
+// at the call sites' bounds.  No kernel calls them; the kernels go through the _to forms.
+LB_HD const fp2_28& fp6_28_at(const fp6_28& a, int i) { return i == 0 ? a.c0 : i == 1 ? a.c1 : a.c2; }
+LB_HD fp2_28& fp6_28_at(fp6_28& a, int i) { return i == 0 ? a.c0 : i == 1 ? a.c1 : a.c2; }
+template <uint32_t CB, uint32_t CB2, uint32_t CT, uint32_t CX, uint32_t CXT>
+LB_HD fp6_28 fp6_28_mul(const fp6_28& a, const fp6_28& b) {
+  fp6_28 r;
+  fp6_28_mul_to<CB, CB2, CT, CX, CXT>([&](int i) { return fp6_28_at(a, i); }, [&](int i) { return fp6_28_at(b, i); },
+                                      [&](int i, const fp2_28& v) { fp6_28_at(r, i) = v; });
+  return r;
+}
+template <uint32_t CB0, uint32_t CB1, uint32_t CBS, uint32_t CT, uint32_t CX>
+LB_HD fp6_28 fp6_28_mul_01(const fp6_28& a, const fp2_28& b0, const fp2_28& b1) {
+  fp6_28 r;
+  fp6_28_mul_01_to<CB0, CB1, CBS, CT, CX>([&](int i) { return fp6_28_at(a, i); }, b0, b1, fp2_28_norm(fp2_28_add(b0, b1)),
+                                          [&](int i, const fp2_28& v) { fp6_28_at(r, i) = v; });
+  return r;
+}
+template <uint32_t CB1, uint32_t CX>
+LB_HD fp6_28 fp6_28_mul_1(const fp6_28& a, const fp2_28& b1) {
+  fp6_28 r;
+  fp6_28_mul_1_to<CB1, CX>([&](int i) { return fp6_28_at(a, i); }, b1, [&](int i, const fp2_28& v) { fp6_28_at(r, i) = v; });
+  return r;
+}
 
 template <bool kInlMul = false>
 LB_HD fp fp_pow_const_i(fp a, const uint32_t* e, int top_bit) {

@@ -1236,78 +1236,50 @@ __global__ void __launch_bounds__(64) k_sig_blind_w4(uint32_t n, const uint32_t*
 // prod_i e(r_i PK_i, H(m)) = e(sum_i r_i PK_i, H(m))), written straight into leaf m + u of the
 // message product tree (stride 2m).  Three forms, picked per launch (lb_engine.hip):
 //   * k_miller_lane: one lane per root, 64 roots per wave.  The fewest instructions per root
-//     (the tower formulas compiled straight, operand sums computed once), but ~12 ms of serial
-//     products per lane and a large private segment; the form when the device is shared with
-//     other batches in flight, whose waves fill the SIMDs while these wait.
+//     (the tower formulas compiled straight, in 28-bit limbs from product to product), but ~9 ms
+//     of serial products per lane; the form when the device is shared with other batches in
+//     flight, whose waves fill the SIMDs while these wait.
 //   * k_miller_g8 (lb_group_exec.h): 8 lanes per root, 32 roots per workgroup, the state in LDS:
 //     ~3x shorter, ~2.5x more VALU work per root; the form for a large batch alone on the device.
 //   * k_miller_wave below: one wave per root, for batches with few distinct roots.
-// One lane per root with the Fp12 accumulator f in LDS (two 72-word slots per lane,
-// lane-interleaved: 36 KB per wave, so LDS allows the same one wave per SIMD as the registers)
-// and T and a tower temporary parked in global memory.  Held in registers across ~100
-// out-of-line product calls per step, f, T, the lines and the temporaries spilled 6.7 KB per
-// lane to the private segment, which the runtime reserves per HIP queue for the device's whole
-// wave capacity (the per-device engine cap).
+// One lane per root, f and T in 28-bit limbs from product to product (lb_pairing.h miller_lane28:
+// the formulas and the product tree of miller_loop_inl, the representation of lb_field.h fp6_28).
+// The state is four slots of 3 fp2_28 = 84 words per lane: f.c0, f.c1 and a tower temporary
+// lane-interleaved in LDS (63 KB per wave: two waves per CU), T parked in global memory.  The step
+// functions read each operand coefficient from its slot where a product uses it and write each
+// finished coefficient straight back, so no Fp6 is held in registers across a product; the
+// products themselves are inlined (no calls: nothing is saved around them), which makes the loop
+// body ~600 KB of straight-line code that streams through the instruction cache.
 typedef __attribute__((address_space(3))) uint32_t lds_w;
 template <int NL>  // slots [0, NL) in LDS (2: f; 3: f and the temporary), the rest in global memory
 struct lane_lds {
   lds_w* L;         // slots 0, 1: f.c0, f.c1
-  uint32_t* g;      // slot 2 (a temporary) and slot 3 (T): word i of slot k at g[((k - 2) * 72 + i) * n + u]
+  uint32_t* g;      // slot 2 (a temporary) and slot 3 (T): word i of slot k at g[((k - 2) * 84 + i) * n + u]
   uint32_t n, u;
   int lane;
-  __device__ __forceinline__ void put(int k, const fp6& v) const {
+  // coefficient i of slot k: words 28 i .. 28 i + 27 (c0's 14 limbs, then c1's); word w of lane l at L[64 w + l]
+  __device__ __forceinline__ void put2(int k, int i, const fp2_28& v) const {
     const uint32_t* w = reinterpret_cast<const uint32_t*>(&v);
     if (k < NL)
-      LB_UNROLL for (int i = 0; i < 72; i++) L[(k * 72 + i) * 64 + lane] = w[i];
+      LB_UNROLL for (int j = 0; j < 28; j++) L[(k * 84 + i * 28 + j) * 64 + lane] = w[j];
     else
-      LB_UNROLL for (int i = 0; i < 72; i++) g[((size_t)(k - 2) * 72 + i) * n + u] = w[i];
+      LB_UNROLL for (int j = 0; j < 28; j++) g[((size_t)(k - 2) * 84 + i * 28 + j) * n + u] = w[j];
     __asm__ volatile("" ::: "memory");
   }
-  __device__ __forceinline__ fp6 get(int k) const {
+  __device__ __forceinline__ fp2_28 get2(int k, int i) const {
     __asm__ volatile("" ::: "memory");
-    fp6 v;
+    fp2_28 v;
     uint32_t* w = reinterpret_cast<uint32_t*>(&v);
     if (k < NL)
-      LB_UNROLL for (int i = 0; i < 72; i++) w[i] = L[(k * 72 + i) * 64 + lane];
+      LB_UNROLL for (int j = 0; j < 28; j++) w[j] = L[(k * 84 + i * 28 + j) * 64 + lane];
     else
-      LB_UNROLL for (int i = 0; i < 72; i++) w[i] = g[((size_t)(k - 2) * 72 + i) * n + u];
+      LB_UNROLL for (int j = 0; j < 28; j++) w[j] = g[((size_t)(k - 2) * 84 + i * 28 + j) * n + u];
     return v;
   }
 };
-// f <- f^2 = (c0' - t - v t) + 2 t w, t = a0 a1, c0' = (a0 + a1)(a0 + v a1)  (slots 0, 1: f; 2: t)
-template <class S_t>
-__device__ __forceinline__ void lane_f_sqr(const S_t& S) {
-  fp6 s1, s2;
-  {
-    const fp6 a0 = S.get(0), a1 = S.get(1);
-    S.put(2, fp6_mul_inl(a0, a1));
-    s1 = fp6_add(a0, a1);
-    s2 = fp6_add(a0, fp6_mul_v(a1));
-  }
-  const fp6 c0 = fp6_mul_inl(s1, s2);
-  const fp6 t = S.get(2);
-  S.put(0, fp6_sub(fp6_sub(c0, t), fp6_mul_v(t)));
-  S.put(1, fp6_add(t, t));
-}
-// f <- f (l0 + l2 v + l3 v w)  (as fp12_mul_line_inl; slot 2 holds t1 = a1 l3)
-template <class S_t>
-__device__ __forceinline__ void lane_f_line(const S_t& S, const fp2& l0, const fp2& l2, const fp2& l3) {
-  fp6 s;
-  {
-    const fp6 a1 = S.get(1);
-    S.put(2, fp6_mul_1(a1, l3));
-    const fp6 a0 = S.get(0);
-    s = fp6_add(a0, a1);
-    S.put(0, fp6_mul_01(a0, l0, l2));  // t0 (f.c0 consumed)
-  }
-  const fp6 c1 = fp6_mul_01(s, l0, fp2_add(l2, l3));
-  const fp6 t0 = S.get(0), t1 = S.get(2);
-  S.put(1, fp6_sub(fp6_sub(c1, t0), t1));
-  S.put(0, fp6_add(t0, fp6_mul_v(t1)));
-}
-// NL = 3 (f and the temporary in LDS, 54 KB per wave: two waves per CU) keeps the per-root chain
-// fastest; NL = 2 (36 KB: one wave per SIMD, as the registers allow) for batches of so many
-// distinct roots that the LDS bound would leave most of them waiting (lb_engine.hip).
+// NL = 3 (f and the temporary in LDS, 63 KB per wave: two waves per CU) keeps the per-root chain
+// fastest; NL = 2 (42 KB: three waves per CU) for batches of so many distinct roots that the LDS
+// bound would leave most of them waiting (lb_engine.hip).
 #if LB_KG(4)
 template <int NL>
 __global__ void __launch_bounds__(LB_TPB, 1) k_miller_lane(uint32_t n, uint32_t m,
@@ -1317,51 +1289,24 @@ __global__ void __launch_bounds__(LB_TPB, 1) k_miller_lane(uint32_t n, uint32_t 
                                                            const uint32_t* __restrict__ h_aff,
                                                            uint32_t* __restrict__ treeP, uint32_t* __restrict__ tpark) {
   static_assert(LB_TPB == 64, "one wave per block: 64 lanes of LDS slots");
-  __shared__ uint32_t lds[NL * 72 * 64];
+  static_assert(sizeof(fp2_28) == 28 * sizeof(uint32_t), "a slot coefficient is 28 words");
+  __shared__ uint32_t lds[NL * 84 * 64];
   const uint32_t u = lb_tid();
   if (u >= *n_u) return;
   const lane_lds<NL> S{(lds_w*)lds, tpark, n, u, (int)threadIdx.x};
-  S.put(0, fp6_one());
-  S.put(1, fp6_zero());
+  S.put2(0, 0, fp2_28{fp28_one(), fp28_zero()});
+  LB_UNROLL for (int c = 1; c < 6; c++) S.put2(c / 3, c % 3, fp2_28{fp28_zero(), fp28_zero()});
   if (!gp_inf[u]) {
-    auto park_t = [&](const g2j& T) { S.put(3, *reinterpret_cast<const fp6*>(&T)); };
-    auto unpark_t = [&]() {
-      const fp6 v = S.get(3);
-      return *reinterpret_cast<const g2j*>(&v);
-    };
-    {
-      const g2a Q = soa_ld<g2a>(h_aff, n, u);
-      park_t(g2j{Q.x, Q.y, fp2_one()});
-    }
-    bool first = true;
-#pragma clang loop unroll(disable)
-    for (int i = 62; i >= 0; i--) {
-      if (!first) lane_f_sqr(S);
-      first = false;
-      fp2 l0, l2, l3;
-      {
-        g2j T = unpark_t();
-        const g1a P = soa_ld<g1a>(gp_aff, n, u);
-        miller_dbl(T, l0, l2, l3, P.x, P.y);
-        park_t(T);
-      }
-      lane_f_line(S, l0, l2, l3);
-      if ((LB_X_ABS >> i) & 1ull) {
-        {
-          g2j T = unpark_t();
-          const g1a P = soa_ld<g1a>(gp_aff, n, u);
-          miller_add(T, soa_ld<g2a>(h_aff, n, u), l0, l2, l3, P.x, P.y);
-          park_t(T);
-        }
-        lane_f_line(S, l0, l2, l3);
-      }
-    }
-    S.put(1, fp6_neg(S.get(1)));  // conjugate (x < 0)
+    miller_lane28(S, [&]() { return soa_ld<g1a>(gp_aff, n, u); }, [&]() { return soa_ld<g2a>(h_aff, n, u); });
+    // conjugate (x < 0): K - f.c1, f.c1 below the invariant's 27 p
+    LB_UNROLL for (int i = 0; i < 3; i++) S.put2(1, i, fp2_28_kminus<LB_M28_CONJ_C, 28>(S.get2(1, i)));
   }
-  LB_UNROLL for (int h = 0; h < 2; h++) {
-    const fp6 v = S.get(h);
+  // down to the canonical 12 words (one product by R mod p and one reduction each), rolled
+#pragma clang loop unroll(disable)
+  for (int c = 0; c < 6; c++) {
+    const fp2 v = fp2_28_to_fp2(S.get2(c / 3, c % 3));
     const uint32_t* w = reinterpret_cast<const uint32_t*>(&v);
-    LB_UNROLL for (int i = 0; i < 72; i++) treeP[(size_t)(72 * h + i) * (2 * m) + m + u] = w[i];
+    LB_UNROLL for (int i = 0; i < 24; i++) treeP[(size_t)(24 * c + i) * (2 * m) + m + u] = w[i];
   }
 }
 #endif  // LB_KG
