@@ -655,6 +655,10 @@ def g1_deserialize(b: bytes):
         if (b[0] & 0x3F) or any(b[1:]):
             raise BlsError("BLST_BAD_ENCODING")
         return None
+    if b[0] & 0x20:
+        # blst dispatches on the top three bits: 000 uncompressed, 1xx compressed, 010 infinity,
+        # 001 and 011 nothing (unpinned parity items)
+        raise BlsError("BLST_BAD_ENCODING")
     x = int.from_bytes(bytes([b[0] & 0x1F]) + b[1:48], "big")
     y = int.from_bytes(b[48:], "big")
     if x >= P or y >= P:
