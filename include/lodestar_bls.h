@@ -65,6 +65,13 @@ const char* lb_error_name(int32_t code);
 int32_t lb_abi_version(void);
 
 /*
+ * The number of usable devices: ordinals 0 .. n-1 are gfx950 and lb_engine_create accepts each of
+ * them (a pool that spreads over the host's GPUs creates its engines on these).  0 when there is
+ * none or when the HIP runtime fails to enumerate; never an error.
+ */
+int32_t lb_device_count(void);
+
+/*
  * One engine = one batch in flight on one GPU (own HIP streams and device workspaces); a process
  * may drive several engines per GPU concurrently (the reference runs one job package per worker
  * thread at a time, multithread/index.ts:290-381).  device < 0 = current.  Returns

@@ -43,6 +43,7 @@ _vp = ctypes.c_void_p
 SIGNATURES = {
     "lb_error_name": (ctypes.c_char_p, [ctypes.c_int32]),
     "lb_abi_version": (ctypes.c_int32, []),
+    "lb_device_count": (ctypes.c_int32, []),
     "lb_engine_create": (ctypes.c_int32, [ctypes.c_int32, ctypes.POINTER(_vp)]),
     "lb_engine_create_ex": (ctypes.c_int32, [ctypes.c_int32, ctypes.c_uint32, ctypes.POINTER(_vp)]),
     "lb_engine_destroy": (None, [_vp]),

@@ -200,6 +200,19 @@ const char* lb_error_name(int32_t code) {
   }
 }
 
+// the leading run of gfx950 ordinals (lb_engine_create_ex refuses any other device, and ordinals
+// from 64 up: the per-device tables above)
+int32_t lb_device_count(void) {
+  int count = 0;
+  if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return 0;
+  int n = 0;
+  for (; n < count && n < 64; n++) {
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, n) != hipSuccess || strncmp(prop.gcnArchName, "gfx950", 6) != 0) break;
+  }
+  return n;
+}
+
 int32_t lb_engine_create(int32_t device, lb_engine** out) { return lb_engine_create_ex(device, 0u, out); }
 // a CU mask over [lo, hi) of ncu CUs (32 per word)
 static std::vector<uint32_t> cu_mask(int ncu, int lo, int hi) {

@@ -179,6 +179,11 @@ class Engine:
         self.h = h
         self.device = device
 
+    @staticmethod
+    def device_count() -> int:
+        """Usable gfx950 devices: ordinals 0 .. n-1 (lb_device_count; 0 when there is none)."""
+        return int(N.load().lb_device_count())
+
     def close(self):
         if self.h:
             self.lib.lb_engine_destroy(self.h)

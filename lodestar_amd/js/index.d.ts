@@ -50,9 +50,19 @@ export declare class BlsGpuVerifier implements IBlsVerifier {
   /** engines: batches in flight on the device (default 2), each with its own streams + workspace; the
    *  pool also creates one engine for verifyOnMainThread calls, so it takes engines + 1 of the
    *  per-device cap (LB_MAX_ENGINES_PER_DEVICE, default 16) */
-  /** modules as BlsMultiThreadWorkerPool's: metrics.blsThreadPool.* / metrics.bls.* get the same updates */
-  constructor(opts?: {device?: number; engines?: number; blsVerifyAllMultiThread?: boolean},
-              modules?: {logger?: {error(msg: string, ctx?: object, e?: Error): void}; metrics?: unknown});
+  /** devices: the device ordinals the pool spreads over, one slot of `engines` pool engines each ("all":
+   *  every usable device; a repeated ordinal is a second, independent slot on that device).  One latency
+   *  engine serves the whole verifier, on devices[0].  A queue is cut over the slots with an idle engine
+   *  at equal cost quantiles, into packages of at least minPackageSets sets.  Without `devices`: one slot
+   *  on `device` (default 0), which takes every queue whole. */
+  /** modules as BlsMultiThreadWorkerPool's: metrics.blsThreadPool.* / metrics.bls.* get the same updates;
+   *  addon replaces the native addon for this instance (tests) */
+  constructor(opts?: {device?: number; devices?: number[] | "all"; engines?: number; minPackageSets?: number;
+                      blsVerifyAllMultiThread?: boolean; latencyPartition?: boolean},
+              modules?: {logger?: {error(msg: string, ctx?: object, e?: Error): void}; metrics?: unknown; addon?: object});
+  /** the slots' device ordinals, in slot order */
+  readonly devices: number[];
+  readonly minPackageSets: number;
   /** 48- or 96-byte keys -> handles carrying their table index (validate: keyValidate checks) */
   registerPubkeys(keys: Uint8Array[], validate?: boolean): GpuPublicKey[];
   verifySignatureSets(sets: ISignatureSet[], opts?: VerifySignatureOpts): Promise<boolean>;
@@ -62,8 +72,18 @@ export declare class BlsGpuVerifier implements IBlsVerifier {
   aggregateSignatures(signatures: Uint8Array[], validate?: boolean): Uint8Array;
   close(): Promise<void>;
   readonly stats: {batches: number; jobs: number; sets: number; batchRetries: number; batchSigsSuccess: number;
-    jobsInvalid: number; jobsError: number; jobWaitMs: number; deviceMs: number; mainThreadMs: number};
+    jobsInvalid: number; jobsError: number; jobWaitMs: number; deviceMs: number; mainThreadMs: number;
+    /** packages launched per slot; dispatch rounds that launched more than one package */
+    packagesPerSlot: number[]; splits: number};
 }
+
+/** Device work of one job (distributed.py's SET_COST per set + KEY_COST per pubkey). */
+export declare function jobCost(job: ISignatureSet[] | {sets: ISignatureSet[]}): number;
+/** k contiguous [lo, hi) ranges of whole jobs at equal cost quantiles (distributed.shard_jobs_by_cost). */
+export declare function splitByCost(jobs: (ISignatureSet[] | {sets: ISignatureSet[]})[], k: number): [number, number][];
+export declare const SET_COST: number;
+export declare const KEY_COST: number;
+export declare const DEFAULT_MIN_PACKAGE_SETS: number;
 
 /** light-client isValidBlsAggregate (validation.ts:154-184) with its stage-prefixed errors */
 export declare function isValidBlsAggregate(verifier: BlsGpuVerifier, publicKeys: PublicKeyLike[],

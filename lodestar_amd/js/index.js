@@ -17,7 +17,10 @@
  * HIP streams and device workspace) take packages from one queue: an idle engine drains EVERY
  * queued job into one device batch through the N-API addon (../napi/lb_napi.c ->
  * include/lodestar_bls.h), like the reference's idle worker taking the next package
- * (multithread/index.ts:290-330).  The event loop is never blocked.
+ * (multithread/index.ts:290-330).  The event loop is never blocked.  With `devices` the pool has
+ * one such slot of engines per listed GPU and cuts a long enough queue over the slots that have
+ * an idle engine (runJobs); the reference pool sizes itself to the host the same way
+ * (createWorkers(implementation, defaultPoolSize), multithread/index.ts).
  *
  * Public keys: a `PublicKey` here is
  *   - a handle returned by registerPubkeys() (the epoch cache's index2pubkey entries,
@@ -41,10 +44,18 @@
 const path = require("path");
 
 const addon = require(path.join(__dirname, "..", "napi", "lodestar_bls.node"));
+// a verifier uses modules.addon in its place when given (tests drive the dispatch through a mock)
+const defaultAddon = addon;
 
 const MAX_SIGNATURE_SETS_PER_JOB = 128;
 const MAX_BUFFERED_SIGS = 32;
 const MAX_BUFFER_WAIT_MS = 100;
+const LB_ERR_NO_DEVICE = 102;  // include/lodestar_bls.h
+// A queue is cut over several slots only into packages of at least this many sets: the smallest
+// power of two at which a lone package on one pool engine verifies at half the rate of a full
+// slot's package or better (measured, DESIGN.md §6 "Multi-GPU inside the drop-in"), so two
+// devices with s sets each finish no later than one device with 2 s sets at its best rate.
+const DEFAULT_MIN_PACKAGE_SETS = 8192;  // profiles/min_package_sets.json (tools/min_package_sets.py)
 
 const SignatureSetType = {single: "single", aggregate: "aggregate"};
 
@@ -112,7 +123,8 @@ function setPubkeys(s) {
  * decompressed on the GPU in one batch by `decompress(flat48) -> {out, status}`; a key that does not
  * decode rejects the call with its blst error.
  */
-function normalizeSets(sets, decompress) {
+function normalizeSets(sets, decompress, errorName) {
+  errorName = errorName || addon.errorName;
   let short = null;  // [setIndex, keyIndex | -1, bytes48]
   sets.forEach((s, si) => {
     const pks = setPubkeys(s);
@@ -131,7 +143,7 @@ function normalizeSets(sets, decompress) {
   short.forEach(([, , b], k) => flat.set(b, 48 * k));
   const d = decompress(flat);
   d.status.forEach((st) => {
-    if (st !== 0) throw Error(addon.errorName(st));
+    if (st !== 0) throw Error(errorName(st));
   });
   const out = sets.slice();
   short.forEach(([si, ki, , pk], k) => {
@@ -195,42 +207,120 @@ function packJobs(jobs) {
   return [jobOff, pkOff, pks, roots, sigs, odd ? sizes : null];
 }
 
-function codeToResult(code) {
-  if (code < 0) throw Error(addon.errorName(-code));
+function codeToResult(code, errorName) {
+  if (code < 0) throw Error(errorName(-code));
   return code === 1;
+}
+
+// Device work of a job in Fp multiplications, as lodestar_amd/distributed.py prices it (SET_COST,
+// KEY_COST there: DESIGN.md §5's kernel table): per set the signature decode + subgroup check,
+// r*PK and the bucket MSM; per aggregated key one mixed addition.
+const SET_COST = 2111 + 601 + 232;
+const KEY_COST = 16;
+
+/** cost of one job (its ISignatureSet[], or a queued job carrying them as `sets`) */
+function jobCost(job) {
+  let c = 0;
+  for (const s of Array.isArray(job) ? job : job.sets) c += SET_COST + KEY_COST * setPubkeys(s).length;
+  return c;
+}
+
+/**
+ * distributed.shard_jobs_by_cost for every rank at once: `k` contiguous ranges [lo, hi) of whole
+ * jobs that cover `jobs`, cut at equal cost quantiles -- range r takes the jobs whose cost midpoint
+ * falls in [r T / k, (r + 1) T / k), T the total cost.  A range may be empty (a job heavier than a
+ * quantile).  The arithmetic is the Python function's, operation for operation (doubles), so both
+ * hosts cut one queue at the same jobs.
+ */
+function splitByCost(jobs, k) {
+  const n = jobs.length;
+  if (n === 0) return Array.from({length: k}, () => [0, 0]);
+  const mid = new Float64Array(n);
+  let pre = 0;
+  for (let j = 0; j < n; j++) {
+    const c = jobCost(jobs[j]);
+    mid[j] = (pre + (pre + c)) / 2.0;
+    pre += c;
+  }
+  const tot = pre;
+  // numpy.searchsorted(mid, x, side="left")
+  const lowerBound = (x) => {
+    let lo = 0;
+    let hi = n;
+    while (lo < hi) {
+      const m = (lo + hi) >>> 1;
+      if (mid[m] < x) lo = m + 1;
+      else hi = m;
+    }
+    return lo;
+  };
+  const out = [];
+  for (let r = 0; r < k; r++) out.push([lowerBound((r * tot) / k), r + 1 < k ? lowerBound(((r + 1) * tot) / k) : n]);
+  return out;
 }
 
 class BlsGpuVerifier {
   /**
-   * @param {{device?: number, engines?: number, blsVerifyAllMultiThread?: boolean, latencyPartition?: boolean}} [opts]
-   * @param {{logger?: object, metrics?: object|null}} [modules] as the reference pool's
+   * @param {{device?: number, devices?: number[]|"all", engines?: number, minPackageSets?: number,
+   *   blsVerifyAllMultiThread?: boolean, latencyPartition?: boolean}} [opts]
+   *   `devices`: the device ordinals the pool spreads over, one slot of `engines` pool engines each
+   *   ("all": 0 .. addon.deviceCount()-1, as the reference pool sizes itself to the host; a repeated
+   *   ordinal is a second slot on that device).  Without it: one slot on `device`.
+   * @param {{logger?: object, metrics?: object|null, addon?: object}} [modules] as the reference pool's
    *   (multithread/index.ts:98-134): `metrics.blsThreadPool.*` / `metrics.bls.*` receive the same
-   *   updates (lodestar.ts:433-523) when given
+   *   updates (lodestar.ts:433-523) when given; `addon` stands in for the native addon
    */
   constructor(opts, modules) {
     opts = opts || {};
     modules = modules || {};
+    const addon = (this.addon = modules.addon || defaultAddon);
     const n = opts.engines === undefined ? 2 : opts.engines;
     if (!(n >= 1)) throw Error("engines must be >= 1");
-    const device = opts.device === undefined ? 0 : opts.device;
+    let devices;
+    if (opts.devices === undefined) {
+      devices = [opts.device === undefined ? 0 : opts.device];
+    } else if (opts.devices === "all") {
+      devices = Array.from({length: addon.deviceCount()}, (_, d) => d);
+      if (devices.length === 0) throw Error(addon.errorName(LB_ERR_NO_DEVICE));
+    } else {
+      devices = Array.from(opts.devices);
+      if (devices.length === 0 || !devices.every((d) => Number.isInteger(d) && d >= 0)) {
+        throw Error('devices must be "all" or a non-empty array of device ordinals');
+      }
+    }
+    const minPackageSets = opts.minPackageSets === undefined ? DEFAULT_MIN_PACKAGE_SETS : opts.minPackageSets;
+    if (!(minPackageSets >= 1)) throw Error("minPackageSets must be >= 1");
+    this.minPackageSets = minPackageSets;
+    this.devices = devices;
+    // one slot per entry of `devices` (a repeated ordinal: a second, independent slot on that
+    // device), each with `engines` pool engines; this.engines is the flattened list, slot by slot
+    this.slots = [];
     this.engines = [];
     try {
       // synchronous calls get their own engine, created first as the device's latency engine
       // (LB_ENGINE_LATENCY: its own reserved CUs, the pool's engines on the rest), so a
       // verifyOnMainThread call is neither queued behind a pool batch's engine mutex nor behind
-      // the pool's kernels on the device
+      // the pool's kernels on the device.  One for the whole verifier, on devices[0].
       try {
-        this.syncEngine = addon.createEngine(device, opts.latencyPartition === false ? 0 : 1);
+        this.syncEngine = addon.createEngine(devices[0], opts.latencyPartition === false ? 0 : 1);
       } catch (e) {
-        this.syncEngine = addon.createEngine(device);
+        this.syncEngine = addon.createEngine(devices[0]);
       }
-      for (let k = 0; k < n; k++) this.engines.push(addon.createEngine(device));
+      devices.forEach((device, position) => {
+        const slot = {position, device, engines: [], idle: [], inflightCost: 0};
+        this.slots.push(slot);
+        for (let k = 0; k < n; k++) {
+          const en = addon.createEngine(device);
+          slot.engines.push(en);
+          this.engines.push(en);
+        }
+        slot.idle = slot.engines.slice();
+      });
     } catch (e) {
       for (const en of this.engines) addon.destroyEngine(en);
       if (this.syncEngine) addon.destroyEngine(this.syncEngine);
       throw e;
     }
-    this.idle = this.engines.slice();
     this.blsVerifyAllMultiThread = Boolean(opts.blsVerifyAllMultiThread);
     this.logger = modules.logger || null;
     this.metrics = modules.metrics || null;
@@ -239,7 +329,9 @@ class BlsGpuVerifier {
     this.running = new Set();
     this.closed = false;
     this.stats = {batches: 0, jobs: 0, sets: 0, batchRetries: 0, batchSigsSuccess: 0, jobsInvalid: 0, jobsError: 0,
-      jobWaitMs: 0, deviceMs: 0, mainThreadMs: 0};
+      jobWaitMs: 0, deviceMs: 0, mainThreadMs: 0,
+      // packages launched per slot, and runJobs rounds that launched more than one package
+      packagesPerSlot: this.slots.map(() => 0), splits: 0};
     this.decompress = (flat48) => addon.g1Decompress(this.syncEngine, flat48);
   }
 
@@ -267,13 +359,13 @@ class BlsGpuVerifier {
     if (size === 48) {
       // decompressed once on the GPU: handles keep the 96-byte form for byte-carrying packages
       const d = this.decompress(flat);
-      for (const st of d.status) if (st !== 0) throw Error(addon.errorName(st));
+      for (const st of d.status) if (st !== 0) throw Error(this.addon.errorName(st));
       flat = d.out;
     }
     let first = -1;
     for (const e of this.allEngines()) {
-      const r = addon.registerPubkeys(e, flat, 96, Boolean(validate));
-      for (const st of r.status) if (st !== 0) throw Error(addon.errorName(st));
+      const r = this.addon.registerPubkeys(e, flat, 96, Boolean(validate));
+      for (const st of r.status) if (st !== 0) throw Error(this.addon.errorName(st));
       if (first >= 0 && r.first !== first) throw Error("engine pubkey tables out of step");
       first = r.first;
     }
@@ -287,22 +379,22 @@ class BlsGpuVerifier {
    */
   verifyMainThread(sets) {
     const t0 = Date.now();
-    return addon.verifyJobs(this.syncEngine, ...packJobs([normalizeSets(sets, this.decompress)])).then((res) => {
+    return this.addon.verifyJobs(this.syncEngine, ...packJobs([normalizeSets(sets, this.decompress, this.addon.errorName)])).then((res) => {
       const dt = Date.now() - t0;
       this.stats.mainThreadMs += dt;
       if (this.metrics) this.metrics.blsThreadPool.mainThreadDurationInThreadPool.observe(dt / 1000);
-      return codeToResult(res[0]);
+      return codeToResult(res[0], this.addon.errorName);
     });
   }
 
   /** one job verified synchronously on the caller's thread (state-transition verifySignatureSet) */
   verifySync(sets) {
     const t0 = Date.now();
-    const res = addon.verifyJobsSync(this.syncEngine, ...packJobs([normalizeSets(sets, this.decompress)]));
+    const res = this.addon.verifyJobsSync(this.syncEngine, ...packJobs([normalizeSets(sets, this.decompress, this.addon.errorName)]));
     const dt = Date.now() - t0;
     this.stats.mainThreadMs += dt;
     if (this.metrics) this.metrics.blsThreadPool.mainThreadDurationInThreadPool.observe(dt / 1000);
-    return codeToResult(res[0]);
+    return codeToResult(res[0], this.addon.errorName);
   }
 
   /**
@@ -329,9 +421,9 @@ class BlsGpuVerifier {
       if (sg.length === 96) flat.set(sg, 96 * i);
       else odd = true;
     });
-    const r = addon.aggregateSignatures(this.syncEngine, Uint32Array.from([0, signatures.length]), flat,
+    const r = this.addon.aggregateSignatures(this.syncEngine, Uint32Array.from([0, signatures.length]), flat,
       odd ? sizes : null, validate === undefined ? true : Boolean(validate));
-    if (r.status[0] !== 0) throw Error(addon.errorName(r.status[0]));
+    if (r.status[0] !== 0) throw Error(this.addon.errorName(r.status[0]));
     return r.out;
   }
 
@@ -348,7 +440,7 @@ class BlsGpuVerifier {
       if (this.closed) throw new QueueError({code: QueueErrorCode.QUEUE_ABORTED});
       if (this.metrics) this.metrics.bls.aggregatedPubkeys.inc(getAggregatedPubkeysCount(sets));
       if (opts.verifyOnMainThread && !this.blsVerifyAllMultiThread) return this.verifyMainThread(sets);
-      sets = normalizeSets(sets, this.decompress);
+      sets = normalizeSets(sets, this.decompress, this.addon.errorName);
     } catch (e) {
       return Promise.reject(e);
     }
@@ -370,10 +462,10 @@ class BlsGpuVerifier {
     }
     for (const job of this.jobs.splice(0)) job.reject(new QueueError({code: QueueErrorCode.QUEUE_ABORTED}));
     await Promise.all([...this.running]);
-    for (const e of this.allEngines()) addon.destroyEngine(e);
+    for (const e of this.allEngines()) this.addon.destroyEngine(e);
     this.engines = [];
     this.syncEngine = null;
-    this.idle = [];
+    for (const slot of this.slots) slot.engines = slot.idle = [];
   }
 
   queueJob(sets, opts) {
@@ -402,18 +494,49 @@ class BlsGpuVerifier {
     setTimeout(() => this.runJobs(), 0);
   }
 
-  /** every idle engine takes the whole queue as one package (multithread/index.ts:290-330) */
+  /**
+   * An idle engine takes the whole queue as one package (multithread/index.ts:290-330).  With
+   * several slots the queue is cut over the slots that have an idle engine, as many as leave each
+   * package minPackageSets sets: k contiguous ranges of whole jobs at equal cost quantiles
+   * (splitByCost), handed to the k slots with the least cost in flight, ties to the lowest slot
+   * position, one idle engine each.  One slot: k = 1, that engine takes everything.
+   */
   runJobs() {
-    while (this.idle.length > 0 && this.jobs.length > 0 && !this.closedEngines()) {
-      const engine = this.idle.pop();
-      const pkg = this.jobs.splice(0);
-      const p = this.runPackage(engine, pkg).finally(() => {
-        this.running.delete(p);
-        if (this.engines.includes(engine)) this.idle.push(engine);
-        if (this.jobs.length > 0) this.runJobs();
-      });
-      this.running.add(p);
+    if (this.jobs.length === 0 || this.closedEngines()) return;
+    const free = this.slots.filter((slot) => slot.idle.length > 0);
+    if (free.length === 0) return;
+    let k = 1;
+    if (free.length > 1) {
+      let sets = 0;
+      for (const j of this.jobs) sets += j.sets.length;
+      k = Math.min(free.length, Math.max(1, Math.floor(sets / this.minPackageSets)));
     }
+    // (Array.prototype.sort is stable: equal costs keep their slot order)
+    const chosen = free.sort((a, b) => a.inflightCost - b.inflightCost).slice(0, k);
+    const queue = this.jobs.splice(0);
+    let launched = 0;
+    (k === 1 ? [[0, queue.length]] : splitByCost(queue, k)).forEach(([lo, hi], r) => {
+      if (hi === lo) return;  // a job heavier than a quantile leaves a range empty
+      this.launch(chosen[r], queue.slice(lo, hi));
+      launched++;
+    });
+    if (launched > 1) this.stats.splits++;
+  }
+
+  /** one package on one idle engine of `slot` */
+  launch(slot, pkg) {
+    const engine = slot.idle.pop();
+    let cost = 0;
+    for (const j of pkg) cost += jobCost(j);
+    slot.inflightCost += cost;
+    this.stats.packagesPerSlot[slot.position]++;
+    const p = this.runPackage(engine, pkg).finally(() => {
+      this.running.delete(p);
+      slot.inflightCost -= cost;
+      if (slot.engines.includes(engine)) slot.idle.push(engine);
+      if (this.jobs.length > 0) this.runJobs();
+    });
+    this.running.add(p);
   }
 
   closedEngines() {
@@ -437,7 +560,7 @@ class BlsGpuVerifier {
     }
     let codes;
     try {
-      codes = await addon.verifyJobs(engine, ...packJobs(pkg.map((j) => j.sets)));
+      codes = await this.addon.verifyJobs(engine, ...packJobs(pkg.map((j) => j.sets)));
     } catch (e) {
       // device failure: every job of the package rejects (multithread/index.ts:368-375)
       if (!this.closed && this.logger) this.logger.error("BlsGpuVerifier error", {}, e);
@@ -456,7 +579,7 @@ class BlsGpuVerifier {
       if (codes[k] < 0) {
         this.stats.jobsError++;
         error += j.sets.length;
-        j.reject(Error(addon.errorName(-codes[k])));
+        j.reject(Error(this.addon.errorName(-codes[k])));
       } else {
         if (codes[k] === 0) {
           this.stats.jobsInvalid++;
@@ -518,6 +641,11 @@ module.exports = {
   getAggregatedPubkeysCount,
   chunkifyMaximizeChunkSize,
   packJobs,
+  splitByCost,
+  jobCost,
+  SET_COST,
+  KEY_COST,
+  DEFAULT_MIN_PACKAGE_SETS,
   addon,
   MAX_SIGNATURE_SETS_PER_JOB,
   MAX_BUFFERED_SIGS,

@@ -20,6 +20,7 @@
  *   - argument lengths are checked against the offsets before anything is queued (TypeError).
  *
  * Exports:
+ *   deviceCount() -> number   (lb_device_count: ordinals 0 .. n-1 are usable; 0 when there is none)
  *   createEngine(device: number, flags?: number) -> External   (flags: 1 = LB_ENGINE_LATENCY)
  *       (the first call raises GPU_MAX_HW_QUEUES to 16 when it is unset or lower -- HIP's and the
  *       GPU boxes' default is 4 -- so the three HIP streams of each engine get their own hardware
@@ -170,15 +171,9 @@ static napi_value throw_code(napi_env env, int32_t code) {
   return NULL;
 }
 
-static napi_value create_engine(napi_env env, napi_callback_info info) {
+/* Before the first call that initialises the HIP runtime (the first engine, or deviceCount). */
+static void set_hw_queues(void) {
   static int queues_set = 0;
-  size_t argc = 2;
-  napi_value argv[2];
-  int32_t device = 0;
-  uint32_t flags = 0;
-  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
-  if (argc >= 1) NAPI_CALL(env, napi_get_value_int32(env, argv[0], &device));
-  if (argc >= 2) NAPI_CALL(env, napi_get_value_uint32(env, argv[1], &flags));
   if (!queues_set) {
     /* HIP reads GPU_MAX_HW_QUEUES once, at runtime initialisation (the first engine): each
      * engine drives three streams, and with the default 4 queues the streams of concurrent
@@ -188,6 +183,25 @@ static napi_value create_engine(napi_env env, napi_callback_info info) {
     if (!v || !*v || atoi(v) < 16) setenv("GPU_MAX_HW_QUEUES", "16", 1);
     queues_set = 1;
   }
+}
+
+static napi_value device_count(napi_env env, napi_callback_info info) {
+  napi_value n;
+  (void)info;
+  set_hw_queues();
+  NAPI_CALL(env, napi_create_int32(env, lb_device_count(), &n));
+  return n;
+}
+
+static napi_value create_engine(napi_env env, napi_callback_info info) {
+  size_t argc = 2;
+  napi_value argv[2];
+  int32_t device = 0;
+  uint32_t flags = 0;
+  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  if (argc >= 1) NAPI_CALL(env, napi_get_value_int32(env, argv[0], &device));
+  if (argc >= 2) NAPI_CALL(env, napi_get_value_uint32(env, argv[1], &flags));
+  set_hw_queues();
   engine_box* b = (engine_box*)calloc(1, sizeof(engine_box));
   int32_t st = lb_engine_create_ex(device, flags, &b->e);
   if (st != LB_OK) {
@@ -1074,6 +1088,7 @@ static napi_value error_name(napi_env env, napi_callback_info info) {
 
 static napi_value init(napi_env env, napi_value exports) {
   napi_property_descriptor props[] = {
+      {"deviceCount", NULL, device_count, NULL, NULL, NULL, napi_default, NULL},
       {"createEngine", NULL, create_engine, NULL, NULL, NULL, napi_default, NULL},
       {"destroyEngine", NULL, destroy_engine, NULL, NULL, NULL, napi_default, NULL},
       {"verifyJobs", NULL, verify_jobs, NULL, NULL, NULL, napi_default, NULL},

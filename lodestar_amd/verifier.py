@@ -15,6 +15,9 @@ The worker threads are replaced by one GPU runner thread per engine (`n_engines`
 flight on the device, default 2): an idle runner drains every queued job into ONE device batch
 (one final exponentiation for all valid jobs, a search for the failing sets when it fails),
 instead of the reference's packages of ~128 sets per CPU worker and per-job re-verification.
+With `devices` the pool holds one such slot of engines per listed GPU and cuts a long enough queue
+over the slots that have an idle runner (BlsGpuVerifier._dispatch), as the reference pool sizes
+itself to the host.
 Malformed inputs (root not 32 bytes, pubkey not a PublicKey, signature not bytes) raise in the
 caller's own call before anything is queued, so they never touch other callers' jobs.
 """
@@ -27,11 +30,16 @@ from dataclasses import dataclass, field
 from enum import Enum
 from typing import List, Optional, Sequence, Union
 
+from . import _native as N
+from .distributed import job_costs, shard_jobs_by_cost
 from .engine import BlsError, Engine, SetInput
 
 MAX_SIGNATURE_SETS_PER_JOB = 128   # multithread/index.ts:39
 MAX_BUFFERED_SIGS = 32             # multithread/index.ts:48
 MAX_BUFFER_WAIT_MS = 100           # multithread/index.ts:57
+# a queue is cut over several slots only into packages of at least this many sets (the measured
+# half-rate package size, DESIGN.md §6 "Multi-GPU inside the drop-in"; js/index.js holds the same)
+DEFAULT_MIN_PACKAGE_SETS = 8192
 
 
 class QueueErrorCode(str, Enum):
@@ -159,35 +167,94 @@ class PoolStats:
     sets: int = 0
     jobs_invalid: int = 0
     jobs_error: int = 0
+    packages_per_slot: List[int] = field(default_factory=list)  # packages handed to each slot
+    splits: int = 0  # dispatch rounds that cut the queue into more than one package
+
+
+@dataclass
+class _Slot:
+    """One entry of `devices`: its pool engines (one runner thread each) and what the dispatch
+    needs to know about them."""
+    position: int
+    device: int
+    engines: list
+    idle: int = 0                  # runners waiting for a package
+    inflight_cost: float = 0.0     # cost of the packages assigned or running (distributed.job_costs)
+    assigned: list = field(default_factory=list)  # (jobs, cost) packages cut for this slot, not yet taken
 
 
 class BlsGpuVerifier:
     """IBlsVerifier backed by MI355X engines (drop-in for BlsMultiThreadWorkerPool)."""
 
     def __init__(self, engine: Optional[Engine] = None, device: int = 0, bls_verify_all_multi_thread: bool = False,
-                 n_engines: int = 2):
+                 n_engines: int = 2, devices: Union[Sequence[int], str, None] = None,
+                 min_package_sets: int = DEFAULT_MIN_PACKAGE_SETS, engine_factory=None):
+        """`devices`: the device ordinals the pool spreads over, one slot of `n_engines` pool engines
+        each ("all": 0 .. Engine.device_count()-1; a repeated ordinal is a second, independent slot on
+        that device), with one latency engine, created first, on devices[0].  Without it: one slot on
+        `device`, or the caller's `engine`.  `engine_factory(device, flags=0)` stands in for Engine
+        (tests drive the dispatch through a fake)."""
+        make = engine_factory or Engine
+        if min_package_sets < 1:
+            raise ValueError("min_package_sets must be >= 1")
+        self.min_package_sets = int(min_package_sets)
         if engine is not None:
-            self.engines = [engine]
+            if devices is not None:
+                raise ValueError("pass either engine or devices")
+            self.devices = [getattr(engine, "device", device)]
+            per_slot = [[engine]]
             self._own_engines = False
+            self.engine = engine
+        elif devices is None:
+            if n_engines < 1:
+                raise ValueError("n_engines must be >= 1")
+            self.devices = [device]
+            per_slot = [[make(device) for _ in range(n_engines)]]
+            self._own_engines = True
+            # synchronous callers (verify_on_main_thread, verify_signature_set, aggregate_signatures,
+            # key decompression) use an engine outside the runners' pool when the pool owns its
+            # engines, so they never wait behind a batch in flight (multithread/index.ts:138-151)
+            self.engine = make(device)
         else:
             if n_engines < 1:
                 raise ValueError("n_engines must be >= 1")
-            self.engines = [Engine(device) for _ in range(n_engines)]
+            if isinstance(devices, str):
+                if devices != "all":
+                    raise ValueError('devices must be "all" or a sequence of device ordinals')
+                self.devices = list(range(getattr(make, "device_count", Engine.device_count)()))
+                if not self.devices:
+                    raise BlsError(N.LB_ERR_NO_DEVICE)
+            else:
+                self.devices = [int(d) for d in devices]
+                if not self.devices or any(d < 0 for d in self.devices):
+                    raise ValueError('devices must be "all" or a non-empty sequence of device ordinals')
             self._own_engines = True
-        # synchronous callers (verify_on_main_thread, verify_signature_set, aggregate_signatures,
-        # key decompression) use an engine outside the runners' pool when the pool owns its
-        # engines, so they never wait behind a batch in flight (multithread/index.ts:138-151)
-        self.engine = Engine(device) if self._own_engines else self.engines[0]
+            created: List[Engine] = []
+            try:
+                self.engine = make(self.devices[0], Engine.LATENCY)
+                created.append(self.engine)
+                per_slot = []
+                for d in self.devices:
+                    per_slot.append([])
+                    for _ in range(n_engines):
+                        per_slot[-1].append(make(d))
+                        created.append(per_slot[-1][-1])
+            except Exception:
+                for e in created:
+                    e.close()
+                raise
+        self._slots = [_Slot(position=p, device=d, engines=es) for p, (d, es) in enumerate(zip(self.devices, per_slot))]
+        self.engines = [e for s in self._slots for e in s.engines]  # flattened, slot by slot
         self.bls_verify_all_multi_thread = bls_verify_all_multi_thread
-        self.stats = PoolStats()
+        self.stats = PoolStats(packages_per_slot=[0] * len(self._slots))
         self._lock = threading.Condition()
         self._jobs: List[_Job] = []
         self._buffered: List[_Job] = []
         self._buffered_sigs = 0
         self._buffer_timer: Optional[asyncio.TimerHandle] = None
         self._closed = False
-        self._runners = [threading.Thread(target=self._run, args=(e,), name=f"lodestar-bls-gpu-{k}", daemon=True)
-                         for k, e in enumerate(self.engines)]
+        self._runners = [threading.Thread(target=self._run, args=(s, e), name=f"lodestar-bls-gpu-{k}", daemon=True)
+                         for k, (s, e) in enumerate((s, e) for s in self._slots for e in s.engines)]
         for t in self._runners:
             t.start()
 
@@ -224,6 +291,10 @@ class BlsGpuVerifier:
                 self._buffer_timer.cancel()
                 self._buffer_timer = None
             pending = self._jobs + self._buffered
+            for s in self._slots:  # packages cut for a slot that no runner has taken yet
+                for jobs, _ in s.assigned:
+                    pending += jobs
+                s.assigned = []
             self._jobs, self._buffered, self._buffered_sigs = [], [], 0
             self._lock.notify_all()
         for j in pending:
@@ -231,6 +302,7 @@ class BlsGpuVerifier:
         for t in self._runners:
             await asyncio.get_running_loop().run_in_executor(None, t.join)
         if self._own_engines:
+            self._own_engines = False  # (a second close() finds nothing left to destroy)
             for e in [self.engine] + self.engines:
                 e.close()
 
@@ -296,14 +368,60 @@ class BlsGpuVerifier:
             self._lock.notify_all()
 
     # ---------------------------------------------------------------- GPU runner
-    def _run(self, engine: Engine):
+    def _dispatch(self):
+        """(lock held) Cuts the queue over the slots that have an idle runner, as js/index.js's
+        runJobs does: k = min(slots, max(1, sets // min_package_sets)) contiguous ranges of whole jobs
+        at equal cost quantiles (distributed.shard_jobs_by_cost), handed to the k slots with the least
+        cost in flight, ties to the lowest position.  One slot: k = 1, the whole queue."""
+        if not self._jobs:
+            return
+        free = [s for s in self._slots if s.idle > len(s.assigned)]
+        if not free:
+            return
+        queue = self._jobs
+        k = 1
+        if len(free) > 1:
+            k = min(len(free), max(1, sum(len(j.sets) for j in queue) // self.min_package_sets))
+        ranges = [(0, len(queue))]
+        costs = None
+        if len(self._slots) > 1:
+            job_off = [0]
+            pk_off = [0]
+            for j in queue:
+                for s in j.sets:
+                    pk_off.append(pk_off[-1] + len(s.pubkeys))
+                job_off.append(job_off[-1] + len(j.sets))
+            costs = job_costs(job_off, pk_off)
+            if k > 1:
+                ranges = [shard_jobs_by_cost(job_off, pk_off, k, r) for r in range(k)]
+        chosen = sorted(free, key=lambda s: s.inflight_cost)[:k]  # (stable: ties keep slot order)
+        self._jobs = []
+        launched = 0
+        for slot, (lo, hi) in zip(chosen, ranges):
+            if hi == lo:
+                continue  # a job heavier than a quantile leaves a range empty
+            cost = float(costs[lo:hi].sum()) if costs is not None else 0.0
+            slot.assigned.append((queue[lo:hi], cost))
+            slot.inflight_cost += cost
+            self.stats.packages_per_slot[slot.position] += 1
+            launched += 1
+        if launched > 1:
+            self.stats.splits += 1
+        self._lock.notify_all()
+
+    def _run(self, slot: _Slot, engine: Engine):
         while True:
             with self._lock:
-                while not self._jobs and not self._closed:
+                slot.idle += 1
+                while True:
+                    self._dispatch()
+                    if slot.assigned or self._closed:
+                        break
                     self._lock.wait()
-                if self._closed and not self._jobs:
+                slot.idle -= 1
+                if not slot.assigned:
                     return
-                jobs, self._jobs = self._jobs, []
+                jobs, cost = slot.assigned.pop(0)
             try:
                 if all(j.idx is not None for j in jobs):
                     codes = engine.verify_jobs_indexed([j.sets for j in jobs], [j.idx for j in jobs])
@@ -313,6 +431,7 @@ class BlsGpuVerifier:
             except Exception as e:  # device failure: every job of the package rejects (index.ts:368-375)
                 codes, err = None, e
             with self._lock:
+                slot.inflight_cost -= cost
                 self.stats.batches += 1
                 self.stats.jobs += len(jobs)
                 self.stats.sets += sum(len(j.sets) for j in jobs)

@@ -10,7 +10,9 @@
 // issued while a round of gossip batches is in flight: its promise's settle time (the loop is
 // busy submitting the round meanwhile), the part of the call that runs on the loop (blocked), and
 // the synchronous entry's device latency on the same engine.
-//   node tools/bench_dropin.js <workload.bin> <engines> <rounds>
+//   node tools/bench_dropin.js <workload.bin> <engines> <rounds> [devices]
+// devices: a comma-separated list of device ordinals or `all` (BlsGpuVerifier's `devices`: `engines`
+// pool engines on each); the line reports the slots' devices and the packages each slot took.
 // workload.bin (little-endian, written by bench.py): u32 magic 0x4C424430, n_keys, n_jobs, n_sets,
 // n_pks, slots; then keys (n_keys x 96 B), job_off (n_jobs+1 u32), pk_off (n_sets+1 u32),
 // pk_idx (n_pks u32, indices into keys), roots (n_sets x 32 B), sigs (n_sets x 96 B), and the
@@ -20,7 +22,7 @@ const path = require("path");
 const m = require(path.join(__dirname, "..", "lodestar_amd", "js", "index.js"));
 
 async function main() {
-  const [file, enginesArg, roundsArg] = process.argv.slice(2);
+  const [file, enginesArg, roundsArg, devicesArg] = process.argv.slice(2);
   const buf = fs.readFileSync(file);
   const u32 = (off) => buf.readUInt32LE(off);
   if (u32(0) !== 0x4c424430) throw Error("bad workload file");
@@ -46,7 +48,9 @@ async function main() {
   const expected = takeU32(nJobs);
   const engines = Number(enginesArg || 4), rounds = Math.max(Number(roundsArg || 10), 1);
 
-  const pool = new m.BlsGpuVerifier({engines});
+  // (without the fourth argument: one slot on device 0, as before)
+  const devices = devicesArg === undefined ? undefined : devicesArg === "all" ? "all" : devicesArg.split(",").map(Number);
+  const pool = new m.BlsGpuVerifier(devices === undefined ? {engines} : {engines, devices});
   const handles = pool.registerPubkeys(Array.from({length: nKeys}, (_, k) => keys.subarray(96 * k, 96 * k + 96)));
   // the ISignatureSet objects the gossip validators would hold (built outside the timed region)
   const jobs = [];
@@ -122,7 +126,8 @@ async function main() {
   await pool.close();
   console.log(JSON.stringify({value_dropin: Math.round(nSets / med), value_dropin_mean: Math.round((nSets * rounds) / el),
                               seconds: Number(el.toFixed(3)), rounds, round_s_median: Number(med.toFixed(4)),
-                              engines, gpu_max_hw_queues: m.addon.hwQueues(), sets_per_round: nSets,
+                              engines, devices: pool.devices, packagesPerSlot: stats.packagesPerSlot, splits: stats.splits,
+                              gpu_max_hw_queues: m.addon.hwQueues(), sets_per_round: nSets,
                               batches: stats.batches, mean_sets_per_batch: Math.round(stats.sets / Math.max(stats.batches, 1)),
                               // the synchronous entry: the device latency under the pool's load, the
                               // quantity round 5 reported under this name (its verifyOnMainThread was
