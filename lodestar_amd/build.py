@@ -129,6 +129,7 @@ KZG_CELLS_HARNESS = os.path.join(ROOT, "build", "lb_kzg_cells_harness.so")
 KZG_FK20_HARNESS = os.path.join(ROOT, "build", "lb_kzg_fk20_harness.so")
 KZG_RECOVER_HARNESS = os.path.join(ROOT, "build", "lb_kzg_recover_harness.so")
 SEARCH_HARNESS = os.path.join(ROOT, "build", "lb_search_harness.so")
+PIPELINE_HARNESS = os.path.join(ROOT, "build", "lb_pipeline_harness.so")
 
 
 def build_harness(force=False, verbose=True):
@@ -185,6 +186,12 @@ def build_search_harness(force=False, verbose=True):
     the CPU (tests/test_search_plan_cpu.py; tests/test_gpu_parity.py compares the device's trace with it)"""
     return _build_so(os.path.join(HDIR, "lb_search_harness.cpp"), SEARCH_HARNESS,
                      [os.path.join(HDIR, "search_model.h")], ("-O2", "-std=c++17"), force, verbose)
+
+
+def build_pipeline_harness(force=False, verbose=True):
+    """the batch pipeline's form selection (csrc/lb_pipeline_plan.h) on the CPU (tests/test_pipeline_plan_cpu.py)"""
+    return _build_so(os.path.join(HDIR, "lb_pipeline_harness.cpp"), PIPELINE_HARNESS, flags=("-O2", "-std=c++17"),
+                     force=force, verbose=verbose)
 
 
 def build_cpu_pool(force=False, verbose=True):
@@ -244,6 +251,7 @@ def build_all(force=False):
     build_kzg_fk20_harness(force)
     build_kzg_recover_harness(force)
     build_search_harness(force)
+    build_pipeline_harness(force)
     build_cpu_pool(force)
     build_ubench(force)
 

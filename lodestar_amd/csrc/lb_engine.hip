@@ -25,6 +25,7 @@
 #include "lb_engine_impl.h"  // dbuf, lb_engine, LB_HIP, run_simple: shared with lb_kzg_host.hip (the KZG calls)
 #include "lb_kdecl.h"  // kernels of the other translation units (split build)
 #include "lb_search_plan.h"  // the invalid-set search's planner and interpreter (device-free)
+// (lb_pipeline_plan.h, every stage's kernel form, comes with lb_engine_impl.h: lb_engine holds its knobs)
 
 #define LB_ABI_VERSION 1
 
@@ -129,7 +130,7 @@ struct busy_scope {
 template <class E>
 static bool device_alone(const E* e) {
   if (e->latency) return true;  // its reserved CUs run nothing else
-  if (e->alone_force >= 0) return e->alone_force != 0;
+  if (e->knobs.alone_force >= 0) return e->knobs.alone_force != 0;
   if (g_device_busy[e->device].load(std::memory_order_relaxed) > 1) return false;
   int64_t other;
   {
@@ -254,30 +255,16 @@ int32_t lb_engine_create_ex(int32_t device, uint32_t flags, lb_engine** out) {
   // profiles/r3_search_split_ab.txt)
   int prio_least = 0, prio_greatest = 0;
   hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest);
-  if (const char* mw = getenv("LB_MILLER_WAVE_MAX")) e->miller_wave_max = (uint32_t)strtoul(mw, nullptr, 10);
-  if (const char* rm = getenv("LB_ROW_MAX")) e->row_max = (uint32_t)strtoul(rm, nullptr, 10);
-  if (const char* rf = getenv("LB_ROW_FE")) e->row_fe = std::atoi(rf) != 0;
-  if (const char* ml = getenv("LB_MILLER_LDS3_MAX")) e->miller_lds3_max = (uint32_t)strtoul(ml, nullptr, 10);
-  if (const char* mf = getenv("LB_MILLER_FORM")) e->miller_form = !strcmp(mf, "lane") ? 1 : !strcmp(mf, "g8") ? 2 : 0;
-  if (const char* hg = getenv("LB_HASH_G8_MAX")) e->hash_g8_max = (uint32_t)strtoul(hg, nullptr, 10);
-  if (const char* hr = getenv("LB_HASH_ROW_MAX")) e->hash_row_max = (uint32_t)strtoul(hr, nullptr, 10);
-  if (const char* dr = getenv("LB_DEC_ROW_MAX")) e->dec_row_max = (uint32_t)strtoul(dr, nullptr, 10);
+  e->knobs = pipe_knobs_from_env([](const char* name) -> const char* { return getenv(name); });
   if (const char* hc = getenv("LB_HASH_ROW_CAREFUL")) e->hash_row_careful = std::atoi(hc) != 0;
-  if (const char* sg = getenv("LB_SUBGROUP_G8_MAX")) e->subgroup_g8_max = (uint32_t)strtoul(sg, nullptr, 10);
-  if (const char* ss = getenv("LB_SMALL_S_MAX")) e->small_s_max = (uint32_t)strtoul(ss, nullptr, 10);
-  if (const char* sg8 = getenv("LB_SMALL_S_G8_MAX")) e->small_s_g8_max = (uint32_t)strtoul(sg8, nullptr, 10);
-  if (const char* sm = getenv("LB_SEARCH_SMALL_MAX")) e->search_small_max = (uint32_t)strtoul(sm, nullptr, 10);
   if (const char* sm = getenv("LB_SEARCH_MERGE")) e->search_merge = std::atoi(sm) != 0;
   if (const char* sm = getenv("LB_SEARCH_ROOTSUM")) e->search_rootsum = std::atoi(sm) != 0;
-  if (const char* sf = getenv("LB_SMSM_FORM")) e->smsm_form = !strcmp(sf, "lane") ? 1 : !strcmp(sf, "g8") ? 2 : 0;
   if (const char* sc = getenv("LB_SEARCH_CHUNK")) {
     const uint32_t v = (uint32_t)strtoul(sc, nullptr, 10);
     if (v >= 1 && v <= 64) e->search_chunk = v;
   }
   if (const char* sm = getenv("LB_SEARCH_BLOCKS")) e->search_blk = std::atoi(sm) != 0;
   if (const char* sm = getenv("LB_ROOT_SHUFFLE")) e->root_shuffle = std::atoi(sm) != 0;
-  if (const char* sm = getenv("LB_MSM_G8")) e->msm_g8 = std::atoi(sm) != 0;
-  if (const char* al = getenv("LB_ALONE")) e->alone_force = std::atoi(al) != 0 ? 1 : 0;
   {
     const char* on = getenv("LB_PK_COMB");
     const char* mb = getenv("LB_PK_COMB_MB");
@@ -342,9 +329,9 @@ int32_t lb_engine_create_ex(int32_t device, uint32_t flags, lb_engine** out) {
     hipEventCreate(&e->ev0[i]);
     hipEventCreate(&e->ev1[i]);
   }
-  // Reserve the streams' scratch now, one engine at a time, for the largest private segments they
-  // can run (s1: k_miller_lane<2>, 2.7 KB per lane): empty dispatches over more waves than the
-  // device holds.
+  // Reserve the streams' scratch now, one engine at a time, for the largest private segments the
+  // forms of lb_pipeline_plan.h can put on them: empty dispatches over more waves than the device
+  // holds.  s1: MILLER_LANE2 (k_miller_lane<2>, 2.7 KB per lane) and HFIN_LANE (k_hash_finish).
   // The runtime sizes a queue's scratch for the largest segment it has run, from one per-process
   // pool, and a queue that cannot grow it mid-run aborts asynchronously; growing it here, with the
   // stream synchronised, turns an exhausted pool into LB_ERR_DEVICE from lb_engine_create.
@@ -358,22 +345,24 @@ int32_t lb_engine_create_ex(int32_t device, uint32_t flags, lb_engine** out) {
                            nullptr, nullptr, nullptr, nullptr, nullptr);
         hipLaunchKernelGGL(k_hash_finish, dim3(4096), dim3(LB_INV_TPB), 0, e->stream, 0u, e->n_u.as<uint32_t>(),
                            nullptr, nullptr, nullptr, 0u);
-        // s2 and s3 the same way (round 6), each for the kernels with a private segment it runs,
-        // at their largest dispatch: s2 the signature decode over the whole device (472 B per
-        // lane), the 8-lane subgroup check and r_i sig_i of small batches (616 / 868 B); s3 the
-        // 96-byte-key chunk sums (584 B).  The rest of s2 / s3's kernels need less per lane and
-        // fewer lanes (resource table: DESIGN.md section 5.2).
+        // s2 and s3 the same way (round 6), each for the forms with a private segment it runs,
+        // at their largest dispatch.  s2: DEC_LANE, the signature decode over the whole device
+        // (472 B per lane), and below SUBGROUP_G8 and SSUM_TERMS_G8 (616 / 868 B), whose largest
+        // dispatches are their knobs.  s3: PKC_BYTES, the 96-byte-key chunk sums (584 B), and
+        // PKB_SPLIT_ROWP.  The other forms of s2 / s3 need less per lane and fewer lanes (resource
+        // table: DESIGN.md section 5.2).
+        const pipe_knobs& k = e->knobs;
         hipLaunchKernelGGL(k_decompress_sigs, dim3(4096), dim3(LB_TPB), 0, e->stream2, 0u, nullptr, nullptr, nullptr,
                            nullptr, nullptr, nullptr);
         hipLaunchKernelGGL(k_pk_chunks, dim3(4096), dim3(LB_TPB), 0, e->stream3, 0u, nullptr, nullptr, nullptr, nullptr);
-        // the row r PK ladder (one row per set), at the largest small batch
-        hipLaunchKernelGGL(k_pk_blind_rowp, dim3(std::max<uint32_t>(1u, e->row_max)), dim3(64), 0, e->stream3,
+        // the row r PK ladder (one row per set), at the largest small batch: row_max sets
+        hipLaunchKernelGGL(k_pk_blind_rowp, dim3(std::max<uint32_t>(1u, k.row_max)), dim3(64), 0, e->stream3,
                            0u, nullptr, nullptr, nullptr, nullptr);
         // (one wave per 8 sets, at least one wave, at most 16 384: more than the device holds)
         auto g8_waves = [](uint32_t sets) { return dim3(std::min<uint32_t>(16384u, std::max<uint32_t>(1u, sets / 8 + 1))); };
-        hipLaunchKernelGGL(k_sig_subgroup_g8, g8_waves(e->subgroup_g8_max), dim3(64), 0, e->stream2, 0u, nullptr,
+        hipLaunchKernelGGL(k_sig_subgroup_g8, g8_waves(k.subgroup_g8_max), dim3(64), 0, e->stream2, 0u, nullptr,
                            nullptr, nullptr);
-        hipLaunchKernelGGL(k_sig_blind_g8, g8_waves(e->small_s_g8_max), dim3(64), 0, e->stream2, 0u, nullptr, nullptr,
+        hipLaunchKernelGGL(k_sig_blind_g8, g8_waves(k.small_s_g8_max), dim3(64), 0, e->stream2, 0u, nullptr, nullptr,
                            nullptr, nullptr, nullptr);
         ok = hipGetLastError() == hipSuccess && hipStreamSynchronize(e->stream) == hipSuccess &&
              hipStreamSynchronize(e->stream2) == hipSuccess && hipStreamSynchronize(e->stream3) == hipSuccess;
@@ -491,7 +480,7 @@ static int32_t batch_fill(lb_engine* e, lb_batch* b, uint32_t n_jobs, const uint
   std::vector<uint32_t>& chunk_lo = b->h_chunk_lo;
   set_chunk_off.resize(n_sets + 1);
   chunk_lo.clear();
-  const uint32_t pkc = n_sets <= e->row_max ? LB_PK_CHUNK_SMALL : LB_PK_CHUNK;
+  const uint32_t pkc = pipe_pk_chunks_small(e->knobs, n_sets) ? LB_PK_CHUNK_SMALL : LB_PK_CHUNK;
   for (uint32_t i = 0; i < n_sets; i++) {
     set_chunk_off[i] = (uint32_t)chunk_lo.size();
     for (uint32_t k = set_pk_offsets[i]; k < set_pk_offsets[i + 1]; k += pkc)
@@ -743,101 +732,97 @@ struct stage_scope {
 
 // Bucket sums -> S_j = sum_d d B_d per instance j (n_inst instances of W windows, buckets
 // [j W 256, (j+1) W 256) of bsum) -> element out0 + j of `out` (SoA, stride n_out).
-// entries: bucket entries (point, window) of the launch, an upper bound.  The bucket sums go by
-// 8-lane groups (one wave per bucket) only when buckets hold several chunks on average (the batch
-// MSM: ~30 chunk sums per bucket); a search round's many small instances leave ~one chunk per
-// bucket, which one lane per bucket sums without the wave's idle groups.
+// entries: bucket entries (point, window) of the launch, an upper bound; the forms: pipe_plan_msm.
 static hipError_t msm_reduce(lb_engine* e, hipStream_t st, uint32_t bcap, uint32_t nb, uint32_t n_inst, int W,
                              uint32_t* out, uint32_t n_out, uint32_t out0, uint64_t entries, uint32_t chunk) {
-  if (e->msm_g8) {
+  const pipe_msm_plan p = pipe_plan_msm(e->knobs, entries, chunk, nb, device_alone(e));
+  const bool w4 = W == LB_MSM_W;  // else LB_SMSM_W windows
+  if (p.reduce == MSMR_WINDOW_HORNER) {
     hipError_t r = e->wsum.ensure((size_t)n_inst * W * sizeof(g2j));
     if (r != hipSuccess) return r;
-    // 8-lane bucket sums only while the device runs no other batch: they issue ~6x the
-    // instructions of one lane per bucket (profiles/r4_r3_valu.txt), which under load is the cost
-    if (entries >= (uint64_t)4 * chunk * nb && device_alone(e))
-      hipLaunchKernelGGL(k_msm_buckets_g8, dim3(nb), dim3(64), 0, st, e->bch.as<uint32_t>(), e->bacc.as<uint32_t>(),
-                         bcap, e->bsum.as<uint32_t>(), nb);
-    else
-      hipLaunchKernelGGL(k_msm_buckets, dim3(nblk(nb)), dim3(LB_TPB), 0, st, e->bch.as<uint32_t>(),
-                         e->bacc.as<uint32_t>(), bcap, e->bsum.as<uint32_t>(), nb);
-    hipLaunchKernelGGL(k_msm_window_g8, dim3(n_inst * W), dim3(256), 0, st, e->bsum.as<uint32_t>(), nb,
-                       e->wsum.as<uint32_t>(), n_inst * W);
-    if (W == LB_MSM_W)
-      hipLaunchKernelGGL(k_msm_horner_g8<LB_MSM_W>, dim3((n_inst + 7) / 8), dim3(64), 0, st, e->wsum.as<uint32_t>(),
-                         n_inst, out, n_out, out0);
-    else
-      hipLaunchKernelGGL(k_msm_horner_g8<LB_SMSM_W>, dim3((n_inst + 7) / 8), dim3(64), 0, st, e->wsum.as<uint32_t>(),
-                         n_inst, out, n_out, out0);
-    return hipGetLastError();
   }
-  hipLaunchKernelGGL(k_msm_buckets, dim3(nblk(nb)), dim3(LB_TPB), 0, st, e->bch.as<uint32_t>(), e->bacc.as<uint32_t>(),
-                     bcap, e->bsum.as<uint32_t>(), nb);
-  if (W == LB_MSM_W)
-    hipLaunchKernelGGL(k_msm_reduce<LB_MSM_W>, dim3(n_inst), dim3(64 * LB_MSM_W), 0, st, e->bsum.as<uint32_t>(), nb, out,
-                       n_out, out0);
-  else
-    hipLaunchKernelGGL(k_msm_reduce<LB_SMSM_W>, dim3(n_inst), dim3(64 * LB_SMSM_W), 0, st, e->bsum.as<uint32_t>(), nb,
-                       out, n_out, out0);
+  const bool bg8 = p.buckets == MSMB_G8;  // one wave per bucket, else one lane
+  hipLaunchKernelGGL(bg8 ? k_msm_buckets_g8 : k_msm_buckets, dim3(bg8 ? nb : nblk(nb)), dim3(bg8 ? 64 : LB_TPB), 0, st,
+                     e->bch.as<uint32_t>(), e->bacc.as<uint32_t>(), bcap, e->bsum.as<uint32_t>(), nb);
+  switch (p.reduce) {
+    case MSMR_WINDOW_HORNER:
+      hipLaunchKernelGGL(k_msm_window_g8, dim3(n_inst * W), dim3(256), 0, st, e->bsum.as<uint32_t>(), nb,
+                         e->wsum.as<uint32_t>(), n_inst * W);
+      hipLaunchKernelGGL(w4 ? k_msm_horner_g8<LB_MSM_W> : k_msm_horner_g8<LB_SMSM_W>, dim3((n_inst + 7) / 8), dim3(64), 0,
+                         st, e->wsum.as<uint32_t>(), n_inst, out, n_out, out0);
+      break;
+    case MSMR_REDUCE:
+      hipLaunchKernelGGL(w4 ? k_msm_reduce<LB_MSM_W> : k_msm_reduce<LB_SMSM_W>, dim3(n_inst), dim3(64 * W), 0, st,
+                         e->bsum.as<uint32_t>(), nb, out, n_out, out0);
+      break;
+  }
   return hipGetLastError();
 }
 
+// members per chunk of the per-root sums (the grouping builds the chunks, per_root_chain sums them)
+static inline uint32_t gsum_chunk(gsum_form f) { return f == GSUM_WAVE ? LB_GROUP_CHUNK_WAVE : LB_GROUP_CHUNK; }
+
 // s1: P_u = sum of r_i PK_i over the live sets of root u (set_live; k_gsum_*), the Miller loops
-// (form by root count and device load) into the leaves of the root product tree, the tree.
+// (pipe_plan_miller, with a fresh device_alone sample) into the leaves of the root product tree,
+// the tree.  Follows e->plan, the batch plan of the run_pipeline that calls it.
 static hipError_t per_root_chain(lb_engine* e, uint32_t n, uint32_t nuh, uint32_t mu) {
   hipStream_t s1 = e->stream;
   const uint32_t* nu = e->n_u.as<uint32_t>();
-  const bool row = e->alone && e->row_fe;  // the row engine, up to row_max roots / tree nodes per launch
-  const bool row_roots = row && nuh <= e->row_max;
+  const pipe_batch_plan& bp = e->plan;
   {
     stage_scope sc(e, ST_GSUM, s1);
     // chunks of <= gchunk members: at most nuh + n / gchunk of them
-    const uint32_t nch = nuh + n / e->gchunk;
-    if (e->alone)
-      hipLaunchKernelGGL(k_gsum_wave, dim3(nblk(nch)), dim3(LB_TPB), 0, s1, n, nu, e->gch.as<uint32_t>(),
-                         e->chunk_beg.as<uint32_t>(), e->chunk_end.as<uint32_t>(), e->chunk_root.as<uint32_t>(),
-                         e->members.as<uint32_t>(), e->set_live.as<uint32_t>(), e->rpk.as<uint32_t>(), e->gacc.as<uint32_t>());
-    else
-      hipLaunchKernelGGL(k_gsum_chunks, dim3(nblk(nch)), dim3(LB_TPB), 0, s1, n, nu,
-                         e->gch.as<uint32_t>(), e->chunk_beg.as<uint32_t>(), e->chunk_end.as<uint32_t>(),
-                         e->members.as<uint32_t>(), e->set_live.as<uint32_t>(), e->rpk.as<uint32_t>(), e->gacc.as<uint32_t>());
+    const uint32_t nch = nuh + n / gsum_chunk(bp.gsum);
+    switch (bp.gsum) {
+      case GSUM_WAVE:
+        hipLaunchKernelGGL(k_gsum_wave, dim3(nblk(nch)), dim3(LB_TPB), 0, s1, n, nu, e->gch.as<uint32_t>(),
+                           e->chunk_beg.as<uint32_t>(), e->chunk_end.as<uint32_t>(), e->chunk_root.as<uint32_t>(),
+                           e->members.as<uint32_t>(), e->set_live.as<uint32_t>(), e->rpk.as<uint32_t>(), e->gacc.as<uint32_t>());
+        break;
+      case GSUM_CHUNKS:
+        hipLaunchKernelGGL(k_gsum_chunks, dim3(nblk(nch)), dim3(LB_TPB), 0, s1, n, nu,
+                           e->gch.as<uint32_t>(), e->chunk_beg.as<uint32_t>(), e->chunk_end.as<uint32_t>(),
+                           e->members.as<uint32_t>(), e->set_live.as<uint32_t>(), e->rpk.as<uint32_t>(), e->gacc.as<uint32_t>());
+        break;
+    }
     hipLaunchKernelGGL(k_gsum_final, dim3(nblk_inv(nuh)), dim3(LB_INV_TPB), 0, s1, n, nu, e->gch.as<uint32_t>(),
                        e->gacc.as<uint32_t>(), e->gp_aff.as<uint32_t>(), e->gp_inf.as<uint32_t>(),
-                       e->alone ? 1u : 0u);
+                       bp.gsum == GSUM_WAVE ? 1u : 0u);
   }
   {
     stage_scope sc(e, ST_MILLER, s1);
-    const bool shared = e->miller_form == 1 ||
-                        (e->miller_form == 0 && !device_alone(e));
-    if (row_roots) {
-      hipLaunchKernelGGL(k_miller_row, dim3(nuh), dim3(LBR_NT), 0, s1, n, mu, nu, e->gp_aff.as<uint32_t>(),
-                         e->gp_inf.as<uint32_t>(), e->h_aff.as<uint32_t>(), e->treeP.as<uint32_t>());
-    } else if (nuh <= e->miller_wave_max) {
-      hipLaunchKernelGGL(k_miller_wave, dim3(nuh), dim3(64), 0, s1, n, mu, nu, e->gp_aff.as<uint32_t>(),
-                         e->gp_inf.as<uint32_t>(), e->h_aff.as<uint32_t>(), e->treeP.as<uint32_t>());
-    } else if (shared) {
-      hipError_t r = e->park.ensure((size_t)2 * 84 * 4 * n);  // T and a temporary per root: two slots of 3 fp2_28
-      if (r != hipSuccess) return r;
-      if (nuh <= e->miller_lds3_max)
-        hipLaunchKernelGGL(k_miller_lane<3>, dim3(nblk(nuh)), dim3(LB_TPB), 0, s1, n, mu, nu, e->gp_aff.as<uint32_t>(),
-                           e->gp_inf.as<uint32_t>(), e->h_aff.as<uint32_t>(), e->treeP.as<uint32_t>(),
-                           e->park.as<uint32_t>());
-      else
-        hipLaunchKernelGGL(k_miller_lane<2>, dim3(nblk(nuh)), dim3(LB_TPB), 0, s1, n, mu, nu, e->gp_aff.as<uint32_t>(),
-                           e->gp_inf.as<uint32_t>(), e->h_aff.as<uint32_t>(), e->treeP.as<uint32_t>(),
-                           e->park.as<uint32_t>());
-    } else {
-      hipLaunchKernelGGL(k_miller_g8, dim3((nuh + LBG_ROOTS - 1) / LBG_ROOTS), dim3(64 * LBG_WAVES), 0, s1, n, mu, nu,
-                         e->gp_aff.as<uint32_t>(), e->gp_inf.as<uint32_t>(), e->h_aff.as<uint32_t>(),
-                         e->treeP.as<uint32_t>());
+    const miller_form mf = pipe_plan_miller(e->knobs, bp, nuh, device_alone(e));
+    switch (mf) {
+      case MILLER_ROW:
+        hipLaunchKernelGGL(k_miller_row, dim3(nuh), dim3(LBR_NT), 0, s1, n, mu, nu, e->gp_aff.as<uint32_t>(),
+                           e->gp_inf.as<uint32_t>(), e->h_aff.as<uint32_t>(), e->treeP.as<uint32_t>());
+        break;
+      case MILLER_WAVE:
+        hipLaunchKernelGGL(k_miller_wave, dim3(nuh), dim3(64), 0, s1, n, mu, nu, e->gp_aff.as<uint32_t>(),
+                           e->gp_inf.as<uint32_t>(), e->h_aff.as<uint32_t>(), e->treeP.as<uint32_t>());
+        break;
+      case MILLER_LANE3:
+      case MILLER_LANE2: {
+        hipError_t r = e->park.ensure((size_t)2 * 84 * 4 * n);  // T and a temporary per root: two slots of 3 fp2_28
+        if (r != hipSuccess) return r;
+        hipLaunchKernelGGL(mf == MILLER_LANE3 ? k_miller_lane<3> : k_miller_lane<2>, dim3(nblk(nuh)), dim3(LB_TPB), 0, s1,
+                           n, mu, nu, e->gp_aff.as<uint32_t>(), e->gp_inf.as<uint32_t>(), e->h_aff.as<uint32_t>(),
+                           e->treeP.as<uint32_t>(), e->park.as<uint32_t>());
+        break;
+      }
+      case MILLER_G8:
+        hipLaunchKernelGGL(k_miller_g8, dim3((nuh + LBG_ROOTS - 1) / LBG_ROOTS), dim3(64 * LBG_WAVES), 0, s1, n, mu, nu,
+                           e->gp_aff.as<uint32_t>(), e->gp_inf.as<uint32_t>(), e->h_aff.as<uint32_t>(),
+                           e->treeP.as<uint32_t>());
+        break;
     }
   }
   {
     stage_scope sc(e, ST_TREE_P, s1);
     for (uint32_t lo = mu / 2; lo >= 1; lo /= 2) {
-      if (row && lo <= e->row_max)
-        hipLaunchKernelGGL(k_tree_up_row, dim3(lo), dim3(LBR_NT), 0, s1, mu, lo, nu, e->treeP.as<uint32_t>());
-      else
-        hipLaunchKernelGGL(k_tree_up_U, dim3(lo), dim3(64), 0, s1, mu, lo, nu, e->treeP.as<uint32_t>());
+      const bool row = pipe_tree_form(e->knobs, bp, lo) == FE_ROW;
+      hipLaunchKernelGGL(row ? k_tree_up_row : k_tree_up_U, dim3(lo), dim3(row ? LBR_NT : 64), 0, s1, mu, lo, nu,
+                         e->treeP.as<uint32_t>());
     }
   }
   return hipGetLastError();
@@ -850,11 +835,11 @@ static int32_t run_pipeline(lb_engine* e, lb_batch* b, const uint64_t* scalars, 
                             bool unblinded) {
   const uint32_t n = b->n_sets, nj = b->n_jobs;
   e->partial_serial = 0;
-  e->alone = device_alone(e);
-  e->gchunk = e->alone ? LB_GROUP_CHUNK_WAVE : LB_GROUP_CHUNK;
-  const bool row = e->alone && e->row_fe;         // the row engine's forms, each up to its own item count
-  const bool row_small = row && n <= e->row_max;  // ... those over the sets of a small batch
-  const bool one_unblinded = n == 1 && !scalars && unblinded;
+  const pipe_shape shape{n, b->n_chunks, b->n_comb, b->indexed, b->route_eng == e, scalars != nullptr, unblinded,
+                         e->root_shuffle};
+  e->plan = pipe_plan_batch(e->knobs, shape, device_alone(e));
+  const pipe_batch_plan& bp = e->plan;
+  const uint32_t gchunk = gsum_chunk(bp.gsum);
   int st = fill_scalars(e, n, scalars, unblinded);
   if (st != LB_OK) return st;
   mj = 1;
@@ -917,92 +902,89 @@ static int32_t run_pipeline(lb_engine* e, lb_batch* b, const uint64_t* scalars, 
   LB_HIP(hipStreamWaitEvent(s3_, e->ev_fork, 0));
   const uint32_t* nu = e->n_u.as<uint32_t>();
   if (n) {
-    // ---- pubkeys, r*PK: on s3 beside the signature decode for batches up to small_s_max sets
-    // (shortens the signature side's chain); on s2 before the decode for large batches, where the
-    // two would contend with the per-root chain on s1 for the whole chip
-    // (also for a large batch alone on the device: its s1 chain then slowed by more than the s2
-    // chain gained, 5.2 -> 5.1 M sets/s, round-3 A/B)
-    const hipStream_t s3 = n <= e->small_s_max ? s3_ : s2;
+    // ---- pubkeys, r*PK: on s3 beside the signature decode, or on s2 before it
+    const bool pk_split = bp.pk_on == PK_ON_S3;  // on its own stream the pubkey side splits: statuses, then r PK
+    const hipStream_t s3 = pk_split ? s3_ : s2;
+    // r_i sig_i on s3 beside the subgroup check (small batches alone, row forms, one-workgroup sum)
+    const bool sb_par = bp.ssum == SSUM_PAR_W4;
     {
       stage_scope sc(e, ST_PK_CHUNKS, s3);
-      if (nc && b->indexed)
-        hipLaunchKernelGGL(k_pk_chunks_idx, dim3(nblk(nc)), dim3(LB_TPB), 0, s3, nc, b->d_chunk_lo.as<uint32_t>(),
-                           b->d_pks.as<uint32_t>(), e->table.as<uint32_t>(), e->table_n, e->chunk_acc.as<uint32_t>(),
-                           e->chunk_status.as<int32_t>());
-      else if (nc)
-        hipLaunchKernelGGL(k_pk_chunks, dim3(nblk(nc)), dim3(LB_TPB), 0, s3, nc, b->d_chunk_lo.as<uint32_t>(),
-                           b->d_pks.as<uint8_t>(), e->chunk_acc.as<uint32_t>(), e->chunk_status.as<int32_t>());
+      switch (bp.pk_chunks) {
+        case PKC_INDEXED:
+          hipLaunchKernelGGL(k_pk_chunks_idx, dim3(nblk(nc)), dim3(LB_TPB), 0, s3, nc, b->d_chunk_lo.as<uint32_t>(),
+                             b->d_pks.as<uint32_t>(), e->table.as<uint32_t>(), e->table_n, e->chunk_acc.as<uint32_t>(),
+                             e->chunk_status.as<int32_t>());
+          break;
+        case PKC_BYTES:
+          hipLaunchKernelGGL(k_pk_chunks, dim3(nblk(nc)), dim3(LB_TPB), 0, s3, nc, b->d_chunk_lo.as<uint32_t>(),
+                             b->d_pks.as<uint8_t>(), e->chunk_acc.as<uint32_t>(), e->chunk_status.as<int32_t>());
+          break;
+        case PKC_NONE:
+          break;
+      }
     }
-    // on its own stream the pubkey side splits: the aggregates' statuses (what the job statuses
-    // and so the S side need) first, then the r PK ladder (only the per-root sums need it)
-    const bool pk_split = s3 != s2;
-    // small batches alone: the r PK ladder (k_pk_blind mode 2) with row products, one 16-lane row
-    // per set (on s3, before r_i sig_i; a fourth stream per engine, round 6, put 7 engines' 28
-    // streams past what the device schedules without stalls: +10 ms on some batches)
-    const bool pk_rowp = pk_split && row_small;
-    // r_i sig_i on s3 beside the subgroup check (small batches alone, row forms, one-workgroup sum)
-    const bool sb_par = pk_split && !one_unblinded && row_small && n <= e->small_s_max && n <= e->small_s_g8_max;
     {
       stage_scope sc(e, ST_PK_BLIND, s3);
-      // modes: 0 all; split: 1 aggregate + status, then 2 the per-set ladder
-      const uint32_t m0 = pk_split ? 1u : 0u, m1 = pk_split ? 2u : 0u;
-      // an indexed batch routed at upload on this engine: the statuses over every set (mode 1),
-      // then the comb over its single-key sets and the ladder over the compacted rest
-      const bool route = b->indexed && b->n_comb && b->route_eng == e && !pk_rowp;
-      if (route) {
-        const uint32_t n_lad = n - b->n_comb;
-        const uint32_t* sel = b->d_route.as<uint32_t>();
-        hipLaunchKernelGGL(k_pk_blind, dim3(nblk_inv(n)), dim3(LB_INV_TPB), 0, s3, n, nc, b->d_set_chunk_off.as<uint32_t>(),
-                           e->chunk_acc.as<uint32_t>(), e->chunk_status.as<int32_t>(), e->pk_aff.as<uint32_t>(),
-                           e->scalars.as<uint64_t>(), e->rpk.as<uint32_t>(), e->pk_status.as<int32_t>(), 1u, nullptr, 0u);
-        LB_HIP(hipEventRecord(e->ev_pkst, s3));
-        hipLaunchKernelGGL(k_pk_blind_comb, dim3(nblk(b->n_comb)), dim3(LB_TPB), 0, s3, n, b->n_comb, sel,
-                           b->d_pk_off.as<uint32_t>(), b->d_pks.as<uint32_t>(), e->comb.as<uint32_t>(), e->comb_n,
-                           e->pk_aff.as<uint32_t>(), e->scalars.as<uint64_t>(), e->pk_status.as<int32_t>(),
-                           e->rpk.as<uint32_t>());
-        e->comb_sets += b->n_comb;
-        if (n_lad)
-          hipLaunchKernelGGL(k_pk_blind, dim3(nblk_inv(n_lad)), dim3(LB_INV_TPB), 0, s3, n, nc,
-                             b->d_set_chunk_off.as<uint32_t>(), e->chunk_acc.as<uint32_t>(), e->chunk_status.as<int32_t>(),
-                             e->pk_aff.as<uint32_t>(), e->scalars.as<uint64_t>(), e->rpk.as<uint32_t>(),
-                             e->pk_status.as<int32_t>(), 2u, sel + b->n_comb, n_lad);
-      }
-      for (uint32_t mode = m0; !route && mode <= m1; mode++) {
-        if (mode == 2u && pk_rowp) {
+      // k_pk_blind's modes: 0 all; 1 aggregate + status, then 2 the per-set ladder
+      const uint32_t mode0 = bp.pk_blind == PKB_ONE_PASS ? 0u : 1u;
+      hipLaunchKernelGGL(k_pk_blind, dim3(nblk_inv(n)), dim3(LB_INV_TPB), 0, s3, n, nc, b->d_set_chunk_off.as<uint32_t>(),
+                         e->chunk_acc.as<uint32_t>(), e->chunk_status.as<int32_t>(), e->pk_aff.as<uint32_t>(),
+                         e->scalars.as<uint64_t>(), e->rpk.as<uint32_t>(), e->pk_status.as<int32_t>(), mode0, nullptr, 0u);
+      if (mode0 == 1u) LB_HIP(hipEventRecord(e->ev_pkst, s3));
+      switch (bp.pk_blind) {
+        case PKB_ONE_PASS:
+          break;
+        case PKB_SPLIT:
+          hipLaunchKernelGGL(k_pk_blind, dim3(nblk_inv(n)), dim3(LB_INV_TPB), 0, s3, n, nc, b->d_set_chunk_off.as<uint32_t>(),
+                             e->chunk_acc.as<uint32_t>(), e->chunk_status.as<int32_t>(), e->pk_aff.as<uint32_t>(),
+                             e->scalars.as<uint64_t>(), e->rpk.as<uint32_t>(), e->pk_status.as<int32_t>(), 2u, nullptr, 0u);
+          break;
+        case PKB_SPLIT_ROWP:
           hipLaunchKernelGGL(k_pk_blind_rowp, dim3(n), dim3(64), 0, s3, n, e->pk_aff.as<uint32_t>(),
                              e->scalars.as<uint64_t>(), e->rpk.as<uint32_t>(), e->pk_status.as<int32_t>());
-          continue;
+          break;
+        case PKB_ROUTE: {
+          // the comb over the batch's single-key sets and the ladder over the compacted rest
+          const uint32_t n_lad = n - b->n_comb;
+          const uint32_t* sel = b->d_route.as<uint32_t>();
+          hipLaunchKernelGGL(k_pk_blind_comb, dim3(nblk(b->n_comb)), dim3(LB_TPB), 0, s3, n, b->n_comb, sel,
+                             b->d_pk_off.as<uint32_t>(), b->d_pks.as<uint32_t>(), e->comb.as<uint32_t>(), e->comb_n,
+                             e->pk_aff.as<uint32_t>(), e->scalars.as<uint64_t>(), e->pk_status.as<int32_t>(),
+                             e->rpk.as<uint32_t>());
+          e->comb_sets += b->n_comb;
+          if (n_lad)
+            hipLaunchKernelGGL(k_pk_blind, dim3(nblk_inv(n_lad)), dim3(LB_INV_TPB), 0, s3, n, nc,
+                               b->d_set_chunk_off.as<uint32_t>(), e->chunk_acc.as<uint32_t>(), e->chunk_status.as<int32_t>(),
+                               e->pk_aff.as<uint32_t>(), e->scalars.as<uint64_t>(), e->rpk.as<uint32_t>(),
+                               e->pk_status.as<int32_t>(), 2u, sel + b->n_comb, n_lad);
+          break;
         }
-        hipLaunchKernelGGL(k_pk_blind, dim3(nblk_inv(n)), dim3(LB_INV_TPB), 0, s3, n, nc, b->d_set_chunk_off.as<uint32_t>(),
-                           e->chunk_acc.as<uint32_t>(), e->chunk_status.as<int32_t>(), e->pk_aff.as<uint32_t>(),
-                           e->scalars.as<uint64_t>(), e->rpk.as<uint32_t>(), e->pk_status.as<int32_t>(), mode, nullptr, 0u);
-        if (mode == 1u) LB_HIP(hipEventRecord(e->ev_pkst, s3));
       }
     }
     LB_HIP(hipEventRecord(e->ev_pk, s3));
     // signatures: decoded while s1 groups and hashes the messages
     {
       stage_scope sc(e, ST_DECODE, s2);
-      if (row && n <= e->dec_row_max)
-        hipLaunchKernelGGL(k_decompress_sigs_row, dim3((n + 1) / 2), dim3(64), 0, s2, n, b->d_sigs.as<uint8_t>(),
-                           b->has_sizes ? b->d_sig_sizes.as<uint32_t>() : nullptr, e->sig_aff.as<uint32_t>(),
-                           e->sig_aos.as<uint4>(), e->sig_inf.as<uint32_t>(), e->sig_status.as<int32_t>());
-      else
-        hipLaunchKernelGGL(k_decompress_sigs, dim3(nblk(n)), dim3(LB_TPB), 0, s2, n, b->d_sigs.as<uint8_t>(),
-                           b->has_sizes ? b->d_sig_sizes.as<uint32_t>() : nullptr, e->sig_aff.as<uint32_t>(),
-                           e->sig_aos.as<uint4>(), e->sig_inf.as<uint32_t>(), e->sig_status.as<int32_t>());
+      const bool drow = bp.decode == DEC_ROW;  // two signatures per wave, else one per lane
+      hipLaunchKernelGGL(drow ? k_decompress_sigs_row : k_decompress_sigs, dim3(drow ? (n + 1) / 2 : nblk(n)),
+                         dim3(drow ? 64 : LB_TPB), 0, s2, n, b->d_sigs.as<uint8_t>(),
+                         b->has_sizes ? b->d_sig_sizes.as<uint32_t>() : nullptr, e->sig_aff.as<uint32_t>(),
+                         e->sig_aos.as<uint4>(), e->sig_inf.as<uint32_t>(), e->sig_status.as<int32_t>());
       if (sb_par) LB_HIP(hipEventRecord(e->ev_sdec, s2));
-      // (8 lanes per signature also for a slot while the device is otherwise idle ran slower:
-      // 13.5 vs 13.0 ms per slot, profiles/r3_idle_forms_ab.txt)
-      if (row_small)  // one wave per signature (round 6)
-        hipLaunchKernelGGL(k_sig_subgroup_w4, dim3(n), dim3(64), 0, s2, n, e->sig_aff.as<uint32_t>(),
-                           e->sig_inf.as<uint32_t>(), e->sig_status.as<int32_t>());
-      else if (n <= e->subgroup_g8_max)
-        hipLaunchKernelGGL(k_sig_subgroup_g8, dim3((n + 7) / 8), dim3(64), 0, s2, n, e->sig_aff.as<uint32_t>(),
-                           e->sig_inf.as<uint32_t>(), e->sig_status.as<int32_t>());
-      else
-        hipLaunchKernelGGL(k_sig_subgroup, dim3(nblk(n)), dim3(LB_TPB), 0, s2, n, e->sig_aff.as<uint32_t>(),
-                           e->sig_inf.as<uint32_t>(), e->sig_status.as<int32_t>());
+      switch (bp.subgroup) {
+        case SUBGROUP_W4:
+          hipLaunchKernelGGL(k_sig_subgroup_w4, dim3(n), dim3(64), 0, s2, n, e->sig_aff.as<uint32_t>(),
+                             e->sig_inf.as<uint32_t>(), e->sig_status.as<int32_t>());
+          break;
+        case SUBGROUP_G8:
+          hipLaunchKernelGGL(k_sig_subgroup_g8, dim3((n + 7) / 8), dim3(64), 0, s2, n, e->sig_aff.as<uint32_t>(),
+                             e->sig_inf.as<uint32_t>(), e->sig_status.as<int32_t>());
+          break;
+        case SUBGROUP_LANE:
+          hipLaunchKernelGGL(k_sig_subgroup, dim3(nblk(n)), dim3(LB_TPB), 0, s2, n, e->sig_aff.as<uint32_t>(),
+                             e->sig_inf.as<uint32_t>(), e->sig_status.as<int32_t>());
+          break;
+      }
       LB_HIP(hipStreamWaitEvent(s2, pk_split ? e->ev_pkst : e->ev_pk, 0));  // job statuses need the pubkey statuses
       hipLaunchKernelGGL(k_job_status, dim3(nblk(nj)), dim3(LB_TPB), 0, s2, nj, b->d_job_off.as<uint32_t>(),
                          e->sig_status.as<int32_t>(), e->pk_status.as<int32_t>(), e->job_status.as<int32_t>(),
@@ -1025,7 +1007,7 @@ static int32_t run_pipeline(lb_engine* e, lb_batch* b, const uint64_t* scalars, 
     // ---- s1: group the sets by signing root
     {
       stage_scope sc(e, ST_DEDUP, s1);
-      if (n == 1) {
+      if (bp.group == GROUP_ONE_SET) {
         hipLaunchKernelGGL(k_dedup_one, dim3(1), dim3(64), 0, s1, e->rep_of.as<uint32_t>(), e->uid_of.as<uint32_t>(),
                            e->uniq_set.as<uint32_t>(), e->n_u.as<uint32_t>(), e->set_uid.as<uint32_t>(),
                            e->gcnt.as<uint32_t>(), e->gpos.as<uint32_t>(), e->goff.as<uint32_t>(), e->gch.as<uint32_t>(),
@@ -1037,7 +1019,7 @@ static int32_t run_pipeline(lb_engine* e, lb_batch* b, const uint64_t* scalars, 
         LB_HIP(hipMemsetAsync(e->gcnt.p, 0, (size_t)n * 4, s1));
         hipLaunchKernelGGL(k_msg_insert, dim3(nblk(n)), dim3(LB_TPB), 0, s1, n, b->d_msgs.as<uint8_t>(), e->msg_key,
                            cap, e->msg_tab.as<uint32_t>(), e->rep_of.as<uint32_t>());
-        if (e->root_shuffle)
+        if (bp.group == GROUP_DEVICE_ORDER)
           hipLaunchKernelGGL(k_msg_uid, dim3(nblk(cap)), dim3(LB_TPB), 0, s1, cap, e->msg_tab.as<uint32_t>(),
                              e->uid_of.as<uint32_t>(), e->uniq_set.as<uint32_t>(), e->n_u.as<uint32_t>());
         else {
@@ -1067,14 +1049,14 @@ static int32_t run_pipeline(lb_engine* e, lb_batch* b, const uint64_t* scalars, 
           LB_HIP(hipMemcpyAsync(e->n_u.p, &nun, 4, hipMemcpyHostToDevice, s1));
           LB_HIP(hipStreamSynchronize(s1));
         }
-        if (e->root_shuffle)
+        if (bp.group == GROUP_DEVICE_ORDER)
           hipLaunchKernelGGL(k_msg_count, dim3(nblk(n)), dim3(LB_TPB), 0, s1, n, e->rep_of.as<uint32_t>(),
                              e->uid_of.as<uint32_t>(), e->set_uid.as<uint32_t>(), e->gcnt.as<uint32_t>(),
                              e->gpos.as<uint32_t>());
-        hipLaunchKernelGGL(k_msg_scan, dim3(1), dim3(1024), 0, s1, nu, 0u, e->gchunk, e->gcnt.as<uint32_t>(), e->goff.as<uint32_t>(),
+        hipLaunchKernelGGL(k_msg_scan, dim3(1), dim3(1024), 0, s1, nu, 0u, gchunk, e->gcnt.as<uint32_t>(), e->goff.as<uint32_t>(),
                            e->gch.as<uint32_t>(), nullptr, nullptr, nullptr);
-        hipLaunchKernelGGL(k_chunk_fill, dim3(nblk(n + n / e->gchunk + 1)), dim3(LB_TPB), 0, s1, nu,
-                           e->gchunk, e->goff.as<uint32_t>(), e->gch.as<uint32_t>(),
+        hipLaunchKernelGGL(k_chunk_fill, dim3(nblk(n + n / gchunk + 1)), dim3(LB_TPB), 0, s1, nu,
+                           gchunk, e->goff.as<uint32_t>(), e->gch.as<uint32_t>(),
                            e->chunk_beg.as<uint32_t>(), e->chunk_end.as<uint32_t>(), e->chunk_root.as<uint32_t>());
         hipLaunchKernelGGL(k_msg_scatter, dim3(nblk(n)), dim3(LB_TPB), 0, s1, n, e->set_uid.as<uint32_t>(),
                            e->gpos.as<uint32_t>(), e->goff.as<uint32_t>(), e->members.as<uint32_t>());
@@ -1082,7 +1064,7 @@ static int32_t run_pipeline(lb_engine* e, lb_batch* b, const uint64_t* scalars, 
       // distinct-root count to the host: the per-root kernels below are launched over it (a
       // launch over the set count would size their private-segment scratch for n lanes)
       // (one set: one root, known without the round trip)
-      if (n == 1) {
+      if (bp.group == GROUP_ONE_SET) {
         *e->h_nu = 1;
       } else {
         LB_HIP(hipMemcpyAsync(e->h_nu, e->n_u.p, 4, hipMemcpyDeviceToHost, s1));
@@ -1090,65 +1072,67 @@ static int32_t run_pipeline(lb_engine* e, lb_batch* b, const uint64_t* scalars, 
       }
     }
     const uint32_t nuh = *e->h_nu;
-    const bool row_hash = row && nuh <= e->hash_row_max;  // hash_to_G2 on the row engine
     if (nuh == 0 || nuh > n) return LB_ERR_DEVICE;
+    const pipe_hash_plan hp = pipe_plan_hash(e->knobs, bp, nuh, device_alone(e));
     mu = 1;
     while (mu < nuh) mu <<= 1;
     // ---- s1: hash_to_G2 once per distinct root
     {
       stage_scope sc(e, ST_HASH_MAP, s1);
-      if (row_hash)
-        hipLaunchKernelGGL(k_hash_map_row, dim3(2 * nuh), dim3(64), 0, s1, n, nuh,
-                           e->uniq_set.as<uint32_t>(), b->d_msgs.as<uint8_t>(), e->q.as<uint32_t>());
-      else
-        hipLaunchKernelGGL(k_hash_map, dim3(nblk(2 * nuh)), dim3(LB_TPB), 0, s1, n, nuh, e->uniq_set.as<uint32_t>(),
-                           b->d_msgs.as<uint8_t>(), e->q.as<uint32_t>());
+      const bool hrow = hp.map == HMAP_ROW;  // one wave per field element, else one lane
+      hipLaunchKernelGGL(hrow ? k_hash_map_row : k_hash_map, dim3(hrow ? 2 * nuh : nblk(2 * nuh)), dim3(hrow ? 64 : LB_TPB),
+                         0, s1, n, nuh, e->uniq_set.as<uint32_t>(), b->d_msgs.as<uint8_t>(), e->q.as<uint32_t>());
     }
     {
       stage_scope sc(e, ST_HASH_FIN, s1);
-      // 8 lanes per root when the device runs no other batch (a few hundred waves on 1 024 SIMDs:
-      // latency), one lane per root under load (2.5x less work), as for the Miller loops below
-      const bool alone = e->miller_form == 0 && device_alone(e);
-      if (row_hash)
-        hipLaunchKernelGGL(k_hash_finish_row, dim3(nuh), dim3(LBR_NT), 0, s1, n, nu, e->q.as<uint32_t>(),
-                           e->h_aff.as<uint32_t>(), e->hash_row_careful ? 1u : 0u);
-      else if (nuh <= e->hash_g8_max || alone)  // by 8-lane groups for few roots, or whenever the device is otherwise idle
-        hipLaunchKernelGGL(k_hash_finish_g8, dim3((nuh + 7) / 8), dim3(64), 0, s1, n, nu, e->q.as<uint32_t>(),
-                           e->h_aff.as<uint32_t>());
-      else
-      {
-        const uint32_t pn = nblk_inv(nuh) * LB_INV_TPB;  // one park column per launched lane
-        LB_HIP(e->park.ensure((size_t)4 * 72 * 4 * (pn > n ? pn : n)));
-        hipLaunchKernelGGL(k_hash_finish, dim3(nblk_inv(nuh)), dim3(LB_INV_TPB), 0, s1, n, nu, e->q.as<uint32_t>(),
-                           e->h_aff.as<uint32_t>(), e->park.as<uint32_t>(), pn);
+      switch (hp.fin) {
+        case HFIN_ROW:
+          hipLaunchKernelGGL(k_hash_finish_row, dim3(nuh), dim3(LBR_NT), 0, s1, n, nu, e->q.as<uint32_t>(),
+                             e->h_aff.as<uint32_t>(), e->hash_row_careful ? 1u : 0u);
+          break;
+        case HFIN_G8:
+          hipLaunchKernelGGL(k_hash_finish_g8, dim3((nuh + 7) / 8), dim3(64), 0, s1, n, nu, e->q.as<uint32_t>(),
+                             e->h_aff.as<uint32_t>());
+          break;
+        case HFIN_LANE: {
+          const uint32_t pn = nblk_inv(nuh) * LB_INV_TPB;  // one park column per launched lane
+          LB_HIP(e->park.ensure((size_t)4 * 72 * 4 * (pn > n ? pn : n)));
+          hipLaunchKernelGGL(k_hash_finish, dim3(nblk_inv(nuh)), dim3(LB_INV_TPB), 0, s1, n, nu, e->q.as<uint32_t>(),
+                             e->h_aff.as<uint32_t>(), e->park.as<uint32_t>(), pn);
+          break;
+        }
       }
     }
-    // ---- s2: S = sum r_i sig_i by bucket MSM, overlapped with the Miller loops
-    if (sb_par) {
-      LB_HIP(hipStreamWaitEvent(s2, e->ev_sblind, 0));
-      hipLaunchKernelGGL(k_g2_sum_g8, dim3(1), dim3(8 * LB_SUM_G8_GROUPS), 0, s2, n, e->s_terms.as<uint32_t>(),
-                         2 * mj, e->treeS.as<uint32_t>(), 1u, e->set_live.as<uint32_t>());
-      if (e->profiling) hipEventRecord(e->ev1[ST_SIG_MSM], s2);
-    } else if (one_unblinded) {
-      stage_scope sc(e, ST_SIG_MSM, s2);
-      hipLaunchKernelGGL(k_sig_unblinded, dim3(1), dim3(64), 0, s2, e->sig_aff.as<uint32_t>(),
-                         e->set_live.as<uint32_t>(), e->sig_inf.as<uint32_t>(), 2 * mj, e->treeS.as<uint32_t>());
-    } else if (n <= e->small_s_max) {
-      stage_scope sc(e, ST_SIG_MSM, s2);
-      LB_HIP(e->s_terms.ensure((size_t)n * sizeof(g2j)));
-      LB_HIP(e->s_part.ensure((size_t)((n + 63) / 64) * sizeof(g2j)));
-      if (n <= e->small_s_g8_max)
-        hipLaunchKernelGGL(k_sig_blind_g8, dim3((n + 7) / 8), dim3(64), 0, s2, n, e->sig_aff.as<uint32_t>(),
-                           e->scalars.as<uint64_t>(), e->set_live.as<uint32_t>(), e->sig_inf.as<uint32_t>(),
-                           e->s_terms.as<uint32_t>());
-      else
+    // ---- s2: S = sum r_i sig_i, overlapped with the Miller loops
+    switch (bp.ssum) {
+      case SSUM_PAR_W4:  // the terms are on their way on s3 (above)
+        LB_HIP(hipStreamWaitEvent(s2, e->ev_sblind, 0));
+        hipLaunchKernelGGL(k_g2_sum_g8, dim3(1), dim3(8 * LB_SUM_G8_GROUPS), 0, s2, n, e->s_terms.as<uint32_t>(),
+                           2 * mj, e->treeS.as<uint32_t>(), 1u, e->set_live.as<uint32_t>());
+        if (e->profiling) hipEventRecord(e->ev1[ST_SIG_MSM], s2);
+        break;
+      case SSUM_UNBLINDED: {
+        stage_scope sc(e, ST_SIG_MSM, s2);
+        hipLaunchKernelGGL(k_sig_unblinded, dim3(1), dim3(64), 0, s2, e->sig_aff.as<uint32_t>(),
+                           e->set_live.as<uint32_t>(), e->sig_inf.as<uint32_t>(), 2 * mj, e->treeS.as<uint32_t>());
+        break;
+      }
+      case SSUM_TERMS_G8:
+      case SSUM_TERMS_LANE: {
+        stage_scope sc(e, ST_SIG_MSM, s2);
+        LB_HIP(e->s_terms.ensure((size_t)n * sizeof(g2j)));
+        LB_HIP(e->s_part.ensure((size_t)((n + 63) / 64) * sizeof(g2j)));
+        if (bp.ssum == SSUM_TERMS_G8) {  // 8 lanes per set, then one workgroup of 8-lane additions
+          hipLaunchKernelGGL(k_sig_blind_g8, dim3((n + 7) / 8), dim3(64), 0, s2, n, e->sig_aff.as<uint32_t>(),
+                             e->scalars.as<uint64_t>(), e->set_live.as<uint32_t>(), e->sig_inf.as<uint32_t>(),
+                             e->s_terms.as<uint32_t>());
+          hipLaunchKernelGGL(k_g2_sum_g8, dim3(1), dim3(8 * LB_SUM_G8_GROUPS), 0, s2, n, e->s_terms.as<uint32_t>(),
+                             2 * mj, e->treeS.as<uint32_t>(), 1u, nullptr);
+          break;
+        }
         hipLaunchKernelGGL(k_sig_blind, dim3(nblk_inv(n)), dim3(LB_INV_TPB), 0, s2, n, e->sig_aff.as<uint32_t>(),
                            e->scalars.as<uint64_t>(), e->set_live.as<uint32_t>(), e->sig_inf.as<uint32_t>(),
                            e->s_terms.as<uint32_t>());
-      if (n <= e->small_s_g8_max) {  // one workgroup of 8-lane additions
-        hipLaunchKernelGGL(k_g2_sum_g8, dim3(1), dim3(8 * LB_SUM_G8_GROUPS), 0, s2, n, e->s_terms.as<uint32_t>(),
-                           2 * mj, e->treeS.as<uint32_t>(), 1u, nullptr);
-      } else {
         // 64:1 levels, ping-ponging between the two buffers; the last level writes treeS[1]
         uint32_t* bufs[2] = {e->s_terms.as<uint32_t>(), e->s_part.as<uint32_t>()};
         uint32_t m = n;
@@ -1160,25 +1144,28 @@ static int32_t run_pipeline(lb_engine* e, lb_batch* b, const uint64_t* scalars, 
           cur ^= 1;
         }
         hipLaunchKernelGGL(k_g2_sum64, dim3(1), dim3(64), 0, s2, m, bufs[cur], 2 * mj, e->treeS.as<uint32_t>(), 1u);
+        break;
       }
-    } else {
-      stage_scope sc(e, ST_SIG_MSM, s2);
-      LB_HIP(hipMemsetAsync(e->bcnt.p, 0, (size_t)LB_MSM_NB * 4, s2));
-      LB_HIP(hipMemsetAsync(e->bcursor.p, 0, (size_t)LB_MSM_NB * 4, s2));
-      hipLaunchKernelGGL(k_msm_count, dim3(nblk(n)), dim3(LB_TPB), 0, s2, n, e->scalars.as<uint64_t>(),
-                         e->set_live.as<uint32_t>(), e->sig_inf.as<uint32_t>(), e->bcnt.as<uint32_t>());
-      hipLaunchKernelGGL(k_msg_scan, dim3(1), dim3(1024), 0, s2, nullptr, (uint32_t)LB_MSM_NB, (uint32_t)LB_MSM_CHUNK,
-                         e->bcnt.as<uint32_t>(),
-                         e->boff.as<uint32_t>(), e->bch.as<uint32_t>(), e->bchunk_beg.as<uint32_t>(),
-                         e->bchunk_end.as<uint32_t>(), nullptr);
-      hipLaunchKernelGGL(k_msm_scatter, dim3(nblk(n)), dim3(LB_TPB), 0, s2, n, e->scalars.as<uint64_t>(),
-                         e->set_live.as<uint32_t>(), e->sig_inf.as<uint32_t>(), e->boff.as<uint32_t>(),
-                         e->bcursor.as<uint32_t>(), e->bmembers.as<uint32_t>());
-      hipLaunchKernelGGL(k_msm_chunks, dim3(nblk(bcap)), dim3(LB_TPB), 0, s2, e->bch.as<uint32_t>(),
-                         e->bchunk_beg.as<uint32_t>(), e->bchunk_end.as<uint32_t>(), e->bmembers.as<uint32_t>(),
-                         e->sig_aos.as<uint4>(), bcap, e->bacc.as<uint32_t>(), (uint32_t)LB_MSM_NB);
-      LB_HIP(msm_reduce(e, s2, bcap, LB_MSM_NB, 1u, LB_MSM_W, e->treeS.as<uint32_t>(), 2 * mj, 1u,
-                        (uint64_t)2 * LB_MSM_W * n, LB_MSM_CHUNK));
+      case SSUM_BUCKET_MSM: {
+        stage_scope sc(e, ST_SIG_MSM, s2);
+        LB_HIP(hipMemsetAsync(e->bcnt.p, 0, (size_t)LB_MSM_NB * 4, s2));
+        LB_HIP(hipMemsetAsync(e->bcursor.p, 0, (size_t)LB_MSM_NB * 4, s2));
+        hipLaunchKernelGGL(k_msm_count, dim3(nblk(n)), dim3(LB_TPB), 0, s2, n, e->scalars.as<uint64_t>(),
+                           e->set_live.as<uint32_t>(), e->sig_inf.as<uint32_t>(), e->bcnt.as<uint32_t>());
+        hipLaunchKernelGGL(k_msg_scan, dim3(1), dim3(1024), 0, s2, nullptr, (uint32_t)LB_MSM_NB, (uint32_t)LB_MSM_CHUNK,
+                           e->bcnt.as<uint32_t>(),
+                           e->boff.as<uint32_t>(), e->bch.as<uint32_t>(), e->bchunk_beg.as<uint32_t>(),
+                           e->bchunk_end.as<uint32_t>(), nullptr);
+        hipLaunchKernelGGL(k_msm_scatter, dim3(nblk(n)), dim3(LB_TPB), 0, s2, n, e->scalars.as<uint64_t>(),
+                           e->set_live.as<uint32_t>(), e->sig_inf.as<uint32_t>(), e->boff.as<uint32_t>(),
+                           e->bcursor.as<uint32_t>(), e->bmembers.as<uint32_t>());
+        hipLaunchKernelGGL(k_msm_chunks, dim3(nblk(bcap)), dim3(LB_TPB), 0, s2, e->bch.as<uint32_t>(),
+                           e->bchunk_beg.as<uint32_t>(), e->bchunk_end.as<uint32_t>(), e->bmembers.as<uint32_t>(),
+                           e->sig_aos.as<uint4>(), bcap, e->bacc.as<uint32_t>(), (uint32_t)LB_MSM_NB);
+        LB_HIP(msm_reduce(e, s2, bcap, LB_MSM_NB, 1u, LB_MSM_W, e->treeS.as<uint32_t>(), 2 * mj, 1u,
+                          (uint64_t)2 * LB_MSM_W * n, LB_MSM_CHUNK));
+        break;
+      }
     }
     // ---- s1: per-root sums of r_i PK_i and the Miller loops, after the signature decode
     LB_HIP(hipStreamWaitEvent(s1, e->ev_dec, 0));
@@ -1199,10 +1186,8 @@ static int32_t run_pipeline(lb_engine* e, lb_batch* b, const uint64_t* scalars, 
   // ---- s2: ML(-G1, S_root)
   {
     stage_scope sc(e, ST_ML_S, s2);
-    if (row)
-      hipLaunchKernelGGL(k_ml_S_row, dim3(1), dim3(LBR_NT), 0, s2, mj, e->treeS.as<uint32_t>(), e->fS.as<uint32_t>());
-    else
-      hipLaunchKernelGGL(k_ml_S, dim3(1), dim3(64), 0, s2, mj, e->treeS.as<uint32_t>(), e->fS.as<uint32_t>());
+    hipLaunchKernelGGL(bp.fe == FE_ROW ? k_ml_S_row : k_ml_S, dim3(1), dim3(bp.fe == FE_ROW ? LBR_NT : 64), 0, s2, mj,
+                       e->treeS.as<uint32_t>(), e->fS.as<uint32_t>());
   }
   LB_HIP(hipEventRecord(e->ev_s, s2));
   LB_HIP(hipStreamWaitEvent(s1, e->ev_s, 0));  // join
@@ -1278,7 +1263,8 @@ static int32_t search_round(lb_engine* e, const search_ctx& x, const launch_set&
   {
     stage_scope sc(e, ST_FALLBACK, s1);
     const smsm_args ma{U(SX_MPRE), U(SX_MLO), U(SX_MMODE), U(SX_MWA), U(SX_MWB)};
-    if (cm && T && (rs_path || T <= e->search_small_max)) {
+    const pipe_search_plan sp = pipe_plan_search_round(e->knobs, cm, T, rs_path, device_alone(e));
+    if (sp.sums == SRCH_TERMS) {
       // small or root-level round: per-position terms + per-instance segmented sums (no bucket MSM)
       std::vector<uint32_t> blo, bhi, bo;
       blocks64(tab.col[SX_MPRE].data(), cm, blo, bhi, bo);
@@ -1288,25 +1274,29 @@ static int32_t search_round(lb_engine* e, const search_ctx& x, const launch_set&
       LB_HIP(sx_up(e, SX_BO, bo, s1));
       LB_HIP(e->s_terms.ensure((size_t)T * sizeof(g2j)));
       LB_HIP(e->s_part.ensure((size_t)(nbk ? nbk : 1) * sizeof(g2j)));
-      if (rs_path)
-        hipLaunchKernelGGL(k_rsm_terms, dim3(nblk(T)), dim3(LB_TPB), 0, s1, T, cm, ma, e->s_root.as<uint32_t>(), x.nu,
-                           e->s_terms.as<uint32_t>());
-      else if (e->smsm_form == 1 ||
-               (e->smsm_form == 0 && !device_alone(e)))
-        hipLaunchKernelGGL(k_smsm_terms_lane, dim3(nblk_inv(T)), dim3(LB_INV_TPB), 0, s1, T, cm, ma,
-                           e->members.as<uint32_t>(), e->set_uid.as<uint32_t>(), e->scalars.as<uint64_t>(),
-                           e->set_live.as<uint32_t>(), e->sig_inf.as<uint32_t>(), e->sig_aff.as<uint32_t>(), n,
-                           e->s_terms.as<uint32_t>());
-      else
-        hipLaunchKernelGGL(k_smsm_terms_g8, dim3((T + 7) / 8), dim3(64), 0, s1, T, cm, ma, e->members.as<uint32_t>(),
-                           e->set_uid.as<uint32_t>(), e->scalars.as<uint64_t>(), e->set_live.as<uint32_t>(),
-                           e->sig_inf.as<uint32_t>(), e->sig_aff.as<uint32_t>(), n, e->s_terms.as<uint32_t>());
+      switch (sp.terms) {
+        case STERMS_ROOT_SUMS:
+          hipLaunchKernelGGL(k_rsm_terms, dim3(nblk(T)), dim3(LB_TPB), 0, s1, T, cm, ma, e->s_root.as<uint32_t>(), x.nu,
+                             e->s_terms.as<uint32_t>());
+          break;
+        case STERMS_LANE:
+          hipLaunchKernelGGL(k_smsm_terms_lane, dim3(nblk_inv(T)), dim3(LB_INV_TPB), 0, s1, T, cm, ma,
+                             e->members.as<uint32_t>(), e->set_uid.as<uint32_t>(), e->scalars.as<uint64_t>(),
+                             e->set_live.as<uint32_t>(), e->sig_inf.as<uint32_t>(), e->sig_aff.as<uint32_t>(), n,
+                             e->s_terms.as<uint32_t>());
+          break;
+        case STERMS_G8:
+          hipLaunchKernelGGL(k_smsm_terms_g8, dim3((T + 7) / 8), dim3(64), 0, s1, T, cm, ma, e->members.as<uint32_t>(),
+                             e->set_uid.as<uint32_t>(), e->scalars.as<uint64_t>(), e->set_live.as<uint32_t>(),
+                             e->sig_inf.as<uint32_t>(), e->sig_aff.as<uint32_t>(), n, e->s_terms.as<uint32_t>());
+          break;
+      }
       if (nbk)
         hipLaunchKernelGGL(k_seg_sum64, dim3(nbk), dim3(64), 0, s1, U(SX_BLO), U(SX_BHI), T, e->s_terms.as<uint32_t>(),
                            nbk, e->s_part.as<uint32_t>(), nullptr);
       hipLaunchKernelGGL(k_seg_final, dim3(cm), dim3(64), 0, s1, U(SX_BO), e->s_part.as<uint32_t>(), nbk ? nbk : 1u,
                          U(SX_S), cm);
-    } else if (cm) {
+    } else if (sp.sums == SRCH_BUCKET_MSM) {
       LB_HIP(e->bcnt.ensure((size_t)nb * 4));
       LB_HIP(e->bcursor.ensure((size_t)nb * 4));
       LB_HIP(e->boff.ensure((size_t)(nb + 1) * 4));
@@ -1423,8 +1413,9 @@ static int32_t search_invalid(lb_engine* e, lb_batch* b, uint32_t mu, int32_t* o
   LB_HIP(hipMemcpyAsync(root.y.data(), e->y_root.p, 576, hipMemcpyDeviceToHost, e->stream));
   LB_HIP(hipStreamSynchronize(e->stream));
   // the first round's form for large batches (see lb_engine::search_blk)
-  const bool r1_plain = e->search_blk && x.nu > 1 && n > e->search_small_max;
-  if (!r1_plain && e->search_rootsum && x.nu > 1 && n > e->search_small_max) {
+  const pipe_search_start ss = pipe_plan_search_start(e->knobs, e->search_blk, e->search_rootsum, n, x.nu);
+  const bool r1_plain = ss.r1_plain;
+  if (ss.root_sums) {
     const int32_t st = search_root_sums(e, x);
     if (st != LB_OK) return st;
     x.rs = true;
@@ -1441,7 +1432,7 @@ static int32_t search_invalid(lb_engine* e, lb_batch* b, uint32_t mu, int32_t* o
       std::vector<int32_t> verdict, tout;
       std::vector<uint32_t> ydir;
       const auto t0 = std::chrono::steady_clock::now();
-      const search_tab tab = search_tables(x, ls.Fs, ls.D, ls.tests, ls.n_fresh, e->search_small_max);
+      const search_tab tab = search_tables(x, ls.Fs, ls.D, ls.tests, ls.n_fresh, e->knobs.search_small_max);
       const int32_t st = search_round(e, x, ls, tab, verdict, ydir, tout);
       if (st != LB_OK) return st;
       if (trace)
@@ -1482,7 +1473,7 @@ static int32_t verify_locked(lb_engine* e, lb_batch* b, const uint64_t* scalars,
   {
     stage_scope sc(e, ST_ROOT, e->stream);
     LB_HIP(e->y_root.ensure(576));
-    hipLaunchKernelGGL((e->alone && e->row_fe) ? k_root_check_row : k_root_check, dim3(1), dim3((e->alone && e->row_fe) ? LBR_NT : 64), 0, e->stream, mu, e->treeP.as<uint32_t>(),
+    hipLaunchKernelGGL(e->plan.fe == FE_ROW ? k_root_check_row : k_root_check, dim3(1), dim3(e->plan.fe == FE_ROW ? LBR_NT : 64), 0, e->stream, mu, e->treeP.as<uint32_t>(),
                        e->fS.as<uint32_t>(), e->verdict.as<int32_t>(), e->y_root.as<uint32_t>());
   }
   LB_HIP(hipGetLastError());
@@ -1527,7 +1518,7 @@ extern "C" int32_t lb_batch_partial(lb_engine* e, lb_batch* b, const uint64_t* s
   LB_HIP(e->parts.ensure(576));
   {
     stage_scope sc(e, ST_ROOT, e->stream);
-    hipLaunchKernelGGL((e->alone && e->row_fe) ? k_root_partial_row : k_root_partial, dim3(1), dim3((e->alone && e->row_fe) ? LBR_NT : 64), 0, e->stream, mu, e->treeP.as<uint32_t>(),
+    hipLaunchKernelGGL(e->plan.fe == FE_ROW ? k_root_partial_row : k_root_partial, dim3(1), dim3(e->plan.fe == FE_ROW ? LBR_NT : 64), 0, e->stream, mu, e->treeP.as<uint32_t>(),
                        e->fS.as<uint32_t>(), e->parts.as<uint8_t>());
   }
   LB_HIP(hipGetLastError());
@@ -1554,7 +1545,7 @@ extern "C" int32_t lb_batch_search_after_partial(lb_engine* e, lb_batch* b, int3
   LB_HIP(e->verdict.ensure(4));
   LB_HIP(e->y_root.ensure(576));
   // this shard's own root check: a passing shard is done, a failing one searches from it
-  hipLaunchKernelGGL((e->alone && e->row_fe) ? k_root_check_row : k_root_check, dim3(1), dim3((e->alone && e->row_fe) ? LBR_NT : 64), 0, e->stream, mu, e->treeP.as<uint32_t>(), e->fS.as<uint32_t>(),
+  hipLaunchKernelGGL(e->plan.fe == FE_ROW ? k_root_check_row : k_root_check, dim3(1), dim3(e->plan.fe == FE_ROW ? LBR_NT : 64), 0, e->stream, mu, e->treeP.as<uint32_t>(), e->fS.as<uint32_t>(),
                      e->verdict.as<int32_t>(), e->y_root.as<uint32_t>());
   LB_HIP(hipGetLastError());
   std::vector<int32_t> jst(nj);
@@ -1580,7 +1571,7 @@ extern "C" int32_t lb_fp12_product_is_one(lb_engine* e, const uint8_t* partials5
   LB_HIP(e->parts.ensure((size_t)(n ? n : 1) * 576));
   LB_HIP(e->ok.ensure(4));
   if (n) LB_HIP(hipMemcpyAsync(e->parts.p, partials576, (size_t)n * 576, hipMemcpyHostToDevice, e->stream));
-  const bool prow = e->row_fe && device_alone(e);
+  const bool prow = pipe_fe_form(e->knobs, device_alone(e)) == FE_ROW;
   hipLaunchKernelGGL(prow ? k_partials_check_row : k_partials_check, dim3(1), dim3(prow ? LBR_NT : 64), 0, e->stream, n, e->parts.as<uint8_t>(),
                      e->ok.as<int32_t>());
   LB_HIP(hipGetLastError());

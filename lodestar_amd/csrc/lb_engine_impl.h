@@ -1,6 +1,6 @@
-// What the two host units of the library share (lb_engine.hip: the BLS pipeline, the device side
-// and the loop of the invalid-set search, whose planning is the device-free lb_search_plan.h, and
-// the small helper calls; lb_kzg_host.hip: the KZG calls): the device buffer, the engine
+// What the two host units of the library share (lb_engine.hip: the BLS pipeline, whose choice of
+// kernel forms is the device-free lb_pipeline_plan.h, the device side and the loop of the
+// invalid-set search, whose planning is the device-free lb_search_plan.h, and the small helper calls; lb_kzg_host.hip: the KZG calls): the device buffer, the engine
 // and its KZG state, the HIP error macro and the generic "inputs up, one launch, outputs back"
 // runner.  Host-only and not part of the public ABI (include/lodestar_bls.h).  Nothing here sits
 // in an anonymous namespace: lb_engine must be one type in both units.
@@ -13,6 +13,7 @@
 
 #include "lb_fr.h"
 #include "lb_kernels.h"
+#include "lb_pipeline_plan.h"  // pipe_knobs and the plans (device-free)
 
 struct dbuf {
   void* p = nullptr;
@@ -121,13 +122,11 @@ struct lb_engine {
   // message grouping (k_msg_*, k_gsum_*)
   dbuf msg_tab, rep_of, uid_of, uniq_set, n_u, set_uid, gcnt, gpos, goff, gch, chunk_beg, chunk_end, members,
       set_live, gacc, gp_aff, gp_inf, chunk_root;
-  // this pipeline run's forms: `alone` (device_alone at its start) picks the latency forms -- the
-  // row engine (row_fe: LB_ROW_FE=0 disables it) and the per-root sums' chunks combined by a
-  // segmented shuffle tree in one launch (k_gsum_wave, chunks of LB_GROUP_CHUNK_WAVE); under load
-  // k_gsum_chunks over LB_GROUP_CHUNK members, the chunk sums added serially per root
-  bool alone = false, row_fe = true;
-  int alone_force = -1;  // LB_ALONE=1 / 0 pins device_alone() (tests: the latency forms must run), -1 by load
-  uint32_t gchunk = LB_GROUP_CHUNK;
+  // which kernel form each stage takes (lb_pipeline_plan.h): the thresholds and pins, read from the
+  // LB_* environment at creation, and the last pipeline run's per-batch plan (per_root_chain, the
+  // root check / partial and lb_batch_search_after_partial's root check follow it)
+  pipe_knobs knobs;
+  pipe_batch_plan plan;
   // bucket MSM for sum r_i sig_i (k_msm_*)
   dbuf sig_aos, bcnt, bcursor, boff, bch, bchunk_beg, bchunk_end, bmembers, bacc, bsum, wsum;
   // parked lone-lane state: k_hash_finish's points (4 x 72 words per launched lane), k_miller_lane's T
@@ -136,51 +135,18 @@ struct lb_engine {
   // this engine's workspace, for lb_batch_search_after_partial; any other pipeline run clears it
   uint64_t partial_serial = 0;
   uint32_t partial_mu = 0;
-  // bucket sums and the bucket reduction by 8-lane groups (k_msm_buckets_g8, k_msm_window_g8,
-  // k_msm_horner_g8); LB_MSM_G8=0: the lone-lane kernels (k_msm_buckets, k_msm_reduce)
-  bool msm_g8 = true;
   // invalid-set search (search_invalid): node descriptors and per-node results
   dbuf sx[32];   // search round buffers (lb_search_plan.h SX_*)
   dbuf pk_aff;  // affine aggregate pubkey per set (single-set checks of the search)
   dbuf y_root;  // FE value of the root check (the search starts from it)
   uint64_t msg_key = 0;  // keyed probe hash (CSPRNG)
-  // batches with at most this many distinct roots run their Miller loops one wave per root
-  // (k_miller_wave); larger ones one lane per root (k_miller_lane) while other batches are in
-  // flight on the device, else 8 lanes per root (k_miller_g8).  LB_MILLER_WAVE_MAX;
-  // LB_MILLER_FORM = lane | g8 pins the large-batch form (default: by device load).
-  uint32_t miller_wave_max = 2048;
-  // ... and up to this many roots (tree nodes of a level) on the row engine (lb_row.h: one 16-wave
-  // workgroup per item, the products split over 16-lane rows; latency).  LB_ROW_MAX.
-  uint32_t row_max = 256;
-  int miller_form = 0;  // 0 by load, 1 lane, 2 g8
-  // one-lane Miller loops with f and a temporary in LDS (two waves per CU) up to this many roots,
-  // f alone in LDS (three waves per CU) above: LB_MILLER_LDS3_MAX (lb_kernels.h k_miller_lane)
-  uint32_t miller_lds3_max = 32768;
-  // ... and hash_to_G2's cofactor clearing with 8 lanes per root (k_hash_finish_g8).  LB_HASH_G8_MAX.
-  uint32_t hash_g8_max = 2048;
-  // ... and with a workgroup per root on the row engine while the device is alone.  LB_HASH_ROW_MAX.
-  uint32_t hash_row_max = 256;
-  bool hash_row_careful = false;  // LB_HASH_ROW_CAREFUL=1: the exceptional-case path always (tests)
-  // ... and the signature decode's square roots on rows up to this many sets.  LB_DEC_ROW_MAX.
-  uint32_t dec_row_max = 4096;
-  // ... and the signatures' subgroup check with 8 lanes per set (k_sig_subgroup_g8).  LB_SUBGROUP_G8_MAX.
-  uint32_t subgroup_g8_max = 4096;
-  // ... and S = sum r_i sig_i by per-set 8-lane scalar multiplications + trees instead of the
-  // bucket MSM (k_sig_blind_g8).  LB_SMALL_S_MAX.
-  uint32_t small_s_max = 32768;
-  uint32_t small_s_g8_max = 2048;  // ... with 8 lanes per set up to here, one lane above (LB_SMALL_S_G8_MAX)
-  // search rounds whose weighted sums cover at most this many positions skip the bucket MSM
-  // (k_smsm_terms_g8 + segmented sums).  LB_SEARCH_SMALL_MAX.
-  uint32_t search_small_max = 32768;
+  bool hash_row_careful = false;  // LB_HASH_ROW_CAREFUL=1: k_hash_finish_row's exceptional-case path always (tests)
   // one launch pair per search round (look-ahead tests not skipped for passing checks)
   bool search_merge = true;
   dbuf s_terms, s_part;
   // per-root signature sums for the search's root-level instances (LB_SEARCH_ROOTSUM)
   dbuf s_root, rs_idx, s_set;
   bool search_rootsum = true;
-  // the small rounds' per-position terms: 0 by load (8 lanes per position while the device runs no
-  // other batch, one lane under load), 1 one lane, 2 eight lanes (LB_SMSM_FORM=lane / g8)
-  int smsm_form = 0;
   // members per lane in the search rounds' bucket MSM chunks (k_msm_chunks).  Its buckets hold ~8
   // members (109 instances x 1 024 buckets over ~0.9 M entries), so long chunks leave most lanes
   // of a wave idle behind the longest one; LB_SEARCH_CHUNK

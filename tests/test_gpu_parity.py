@@ -755,11 +755,16 @@ def test_per_root_kernel_forms_agree(monkeypatch, name):
     search's weighted range sums (bucket MSM / per-position 8-lane terms + segmented sums).
     Engines created with the thresholds at 0 and at 2^31 run the same batch (same blinding
     scalars) through each form; verdicts must match the planted expectation, and the root partials
-    (576-byte Fp12 products before the final exponentiation) must be byte-identical."""
+    (576-byte Fp12 products before the final exponentiation) must be byte-identical.
+    LB_ALONE=0 pins the engine's "device alone" test: an engine that finds the device to itself
+    sends c2 (131 sets, at most 256 roots) to the row forms in every one of the six settings, before
+    it looks at any of these thresholds (tests/test_pipeline_plan_cpu.py
+    test_recipes_of_test_gpu_parity_per_root_forms holds the forms each setting selects)."""
     from lodestar_amd.engine import Engine
     from lodestar_amd import workloads as W
     outs = []
     big = str(1 << 31)
+    monkeypatch.setenv("LB_ALONE", "0")
     # (all one-lane / MSM forms), (the same with 8-lane Miller loops), (many-lane forms, one-lane
     # S terms), (many-lane forms, 8-lane S terms)
     # + the bucket MSM's lone-lane bucket sums and reduction (LB_MSM_G8=0) against the 8-lane ones,
