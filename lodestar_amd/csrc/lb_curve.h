@@ -306,6 +306,15 @@ LB_NI jac<F> jac_mul_u256(aff<F> p, const uint32_t* k) {
   }
   return acc;
 }
+// [r] P == O for an affine G1 point (r = the BLS12-381 subgroup order): the plain subgroup check of
+// G1 points that come from the wire, one-time per point (PublicKey.keyValidate for the resident
+// pubkey table; KZG commitments, proofs and setup points, where c-kzg's validate_kzg_g1 rejects
+// the same points)
+LB_HD bool g1_in_subgroup_r(const aff<fp>& a) {
+  const uint32_t rr[8] = {0x00000001u, 0xffffffffu, 0xfffe5bfeu, 0x53bda402u,
+                          0x09a1d805u, 0x3339d808u, 0x299d7d48u, 0x73eda753u};
+  return jac_is_inf(jac_mul_u256(a, rr));
+}
 
 // [|x|]P for the curve parameter |x| = 0xd201000000010000 (wave-uniform bits)
 template <class F, bool kInl = false>

@@ -19,6 +19,7 @@
 #include "lb_serial.h"
 #include "lb_h2c.h"
 #include "lb_pairing.h"
+#include "lb_kernel_index.h"  // seg_is_head, seg_next_head, msm_for_digits
 
 #define LB_TPB 64  // one wave per workgroup: spreads few-thousand-item batches over all 256 CUs
 #ifndef LB_MINW
@@ -773,18 +774,41 @@ __global__ void __launch_bounds__(LBR_NT) k_hash_finish_row(uint32_t n, const ui
 // sum is then the sum of its segment heads: its first chunk and every later chunk at a wave
 // boundary (c % 64 == 0), at most 1 + ceil(chunks / 64) of them (k_pk_blind).  The same for the
 // per-root sums of a batch alone (k_gsum_wave).  (north_star: tree reduction for G1 aggregation.)
-__device__ __forceinline__ g1j g1j_shfl_down(const g1j& a, unsigned d) {
+__device__ __forceinline__ g1j jac_shfl_down(const g1j& a, unsigned d) {
   return g1j{fp_shfl_down(a.x, d), fp_shfl_down(a.y, d), fp_shfl_down(a.z, d)};
+}
+__device__ __forceinline__ g2j jac_shfl_down(const g2j& a, unsigned d) {
+  return g2j{fp2{fp_shfl_down(a.x.c0, d), fp_shfl_down(a.x.c1, d)},
+             fp2{fp_shfl_down(a.y.c0, d), fp_shfl_down(a.y.c1, d)},
+             fp2{fp_shfl_down(a.z.c0, d), fp_shfl_down(a.z.c1, d)}};
 }
 // v: this lane's partial; rel: lanes of its segment before it; left: lanes of its segment from it on
 template <class F>
 __device__ __forceinline__ jac<F> wave_seg_sum(jac<F> v, uint32_t rel, uint32_t left) {
   LB_UNROLL for (uint32_t s = 1; s < 64; s <<= 1) {
-    const jac<F> o = jac_as<F>(g1j_shfl_down(jac_as<fp>(v), s));
+    const jac<F> o = jac_as<F>(jac_shfl_down(jac_as<fp>(v), s));
     if ((rel & (2 * s - 1)) == 0 && s < left) v = jac_add_i<F, true>(v, o);
   }
   return v;
 }
+// The whole wave as one segment: six shuffle-down levels leave the sum of the 64 lanes' v in lane 0
+// (lane = the thread's lane of its wave; the other lanes end with partial sums).  Rolled: the body
+// is an inlined addition.  The KZG checks (lb_kzg.h) sum through it; k_g2_sum64, k_seg_sum64,
+// k_seg_final, k_msm_reduce and k_g1_sum64 keep the same loop in their own words, because through
+// any wrapper, even a lambda, their registers are allocated in another order.
+template <class F>
+__device__ __forceinline__ jac<F> wave_sum64(jac<F> v, uint32_t lane) {
+  for (int l = 5; l >= 0; l--) {
+    const unsigned d = 1u << l;
+    const jac<F> o = jac_shfl_down(v, d);
+    if (lane < d) v = jac_add_i(v, o);
+  }
+  return v;
+}
+// The readers of the segment sums (k_pk_blind, k_pk_out96, k_gsum_final) find the heads by chunk
+// index alone (lb_kernel_index.h seg_is_head, seg_next_head).  That is right only while chunk c sits
+// on lane c % 64 of its wave, i.e. while a workgroup of the chunk kernels is exactly one wave:
+static_assert(LB_TPB == LB_WAVE, "segment heads by chunk index: wave_segments breaks at threadIdx.x & 63, the readers at c % 64");
 // segments of the wave from per-lane "starts a segment" flags (inactive lanes: pass true)
 __device__ __forceinline__ void wave_segments(bool starts, uint32_t& rel, uint32_t& left) {
   const uint64_t heads = __ballot(starts) | 1ull;  // the wave's first lane always starts one
@@ -899,10 +923,8 @@ __global__ void __launch_bounds__(LB_TPB, LB_MINW) k_table_fill(uint32_t n, cons
   if (st == LB_OK && validate) {
     if (inf) {
       st = LB_PK_IS_INFINITY;
-    } else {
-      const uint32_t rr[8] = {0x00000001u, 0xffffffffu, 0xfffe5bfeu, 0x53bda402u,
-                              0x09a1d805u, 0x3339d808u, 0x299d7d48u, 0x73eda753u};
-      if (!jac_is_inf(jac_mul_u256(a, rr))) st = LB_POINT_NOT_IN_GROUP;
+    } else if (!g1_in_subgroup_r(a)) {
+      st = LB_POINT_NOT_IN_GROUP;
     }
   }
   if (st != LB_OK) {
@@ -917,6 +939,12 @@ __global__ void __launch_bounds__(LB_TPB, LB_MINW) k_table_fill(uint32_t n, cons
 }
 #endif  // LB_KG
 
+// The GLV table of an affine G1 point for jac_mul_glv_i (r = lo + hi lambda): t2 = [lambda] P =
+// (beta x, y) and t3 = P + t2 = (beta^2 x, -y), no inversion needed
+__device__ __forceinline__ void g1_glv_table(const g1a& p, g1a& t2, g1a& t3) {
+  t2 = g1a{fp_mul(p.x, fp_load(LB_GLV_BETA)), p.y};
+  t3 = g1a{fp_mul(p.x, fp_load(LB_GLV_BETA2)), fp_neg(p.y)};
+}
 // pk_status: LB_OK / pubkey decode error / LB_EMPTY_AGGREGATE_ARRAY / LB_PK_IS_INFINITY
 // r * PK (Jacobian) for the per-root sums; the affine aggregate PK itself -> pk_aff.  block of LB_INV_TPB threads (fp_inv_block)
 #if LB_KG(4)
@@ -945,8 +973,8 @@ __global__ void __launch_bounds__(LB_INV_TPB, LB_MINW_G1) k_pk_blind(uint32_t n,
       rj = g1j{pk.x, pk.y, fp_one()};
     } else if (st == LB_OK) {
       const g1a pk = soa_ld<g1a>(pk_aff, n, i);
-      const g1a t2{fp_mul(pk.x, fp_load(LB_GLV_BETA)), pk.y};
-      const g1a t3{fp_mul(pk.x, fp_load(LB_GLV_BETA2)), fp_neg(pk.y)};
+      g1a t2, t3;
+      g1_glv_table(pk, t2, t3);
       rj = jac_as<fp>(jac_mul_glv_i<fpi, true>(aff_as<fpi>(pk), aff_as<fpi>(t2), aff_as<fpi>(t3), scalars[i]));
     }
     aos_st(rpk, i, rj);
@@ -956,11 +984,10 @@ __global__ void __launch_bounds__(LB_INV_TPB, LB_MINW_G1) k_pk_blind(uint32_t n,
     uint32_t c0 = set_chunk_off[i], c1 = set_chunk_off[i + 1];
     st = (c0 == c1) ? LB_EMPTY_AGGREGATE_ARRAY : LB_OK;
     g1j acc = jac_infinity<fp>();
-    // every chunk's status, the segment heads' sums (k_pk_chunks[_idx]: the set's first chunk and
-    // its chunks at wave boundaries)
+    // every chunk's status, the segment heads' sums (k_pk_chunks[_idx])
     for (uint32_t c = c0; c < c1 && st == LB_OK; c++) {
       st = chunk_status[c];
-      if (st == LB_OK && (c == c0 || (c & (LB_TPB - 1)) == 0))
+      if (st == LB_OK && seg_is_head(c, c0))
         acc = (c == c0) ? soa_ld<g1j>(chunk_acc, nc, c) : jac_add_i<fp, true>(acc, soa_ld<g1j>(chunk_acc, nc, c));
     }
     if (st == LB_OK && jac_is_inf(acc)) st = LB_PK_IS_INFINITY;
@@ -988,9 +1015,8 @@ __global__ void __launch_bounds__(LB_INV_TPB, LB_MINW_G1) k_pk_blind(uint32_t n,
     return;
   }
   if (ok) {
-    // r * PK with r = lo + hi * lambda: t2 = [lambda]PK = (beta x, y), t3 = PK + t2 = (beta^2 x, -y)
-    const g1a t2{fp_mul(pk.x, fp_load(LB_GLV_BETA)), pk.y};
-    const g1a t3{fp_mul(pk.x, fp_load(LB_GLV_BETA2)), fp_neg(pk.y)};
+    g1a t2, t3;
+    g1_glv_table(pk, t2, t3);
     rj = jac_as<fp>(jac_mul_glv_i<fpi, true>(aff_as<fpi>(pk), aff_as<fpi>(t2), aff_as<fpi>(t3), scalars[i]));
   } else {
     rj = jac_infinity<fp>();
@@ -1564,9 +1590,7 @@ __global__ void __launch_bounds__(LB_TPB) k_msg_scatter(uint32_t n, const uint32
 // sum_d d B_d per window and combines the windows.  About 8 mixed additions per set instead of
 // the 32 doublings + 32 additions of a per-set r*sig.  The invalid-set search reuses the same
 // machinery over ranges of sets (k_rmsm_*) after a failing root check.
-#define LB_MSM_C 8
-#define LB_MSM_W 4
-#define LB_MSM_B (1 << LB_MSM_C)
+#define LB_MSM_W 4  // (LB_MSM_C, LB_MSM_B and the digit split msm_for_digits: lb_kernel_index.h)
 #define LB_MSM_NB (LB_MSM_W * LB_MSM_B)  // bucket ids w * 256 + d (d = 0 unused)
 // (set_live == nullptr: every decoded set; the caller masks the terms later, k_g2_sum_g8)
 __device__ __forceinline__ bool msm_live(uint32_t i, const uint32_t* set_live, const uint32_t* sig_inf) {
@@ -1579,13 +1603,8 @@ __global__ void __launch_bounds__(LB_TPB) k_msm_count(uint32_t n, const uint64_t
   const uint32_t i = lb_tid();
   if (i >= n || !msm_live(i, set_live, sig_inf)) return;
   const uint64_t wd = scalars[i];
-  LB_UNROLL for (int h = 0; h < 2; h++) {
-    const uint32_t k = (uint32_t)(wd >> (32 * h));
-    LB_UNROLL for (int w = 0; w < LB_MSM_W; w++) {
-      const uint32_t d = (k >> (LB_MSM_C * w)) & (LB_MSM_B - 1);
-      if (d) atomicAdd(&cnt[w * LB_MSM_B + d], 1u);
-    }
-  }
+  LB_UNROLL for (int h = 0; h < 2; h++)
+    msm_for_digits<LB_MSM_W>((uint32_t)(wd >> (32 * h)), [=](int w, uint32_t d) { atomicAdd(&cnt[w * LB_MSM_B + d], 1u); });
 }
 #endif  // LB_KG
 #if LB_KG(6)
@@ -1597,16 +1616,11 @@ __global__ void __launch_bounds__(LB_TPB) k_msm_scatter(uint32_t n, const uint64
   const uint32_t i = lb_tid();
   if (i >= n || !msm_live(i, set_live, sig_inf)) return;
   const uint64_t wd = scalars[i];
-  LB_UNROLL for (int h = 0; h < 2; h++) {
-    const uint32_t k = (uint32_t)(wd >> (32 * h));
-    LB_UNROLL for (int w = 0; w < LB_MSM_W; w++) {
-      const uint32_t d = (k >> (LB_MSM_C * w)) & (LB_MSM_B - 1);
-      if (d) {
-        const uint32_t b = w * LB_MSM_B + d;
-        members[boff[b] + atomicAdd(&cursor[b], 1u)] = i | ((uint32_t)h << 31);
-      }
-    }
-  }
+  LB_UNROLL for (int h = 0; h < 2; h++)
+    msm_for_digits<LB_MSM_W>((uint32_t)(wd >> (32 * h)), [=](int w, uint32_t d) {
+      const uint32_t b = w * LB_MSM_B + d;
+      members[boff[b] + atomicAdd(&cursor[b], 1u)] = i | ((uint32_t)h << 31);
+    });
 }
 #endif  // LB_KG
 // chunk c of a bucket: Jacobian sum of its member points (AoS affine signatures; bit 31 of a
@@ -1664,11 +1678,6 @@ __global__ void __launch_bounds__(LB_TPB, LB_MINW) k_msm_buckets(const uint32_t*
 // `out` (SoA, stride n_out).  The dependent chain is ~19 additions + 2 doublings + the Horner
 // doublings, against 34 additions + 12 doublings + the Horner for 16 lanes of 16 digits.  W = 4
 // (32-bit scalars) for the batch MSM, 6 for the search's weighted scalars (up to 43 bits).
-__device__ __forceinline__ g2j g2j_shfl_down(const g2j& a, unsigned d) {
-  return g2j{fp2{fp_shfl_down(a.x.c0, d), fp_shfl_down(a.x.c1, d)},
-             fp2{fp_shfl_down(a.y.c0, d), fp_shfl_down(a.y.c1, d)},
-             fp2{fp_shfl_down(a.z.c0, d), fp_shfl_down(a.z.c1, d)}};
-}
 #if LB_KG(6)
 template <int W>
 __global__ void __launch_bounds__(64 * W) k_msm_reduce(const uint32_t* __restrict__ bsum, uint32_t nb,
@@ -1683,7 +1692,7 @@ __global__ void __launch_bounds__(64 * W) k_msm_reduce(const uint32_t* __restric
   typedef jac<rf> g2jm;
   auto ld = [&](uint32_t e) { return soa_ld<g2j>(bw, nb, e); };
   auto add = [](const g2jm& a, const g2jm& b) { return jac_add_i(a, b); };
-  auto shfl = [](const g2jm& a, unsigned d) { return g2j_shfl_down(a, d); };
+  auto shfl = [](const g2jm& a, unsigned d) { return jac_shfl_down(a, d); };
   g2jm run = ld(e0 + 3);
   g2jm y = run;
   run = add(run, ld(e0 + 2));
@@ -1699,7 +1708,7 @@ __global__ void __launch_bounds__(64 * W) k_msm_reduce(const uint32_t* __restric
   }
   g2jm v = y;
   if (s) v = add(v, jac_dbl_i(jac_dbl_i(u)));
-  for (int l = 5; l >= 0; l--) {
+  for (int l = 5; l >= 0; l--) {  // (wave_sum64 with this kernel's out-of-line addition)
     const unsigned d = 1u << l;
     const g2jm o = shfl(v, d);
     if (s < d) v = add(v, o);
@@ -1911,7 +1920,7 @@ __global__ void __launch_bounds__(64) k_g2_sum64(uint32_t n_in, const uint32_t* 
   g2j v = i < n_in ? soa_ld<g2j>(in, n_in, i) : jac_infinity<fp2>();
   for (int l = 5; l >= 0; l--) {
     const unsigned d = 1u << l;
-    const g2j o = g2j_shfl_down(v, d);
+    const g2j o = jac_shfl_down(v, d);
     if (threadIdx.x < d) v = jac_add_i(v, o);
   }
   if (threadIdx.x == 0) soa_st(out, n_out, out0 + blockIdx.x, v);
@@ -2016,7 +2025,7 @@ __global__ void __launch_bounds__(LB_TPB) k_smsm_count(uint32_t T, uint32_t c, s
   const uint64_t wd = scalars[i];
   LB_UNROLL for (int h = 0; h < 2; h++) {
     const uint64_t k = (uint64_t)(uint32_t)(wd >> (32 * h)) * wt;
-    LB_UNROLL for (int w = 0; w < W; w++) {
+    LB_UNROLL for (int w = 0; w < W; w++) {  // msm_for_digits<W>(k, ...) in its own words (it compiles otherwise)
       const uint32_t d = (uint32_t)(k >> (LB_MSM_C * w)) & (LB_MSM_B - 1);
       if (d) atomicAdd(&cnt[j * (W * LB_MSM_B) + w * LB_MSM_B + d], 1u);
     }
@@ -2041,7 +2050,7 @@ __global__ void __launch_bounds__(LB_TPB) k_smsm_scatter(uint32_t T, uint32_t c,
   const uint64_t wd = scalars[i];
   LB_UNROLL for (int h = 0; h < 2; h++) {
     const uint64_t k = (uint64_t)(uint32_t)(wd >> (32 * h)) * wt;
-    LB_UNROLL for (int w = 0; w < W; w++) {
+    LB_UNROLL for (int w = 0; w < W; w++) {  // msm_for_digits<W>(k, ...) in its own words (it compiles otherwise)
       const uint32_t d = (uint32_t)(k >> (LB_MSM_C * w)) & (LB_MSM_B - 1);
       if (d) {
         const uint32_t b = j * (W * LB_MSM_B) + w * LB_MSM_B + d;
@@ -2135,7 +2144,7 @@ __global__ void __launch_bounds__(64) k_seg_sum64(const uint32_t* __restrict__ b
   g2j v = p < bhi[b] ? soa_ld<g2j>(terms, T, perm ? perm[p] : p) : jac_infinity<fp2>();
   for (int l = 5; l >= 0; l--) {
     const unsigned d = 1u << l;
-    const g2j o = g2j_shfl_down(v, d);
+    const g2j o = jac_shfl_down(v, d);
     if (threadIdx.x < d) v = jac_add_i(v, o);
   }
   if (threadIdx.x == 0) soa_st(part, nb, b, v);
@@ -2150,7 +2159,7 @@ __global__ void __launch_bounds__(64) k_seg_final(const uint32_t* __restrict__ b
   for (uint32_t k = bo[j] + threadIdx.x; k < bo[j + 1]; k += 64) v = jac_add_i(v, soa_ld<g2j>(part, nb, k));
   for (int l = 5; l >= 0; l--) {
     const unsigned d = 1u << l;
-    const g2j o = g2j_shfl_down(v, d);
+    const g2j o = jac_shfl_down(v, d);
     if (threadIdx.x < d) v = jac_add_i(v, o);
   }
   if (threadIdx.x == 0) soa_st(out, n_out, j, v);
@@ -2247,6 +2256,16 @@ __global__ void __launch_bounds__(64) k_test_pk(uint32_t nt, const uint32_t* __r
 }
 #endif  // LB_KG
 
+// The arguments of the next w_miller, ML(p, q) of two finite affine points, into LBW_PT: one lane
+// (lane 0) calls it, and a w_sync / __syncthreads follows before w_miller
+__device__ __forceinline__ void w_stage_pair(fp* S, const g1a& p, const g2a& q) {
+  w_st(S, LBW_PT + 0, p.x);
+  w_st(S, LBW_PT + 1, p.y);
+  w_st(S, LBW_PT + 2, q.x.c0);
+  w_st(S, LBW_PT + 3, q.x.c1);
+  w_st(S, LBW_PT + 4, q.y.c0);
+  w_st(S, LBW_PT + 5, q.y.c1);
+}
 // ML(PK, H_u) of a G1 Jacobian point into area dst (1 for infinity); lane 0 stages the points
 __device__ void w_miller_pk(fp* S, int dst, const g1j& pj_lane0, const uint32_t* __restrict__ h_aff, uint32_t n,
                             uint32_t u) {
@@ -2256,13 +2275,7 @@ __device__ void w_miller_pk(fp* S, int dst, const g1j& pj_lane0, const uint32_t*
     if (!s_inf) {
       g1a pa;
       g1_to_aff_inl(pa, pj_lane0);
-      const g2a h = soa_ld<g2a>(h_aff, n, u);
-      w_st(S, LBW_PT + 0, pa.x);
-      w_st(S, LBW_PT + 1, pa.y);
-      w_st(S, LBW_PT + 2, h.x.c0);
-      w_st(S, LBW_PT + 3, h.x.c1);
-      w_st(S, LBW_PT + 4, h.y.c0);
-      w_st(S, LBW_PT + 5, h.y.c1);
+      w_stage_pair(S, pa, soa_ld<g2a>(h_aff, n, u));
     }
   }
   w_sync();
@@ -2281,12 +2294,7 @@ __device__ void w_miller_negg1(fp* S, int dst, const g2j& q_lane0) {
     if (!s_inf) {
       g2a a;
       g2_to_aff_inl(a, q_lane0);
-      w_st(S, LBW_PT + 0, fp_load(LB_G1X));
-      w_st(S, LBW_PT + 1, fp_load(LB_G1NEGY));
-      w_st(S, LBW_PT + 2, a.x.c0);
-      w_st(S, LBW_PT + 3, a.x.c1);
-      w_st(S, LBW_PT + 4, a.y.c0);
-      w_st(S, LBW_PT + 5, a.y.c1);
+      w_stage_pair(S, g1a{fp_load(LB_G1X), fp_load(LB_G1NEGY)}, a);  // -G1
     }
   }
   w_sync();
@@ -2591,8 +2599,8 @@ __global__ void __launch_bounds__(LB_INV_TPB, LB_MINW) k_gsum_final(uint32_t n, 
   const bool act = u < nu;
   g1j acc = jac_infinity<fp>();
   if (act) {
-    if (wave_heads)  // the root's first chunk, then its chunks at wave boundaries
-      for (uint32_t c = gch[u]; c < gch[u + 1]; c = (c / LB_TPB + 1) * LB_TPB) acc = jac_add(acc, soa_ld<g1j>(gacc, n, c));
+    if (wave_heads)
+      for (uint32_t c = gch[u]; c < gch[u + 1]; c = seg_next_head(c)) acc = jac_add(acc, soa_ld<g1j>(gacc, n, c));
     else  // (under load) the root's chunk sums added on this lane
       for (uint32_t c = gch[u]; c < gch[u + 1]; c++) acc = jac_add(acc, soa_ld<g1j>(gacc, n, c));
   }
@@ -2706,12 +2714,7 @@ __global__ void __launch_bounds__(64) k_ml_S(uint32_t m, const uint32_t* __restr
     if (!s_inf) {
       g2a a;
       g2_to_aff_inl(a, Sj);
-      w_st(S, LBW_PT + 0, fp_load(LB_G1X));
-      w_st(S, LBW_PT + 1, fp_load(LB_G1NEGY));
-      w_st(S, LBW_PT + 2, a.x.c0);
-      w_st(S, LBW_PT + 3, a.x.c1);
-      w_st(S, LBW_PT + 4, a.y.c0);
-      w_st(S, LBW_PT + 5, a.y.c1);
+      w_stage_pair(S, g1a{fp_load(LB_G1X), fp_load(LB_G1NEGY)}, a);  // -G1
     }
   }
   w_sync();
@@ -2877,7 +2880,7 @@ __global__ void __launch_bounds__(LB_TPB, LB_MINW) k_pk_out96(uint32_t n, uint32
   g1j acc = jac_infinity<fp>();
   for (uint32_t c = c0; c < c1 && st == LB_OK; c++) {
     st = chunk_status[c];
-    if (st == LB_OK && (c == c0 || (c & (LB_TPB - 1)) == 0)) acc = jac_add(acc, soa_ld<g1j>(chunk_acc, nc, c));
+    if (st == LB_OK && seg_is_head(c, c0)) acc = jac_add(acc, soa_ld<g1j>(chunk_acc, nc, c));
   }
   uint8_t ob[96];
   g1a r;
@@ -2953,11 +2956,8 @@ __global__ void __launch_bounds__(LB_TPB, LB_MINW) k_g1_decompress(uint32_t n, c
   if (st == LB_OK && validate) {
     if (inf) {
       st = LB_PK_IS_INFINITY;
-    } else {
-      // r * P == O  (r = BLS12-381 subgroup order); plain check, one-time per key
-      uint32_t rr[8] = {0x00000001u, 0xffffffffu, 0xfffe5bfeu, 0x53bda402u,
-                        0x09a1d805u, 0x3339d808u, 0x299d7d48u, 0x73eda753u};
-      if (!jac_is_inf(jac_mul_u256(a, rr))) st = LB_POINT_NOT_IN_GROUP;
+    } else if (!g1_in_subgroup_r(a)) {
+      st = LB_POINT_NOT_IN_GROUP;
     }
   }
   uint8_t ob[96];
@@ -2968,17 +2968,21 @@ __global__ void __launch_bounds__(LB_TPB, LB_MINW) k_g1_decompress(uint32_t n, c
 #endif  // LB_KG
 
 // ---------------------------------------------------------------- synthetic data (bench/tests)
-// sk (32-byte big-endian, < r) -> 48-byte compressed and 96-byte uncompressed pubkey
+// secret key i of sks (32 bytes, big endian, < r) -> 8 little-endian words
+__device__ __forceinline__ void sk_load(uint32_t k[8], const uint8_t* __restrict__ sks, uint32_t i) {
+  for (int w = 0; w < 8; w++) {
+    const uint8_t* s = sks + (size_t)32 * i + 28 - 4 * w;
+    k[w] = ((uint32_t)s[0] << 24) | ((uint32_t)s[1] << 16) | ((uint32_t)s[2] << 8) | s[3];
+  }
+}
+// sk -> 48-byte compressed and 96-byte uncompressed pubkey
 #if LB_KG(2)
 __global__ void __launch_bounds__(LB_TPB, LB_MINW) k_sk_to_pk(uint32_t n, const uint8_t* __restrict__ sks,
                                                      uint8_t* __restrict__ out48, uint8_t* __restrict__ out96) {
   uint32_t i = lb_tid();
   if (i >= n) return;
   uint32_t k[8];
-  for (int w = 0; w < 8; w++) {
-    const uint8_t* s = sks + (size_t)32 * i + 28 - 4 * w;
-    k[w] = ((uint32_t)s[0] << 24) | ((uint32_t)s[1] << 16) | ((uint32_t)s[2] << 8) | s[3];
-  }
+  sk_load(k, sks, i);
   g1a g{fp_load(LB_G1X), fp_load(LB_G1Y)};
   g1a a;
   bool fin = jac_to_aff(a, jac_mul_u256(g, k));
@@ -2999,10 +3003,7 @@ __global__ void __launch_bounds__(LB_TPB, LB_MINW) k_sign(uint32_t n, const uint
   uint32_t i = lb_tid();
   if (i >= n) return;
   uint32_t k[8];
-  for (int w = 0; w < 8; w++) {
-    const uint8_t* s = sks + (size_t)32 * i + 28 - 4 * w;
-    k[w] = ((uint32_t)s[0] << 24) | ((uint32_t)s[1] << 16) | ((uint32_t)s[2] << 8) | s[3];
-  }
+  sk_load(k, sks, i);
   uint8_t m[32];
   for (int j = 0; j < 32; j++) m[j] = msgs[(size_t)32 * i + j];
   g2a h;

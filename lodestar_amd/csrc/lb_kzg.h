@@ -17,17 +17,9 @@
 #include "lb_fr.h"  // kzg_group_status
 #include "lb_kernels.h"
 
-// [r] P == O for an affine G1 point (r = the BLS12-381 subgroup order): the G1 subgroup check of
-// points that come from the wire (KZG commitments and proofs of gossip blob sidecars; c-kzg's
-// validate_kzg_g1 rejects the same points)
-__device__ __forceinline__ bool g1_in_subgroup_r(const g1a& a) {
-  const uint32_t rr[8] = {0x00000001u, 0xffffffffu, 0xfffe5bfeu, 0x53bda402u,
-                          0x09a1d805u, 0x3339d808u, 0x299d7d48u, 0x73eda753u};
-  return jac_is_inf(jac_mul_u256(a, rr));
-}
-
 // one point per thread: P_i (table entry i, or 48 compressed bytes) times scalar i (32 bytes,
-// little endian, < r) -> Jacobian SoA terms.  Given points are curve- and subgroup-checked.
+// little endian, < r) -> Jacobian SoA terms.  Given points are curve- and subgroup-checked
+// (lb_curve.h g1_in_subgroup_r).
 #if LB_KG(7)
 __global__ void __launch_bounds__(LB_TPB, LB_MINW) k_g1_terms(uint32_t n, const uint8_t* __restrict__ pts48,
                                                      const uint32_t* __restrict__ table, uint32_t table_cap,
@@ -55,7 +47,9 @@ __global__ void __launch_bounds__(LB_TPB, LB_MINW) k_g1_terms(uint32_t n, const 
 }
 #endif  // LB_KG
 
-// out[b] = sum of in[64 b .. 64 b + 63] (SoA, strides n_in / n_out), one wave per block
+// out[b] = sum of in[64 b .. 64 b + 63] (SoA, strides n_in / n_out), one wave per block.  (The tree
+// is wave_sum64's, kept in its own words: through the helper this kernel's registers come out in
+// another order.)
 #if LB_KG(7)
 __global__ void __launch_bounds__(64) k_g1_sum64(uint32_t n_in, const uint32_t* __restrict__ in, uint32_t n_out,
                                                  uint32_t* __restrict__ out) {
@@ -96,11 +90,7 @@ __global__ void __launch_bounds__(LB_TPB, LB_MINW) k_kzg_setup_g1(uint32_t n, co
   bool inf;
   int st = g1_decompress48(b, a, inf);
   if (st == LB_OK && inf) st = LB_PK_IS_INFINITY;
-  if (st == LB_OK) {
-    const uint32_t rr[8] = {0x00000001u, 0xffffffffu, 0xfffe5bfeu, 0x53bda402u,
-                            0x09a1d805u, 0x3339d808u, 0x299d7d48u, 0x73eda753u};
-    if (!jac_is_inf(jac_mul_u256(a, rr))) st = LB_POINT_NOT_IN_GROUP;
-  }
+  if (st == LB_OK && !g1_in_subgroup_r(a)) st = LB_POINT_NOT_IN_GROUP;
   if (st != LB_OK) {
     a.x = fp_zero();
     a.y = fp_zero();
@@ -126,6 +116,44 @@ __global__ void __launch_bounds__(64) k_kzg_setup_g2(uint32_t n, const uint8_t* 
 }
 #endif  // LB_KG
 
+// The two-pair pairing check that every KZG verification ends in,
+//   e(Q, -[tau^0] G2) e(P, G) == 1,   G = setup G2 point gi (g2: [tau^0] G2, [tau^1] G2, [tau^64] G2 as g2a),
+// for one wave (the block) on the wave engine; every lane calls it, with what LANE 0 computed: the
+// status st, and Q and P in affine form with their finite flags (the other lanes' arguments are not
+// read).  Lane 0's values go to all lanes through LDS, since the Miller-or-one choices must be
+// wave-uniform; a point at infinity pairs to 1, so Q = P = O accepts and exactly one of them at
+// infinity rejects.  Returns what the kernel writes: 1 / 0, or -st for a bad status, which never
+// reaches the pairing (Q and P need not be set then).  Uses areas LBW_A(0) and LBW_A(7).
+__device__ __forceinline__ int w_kzg_pairing_check(fp* S, int st, const g1a& qa, bool qfin, const g1a& pa, bool pfin,
+                                                   const uint32_t* __restrict__ g2, int gi) {
+  __shared__ int st_sh, qinf_sh, pinf_sh;
+  const int lane = threadIdx.x;
+  const g2a* G = reinterpret_cast<const g2a*>(g2);
+  if (lane == 0) {
+    st_sh = st;
+    qinf_sh = qfin ? 0 : 1;
+    pinf_sh = pfin ? 0 : 1;
+    if (st == LB_OK) w_stage_pair(S, qa, g2a_neg(G[0]));  // -G2
+  }
+  __syncthreads();
+  const int st_u = st_sh, qinf = qinf_sh, pinf = pinf_sh;
+  __syncthreads();
+  if (st_u != LB_OK) return -st_u;
+  if (qinf)
+    w_set_one(S, LBW_A(0));
+  else
+    w_miller(S, LBW_A(0));
+  if (lane == 0) w_stage_pair(S, pa, G[gi]);
+  __syncthreads();
+  if (pinf)
+    w_set_one(S, LBW_A(7));
+  else
+    w_miller(S, LBW_A(7));
+  w_mul(S, LBW_A(0), LBW_A(0), LBW_A(7));
+  w_final_exp(S, LBW_A(0), LBW_A(0));
+  return w_is_one(S, LBW_A(0)) ? 1 : 0;
+}
+
 // verify_kzg_proof_impl: e(C - [y] G1, -G2) e(pi, [tau] G2 - [z] G2) == 1, rewritten with the
 // scalar moved to G1 (bilinearity): e(Q, -G2) e(pi, [tau] G2) == 1 with Q = C - [y] G1 + [z] pi.
 // Lanes 0 and 1 compute [y] G1 and [z] pi side by side, lanes 2 and 3 the subgroup checks of C
@@ -137,7 +165,7 @@ __global__ void __launch_bounds__(64) k_kzg_check(const uint8_t* __restrict__ io
                                                   const uint32_t* __restrict__ g2, int32_t* __restrict__ ok) {
   LBW_SHARED_ML(S);
   __shared__ g1j sh[2];
-  __shared__ int st_sh, qinf_sh, pinf_sh, grp_sh[2];
+  __shared__ int grp_sh[2];
   const int lane = threadIdx.x;
   w_init_consts(S, LBW_PROGS_ALL);
   g1a c, pi;
@@ -165,54 +193,16 @@ __global__ void __launch_bounds__(64) k_kzg_check(const uint8_t* __restrict__ io
   }
   __syncthreads();
   if (st == LB_OK && !(grp_sh[0] && grp_sh[1])) st = LB_POINT_NOT_IN_GROUP;
+  g1a qa;
+  bool qfin = false;
   if (lane == 0) {
     g1j q = cinf ? jac_infinity<fp>() : jac_from_aff(c);
     q = jac_add_i(q, jac_neg(sh[0]));
     q = jac_add_i(q, sh[1]);
-    g1a qa;
-    const bool qfin = jac_to_aff(qa, q);
-    st_sh = st;
-    qinf_sh = qfin ? 0 : 1;
-    pinf_sh = pinf ? 1 : 0;
-    w_st(S, LBW_PT + 0, qa.x);
-    w_st(S, LBW_PT + 1, qa.y);
-    const g2a* G = reinterpret_cast<const g2a*>(g2);
-    const g2a g0 = G[0];
-    w_st(S, LBW_PT + 2, g0.x.c0);
-    w_st(S, LBW_PT + 3, g0.x.c1);
-    w_st(S, LBW_PT + 4, fp_neg(g0.y.c0));  // -G2
-    w_st(S, LBW_PT + 5, fp_neg(g0.y.c1));
+    qfin = jac_to_aff(qa, q);
   }
-  __syncthreads();
-  const int st_u = st_sh, qinf = qinf_sh, pinf_u = pinf_sh;
-  __syncthreads();
-  if (st_u != LB_OK) {
-    if (lane == 0) *ok = -st_u;
-    return;
-  }
-  if (qinf)
-    w_set_one(S, LBW_A(0));
-  else
-    w_miller(S, LBW_A(0));
-  if (lane == 0) {
-    const g2a* G = reinterpret_cast<const g2a*>(g2);
-    const g2a g1t = G[1];
-    w_st(S, LBW_PT + 0, pi.x);
-    w_st(S, LBW_PT + 1, pi.y);
-    w_st(S, LBW_PT + 2, g1t.x.c0);
-    w_st(S, LBW_PT + 3, g1t.x.c1);
-    w_st(S, LBW_PT + 4, g1t.y.c0);
-    w_st(S, LBW_PT + 5, g1t.y.c1);
-  }
-  __syncthreads();
-  if (pinf_u)
-    w_set_one(S, LBW_A(7));
-  else
-    w_miller(S, LBW_A(7));
-  w_mul(S, LBW_A(0), LBW_A(0), LBW_A(7));
-  w_final_exp(S, LBW_A(0), LBW_A(0));
-  const bool one = w_is_one(S, LBW_A(0));
-  if (lane == 0) *ok = one ? 1 : 0;
+  const int verdict = w_kzg_pairing_check(S, st, qa, qfin, pi, !pinf, g2, 1);
+  if (lane == 0) *ok = verdict;
 }
 #endif  // LB_KG
 
@@ -233,7 +223,6 @@ __global__ void __launch_bounds__(64) k_kzg_check_many(uint32_t n, const uint32_
                                                        const uint32_t* __restrict__ terms, const int32_t* __restrict__ tstatus,
                                                        const uint32_t* __restrict__ g2, int32_t* __restrict__ ok) {
   LBW_SHARED_ML(S);
-  __shared__ int st_sh, qinf_sh, pinf_sh;
   const int lane = threadIdx.x;
   const uint32_t k = blockIdx.x;
   if (k >= n) return;
@@ -249,21 +238,15 @@ __global__ void __launch_bounds__(64) k_kzg_check_many(uint32_t n, const uint32_
     if (q + 1 == m) t = jac_neg(t);
     v = jac_add_i(v, t);
   }
-  for (int l = 5; l >= 0; l--) {
-    const unsigned d = 1u << l;
-    const g1j o{fp_shfl_down(v.x, d), fp_shfl_down(v.y, d), fp_shfl_down(v.z, d)};
-    if (threadIdx.x < d) v = jac_add_i(v, o);
-  }
-  g1a pi;
+  v = wave_sum64(v, threadIdx.x);
+  int st = LB_OK;
+  g1a qa, pi;
+  bool qfin = false, pinf = false;
   if (lane == 0) {
-    int st = LB_OK;
     for (uint32_t j = lo; j < hi && st == LB_OK; j++)
       if (bstatus[j] != LB_OK) st = LB_BAD_SCALAR;
     for (uint32_t j = lo; j < hi && st == LB_OK; j++) st = tstatus[j];
     if (st == LB_OK) st = tstatus[i_pi];
-    bool pinf = false;
-    bool qfin = false;
-    g1a qa;
     if (st == LB_OK) {
       // pi in affine form for its Miller loop (its status is LB_OK: it decodes)
       uint8_t b[48];
@@ -271,50 +254,9 @@ __global__ void __launch_bounds__(64) k_kzg_check_many(uint32_t n, const uint32_
       st = g1_decompress48(b, pi, pinf);
       qfin = jac_to_aff(qa, v);
     }
-    if (st == LB_OK) {
-      w_st(S, LBW_PT + 0, qa.x);
-      w_st(S, LBW_PT + 1, qa.y);
-      const g2a* G = reinterpret_cast<const g2a*>(g2);
-      const g2a g0 = G[0];
-      w_st(S, LBW_PT + 2, g0.x.c0);
-      w_st(S, LBW_PT + 3, g0.x.c1);
-      w_st(S, LBW_PT + 4, fp_neg(g0.y.c0));  // -G2
-      w_st(S, LBW_PT + 5, fp_neg(g0.y.c1));
-    }
-    st_sh = st;
-    qinf_sh = qfin ? 0 : 1;
-    pinf_sh = pinf ? 1 : 0;
   }
-  __syncthreads();
-  const int st_u = st_sh, qinf = qinf_sh, pinf_u = pinf_sh;
-  __syncthreads();
-  if (st_u != LB_OK) {
-    if (lane == 0) ok[k] = -st_u;
-    return;
-  }
-  if (qinf)
-    w_set_one(S, LBW_A(0));
-  else
-    w_miller(S, LBW_A(0));
-  if (lane == 0) {
-    const g2a* G = reinterpret_cast<const g2a*>(g2);
-    const g2a g1t = G[1];
-    w_st(S, LBW_PT + 0, pi.x);
-    w_st(S, LBW_PT + 1, pi.y);
-    w_st(S, LBW_PT + 2, g1t.x.c0);
-    w_st(S, LBW_PT + 3, g1t.x.c1);
-    w_st(S, LBW_PT + 4, g1t.y.c0);
-    w_st(S, LBW_PT + 5, g1t.y.c1);
-  }
-  __syncthreads();
-  if (pinf_u)
-    w_set_one(S, LBW_A(7));
-  else
-    w_miller(S, LBW_A(7));
-  w_mul(S, LBW_A(0), LBW_A(0), LBW_A(7));
-  w_final_exp(S, LBW_A(0), LBW_A(0));
-  const bool one = w_is_one(S, LBW_A(0));
-  if (lane == 0) ok[k] = one ? 1 : 0;
+  const int verdict = w_kzg_pairing_check(S, st, qa, qfin, pi, !pinf, g2, 1);
+  if (lane == 0) ok[k] = verdict;
 }
 #endif  // LB_KG
 
@@ -339,7 +281,6 @@ __global__ void __launch_bounds__(64) k_kzg_check_groups(uint32_t n, const uint3
                                                          const int32_t* __restrict__ tstatus, const uint32_t* __restrict__ g2,
                                                          int32_t* __restrict__ ok) {
   LBW_SHARED_ML(S);
-  __shared__ int st_sh, qinf_sh, pinf_sh;
   const int lane = threadIdx.x;
   const uint32_t k = blockIdx.x;
   if (k >= n) return;
@@ -355,70 +296,23 @@ __global__ void __launch_bounds__(64) k_kzg_check_groups(uint32_t n, const uint3
     if (q == 2 * m) t = jac_neg(t);
     v = jac_add_i(v, t);
   }
-  for (int l = 5; l >= 0; l--) {
-    const unsigned d = 1u << l;
-    const g1j o{fp_shfl_down(v.x, d), fp_shfl_down(v.y, d), fp_shfl_down(v.z, d)};
-    if (threadIdx.x < d) v = jac_add_i(v, o);
-  }
+  v = wave_sum64(v, threadIdx.x);
   // P: the group's pi terms
   g1j u = jac_infinity<fp>();
   for (uint32_t q = lane; q < m; q += 64) u = jac_add_i(u, soa_ld<g1j>(terms, n_pts, 2 * n_blobs + lo + q));
-  for (int l = 5; l >= 0; l--) {
-    const unsigned d = 1u << l;
-    const g1j o{fp_shfl_down(u.x, d), fp_shfl_down(u.y, d), fp_shfl_down(u.z, d)};
-    if (threadIdx.x < d) u = jac_add_i(u, o);
-  }
-  g1a pa;
+  u = wave_sum64(u, threadIdx.x);
+  int st = LB_OK;
+  g1a qa, pa;
+  bool qfin = false, pfin = false;
   if (lane == 0) {
-    const int st = kzg_group_status(bstatus, tstatus, n_blobs, lo, hi);
-    bool qfin = false, pfin = false;
+    st = kzg_group_status(bstatus, tstatus, n_blobs, lo, hi);
     if (st == LB_OK) {
-      g1a qa;
       qfin = jac_to_aff(qa, v);
       pfin = jac_to_aff(pa, u);
-      w_st(S, LBW_PT + 0, qa.x);
-      w_st(S, LBW_PT + 1, qa.y);
-      const g2a* G = reinterpret_cast<const g2a*>(g2);
-      const g2a g0 = G[0];
-      w_st(S, LBW_PT + 2, g0.x.c0);
-      w_st(S, LBW_PT + 3, g0.x.c1);
-      w_st(S, LBW_PT + 4, fp_neg(g0.y.c0));  // -G2
-      w_st(S, LBW_PT + 5, fp_neg(g0.y.c1));
     }
-    st_sh = st;
-    qinf_sh = qfin ? 0 : 1;
-    pinf_sh = pfin ? 0 : 1;
   }
-  __syncthreads();
-  const int st_u = st_sh, qinf = qinf_sh, pinf_u = pinf_sh;
-  __syncthreads();
-  if (st_u != LB_OK) {
-    if (lane == 0) ok[k] = -st_u;
-    return;
-  }
-  if (qinf)
-    w_set_one(S, LBW_A(0));
-  else
-    w_miller(S, LBW_A(0));
-  if (lane == 0) {
-    const g2a* G = reinterpret_cast<const g2a*>(g2);
-    const g2a g1t = G[1];
-    w_st(S, LBW_PT + 0, pa.x);
-    w_st(S, LBW_PT + 1, pa.y);
-    w_st(S, LBW_PT + 2, g1t.x.c0);
-    w_st(S, LBW_PT + 3, g1t.x.c1);
-    w_st(S, LBW_PT + 4, g1t.y.c0);
-    w_st(S, LBW_PT + 5, g1t.y.c1);
-  }
-  __syncthreads();
-  if (pinf_u)
-    w_set_one(S, LBW_A(7));
-  else
-    w_miller(S, LBW_A(7));
-  w_mul(S, LBW_A(0), LBW_A(0), LBW_A(7));
-  w_final_exp(S, LBW_A(0), LBW_A(0));
-  const bool one = w_is_one(S, LBW_A(0));
-  if (lane == 0) ok[k] = one ? 1 : 0;
+  const int verdict = w_kzg_pairing_check(S, st, qa, qfin, pa, pfin, g2, 1);
+  if (lane == 0) ok[k] = verdict;
 }
 #endif  // LB_KG
 
@@ -483,7 +377,6 @@ __global__ void __launch_bounds__(64) k_kzg_check_cells(uint32_t n, const uint32
                                                         const int32_t* __restrict__ tstatus, const uint32_t* __restrict__ g2,
                                                         int32_t* __restrict__ ok) {
   LBW_SHARED_ML(S);
-  __shared__ int st_sh, qinf_sh, pinf_sh;
   const int lane = threadIdx.x;
   const uint32_t k = blockIdx.x;
   if (k >= n) return;
@@ -497,69 +390,22 @@ __global__ void __launch_bounds__(64) k_kzg_check_cells(uint32_t n, const uint32
     const uint32_t idx = q < d ? 2 * n_cells + dlo + q : (q < d + m ? n_cells + lo + (q - d) : n_given + 64 * k + (q - d - m));
     v = jac_add_i(v, soa_ld<g1j>(terms, n_pts, idx));
   }
-  for (int l = 5; l >= 0; l--) {
-    const unsigned s = 1u << l;
-    const g1j o{fp_shfl_down(v.x, s), fp_shfl_down(v.y, s), fp_shfl_down(v.z, s)};
-    if (threadIdx.x < s) v = jac_add_i(v, o);
-  }
+  v = wave_sum64(v, threadIdx.x);
   // LL: the pi terms
   g1j u = jac_infinity<fp>();
   for (uint32_t q = lane; q < m; q += 64) u = jac_add_i(u, soa_ld<g1j>(terms, n_pts, lo + q));
-  for (int l = 5; l >= 0; l--) {
-    const unsigned s = 1u << l;
-    const g1j o{fp_shfl_down(u.x, s), fp_shfl_down(u.y, s), fp_shfl_down(u.z, s)};
-    if (threadIdx.x < s) u = jac_add_i(u, o);
-  }
-  g1a pa;
+  u = wave_sum64(u, threadIdx.x);
+  int st = LB_OK;
+  g1a qa, pa;
+  bool qfin = false, pfin = false;
   if (lane == 0) {
-    const int st = kzg_cell_group_status(tstatus + 2 * n_cells, dlo, dhi, cstatus, tstatus, lo, hi);
-    bool qfin = false, pfin = false;
+    st = kzg_cell_group_status(tstatus + 2 * n_cells, dlo, dhi, cstatus, tstatus, lo, hi);
     if (st == LB_OK) {
-      g1a qa;
       qfin = jac_to_aff(qa, v);
       pfin = jac_to_aff(pa, u);
-      w_st(S, LBW_PT + 0, qa.x);
-      w_st(S, LBW_PT + 1, qa.y);
-      const g2a* G = reinterpret_cast<const g2a*>(g2);
-      const g2a g0 = G[0];
-      w_st(S, LBW_PT + 2, g0.x.c0);
-      w_st(S, LBW_PT + 3, g0.x.c1);
-      w_st(S, LBW_PT + 4, fp_neg(g0.y.c0));  // -G2
-      w_st(S, LBW_PT + 5, fp_neg(g0.y.c1));
     }
-    st_sh = st;
-    qinf_sh = qfin ? 0 : 1;
-    pinf_sh = pfin ? 0 : 1;
   }
-  __syncthreads();
-  const int st_u = st_sh, qinf = qinf_sh, pinf_u = pinf_sh;
-  __syncthreads();
-  if (st_u != LB_OK) {
-    if (lane == 0) ok[k] = -st_u;
-    return;
-  }
-  if (qinf)
-    w_set_one(S, LBW_A(0));
-  else
-    w_miller(S, LBW_A(0));
-  if (lane == 0) {
-    const g2a* G = reinterpret_cast<const g2a*>(g2);
-    const g2a g64 = G[2];
-    w_st(S, LBW_PT + 0, pa.x);
-    w_st(S, LBW_PT + 1, pa.y);
-    w_st(S, LBW_PT + 2, g64.x.c0);
-    w_st(S, LBW_PT + 3, g64.x.c1);
-    w_st(S, LBW_PT + 4, g64.y.c0);
-    w_st(S, LBW_PT + 5, g64.y.c1);
-  }
-  __syncthreads();
-  if (pinf_u)
-    w_set_one(S, LBW_A(7));
-  else
-    w_miller(S, LBW_A(7));
-  w_mul(S, LBW_A(0), LBW_A(0), LBW_A(7));
-  w_final_exp(S, LBW_A(0), LBW_A(0));
-  const bool one = w_is_one(S, LBW_A(0));
-  if (lane == 0) ok[k] = one ? 1 : 0;
+  const int verdict = w_kzg_pairing_check(S, st, qa, qfin, pa, pfin, g2, 2);
+  if (lane == 0) ok[k] = verdict;
 }
 #endif  // LB_KG

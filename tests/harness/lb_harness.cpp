@@ -53,11 +53,7 @@ int h_g2_decompress(const uint8_t* b96, uint8_t* out192, int* inf) { g2a a; bool
 int h_g1_decompress(const uint8_t* b48, uint8_t* out96, int* inf) { g1a a; bool i; int st = g1_decompress48(b48, a, i); wr(out96, a.x); wr(out96 + 48, a.y); *inf = i; return st; }
 int h_g1_deserialize(const uint8_t* b96, uint8_t* out96, int* inf) { g1a a; bool i; int st = g1_deserialize96(b96, a, i); wr(out96, a.x); wr(out96 + 48, a.y); *inf = i; return st; }
 // PublicKey.keyValidate's subgroup test as k_g1_decompress and k_table_fill run it: [r]P == O by jac_mul_u256
-int h_g1_in_subgroup_r(const uint8_t* p96) {
-  const uint32_t rr[8] = {0x00000001u, 0xffffffffu, 0xfffe5bfeu, 0x53bda402u,
-                          0x09a1d805u, 0x3339d808u, 0x299d7d48u, 0x73eda753u};
-  return jac_is_inf(jac_mul_u256(rdg1(p96), rr));
-}
+int h_g1_in_subgroup_r(const uint8_t* p96) { return g1_in_subgroup_r(rdg1(p96)); }
 void h_g2_compress(const uint8_t* p192, uint8_t* out96) { g2_compress96(out96, rdg2(p192), false); }
 void h_g1_compress(const uint8_t* p96, uint8_t* out48) { g1_compress48(out48, rdg1(p96), false); }
 void h_miller(const uint8_t* p96, const uint8_t* q192, uint8_t* out576) { fp12_to_be576(out576, miller_loop(rdg1(p96), rdg2(q192))); }

@@ -126,6 +126,24 @@ def test_aggregate_proof_round_trip_and_tampering(kzg):
         kzg.verifyAggregateKzgProof(blobs[:1], [], proof)
 
 
+@pytest.mark.gpu
+def test_points_at_infinity_in_the_pairing_check(kzg):
+    """verify_kzg_proof with Q = C - [y] G1 + [z] pi or pi itself at infinity: a point at infinity
+    pairs to 1, so both at infinity accept and exactly one rejects"""
+    inf = bytes([0xC0]) + bytes(47)
+    z, y, s = 0x1234567, 0x89ABCDE, 0x5EED
+    g = o.g1_compress(o.G1)
+    # both: the zero polynomial, and a constant one (C = [y] G1 with the infinity proof)
+    assert kzg.verify_kzg_proof(inf, z, 0, inf) is True
+    assert kzg.verify_kzg_proof(o.g1_compress(o.g1_mul(o.G1, y)), z, y, inf) is True
+    # Q at infinity under a finite proof: pi = [s] G1 and C = [y - z s] G1
+    pi = o.g1_compress(o.g1_mul(o.G1, s))
+    assert kzg.verify_kzg_proof(o.g1_compress(o.g1_mul(o.G1, (y - z * s) % R)), z, y, pi) is False
+    # the proof at infinity under a finite Q = C - [y] G1
+    assert kzg.verify_kzg_proof(g, z, y, inf) is False
+    assert kzg.verify_kzg_proof(g, z, 0, inf) is False  # Q = C itself
+
+
 def _off_subgroup_g1():
     """an on-curve G1 point outside the order-r subgroup (cofactor component)"""
     x = 5

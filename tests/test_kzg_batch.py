@@ -187,6 +187,18 @@ def test_rejections_stay_local(dev, cars):
     assert got == expect
 
 
+def test_exactly_one_point_at_infinity_rejects(dev, cars):
+    """a one-blob sidecar whose proof is the point at infinity although its polynomial is not constant:
+    P is infinity, T = C - [y] G1 is not, and e(T, -G2) alone is not 1.  (The other way round, T at
+    infinity under a finite proof, would need C = [y] G1 - [x] pi with x hashed from C; both at
+    infinity is the empty sidecar of test_rejections_stay_local.)"""
+    blobs, comms, proof = cars[(0,)]
+    assert proof != INF
+    rc, got = c_batch(dev.engine.h, [(blobs, comms, INF)])
+    assert (rc, got) == (N.LB_OK, [0])
+    assert c_single(dev.engine.h, (blobs, comms, INF)) == 0
+
+
 def test_argument_errors(dev, cars):
     from lodestar_amd.engine import Engine
     lib = N.load()

@@ -166,6 +166,14 @@ def test_all_groups_accepted(host, dev, ref, monkeypatch):
     assert c_verify(dev.engine.h, [const, const], [ref["comms"][CONSTANT]] * 2, [INF, INF], [0, 2]) == (N.LB_OK, [1])
 
 
+def test_exactly_one_point_at_infinity_rejects(dev, ref):
+    """a one-blob group whose proof is the point at infinity although its polynomial is not constant:
+    P is infinity, T = C - [y] G1 is not, and e(T, -G2) alone is not 1.  (The other way round, T at
+    infinity under a finite P, would need C = [y] G1 - [z] pi with z hashed from C.)"""
+    assert ref["proofs"][1] != INF
+    assert c_verify(dev.engine.h, [BLOBS[1]], [ref["comms"][1]], [INF], [0, 1]) == (N.LB_OK, [0])
+
+
 def test_rejections_stay_local(host, dev, ref):
     comms, proofs = ref["comms"], ref["proofs"]
     h = dev.engine.h

@@ -156,6 +156,23 @@ def test_all_groups_accepted(host, fx, monkeypatch):
     assert c_verify(h, [c9], [5], [S.values_to_blob([10] * 64)], [INF], [0, 1]) == (N.LB_OK, [0])
 
 
+def test_exactly_one_point_at_infinity_rejects(host):
+    """one group of one cell (its combiner power is r^0 = 1, so the points can be chosen): the cell is
+    the constant v, the proof pi = [s] G1 and the commitment C = [v - h^64 s] G1, which makes
+    RL = C + [h^64] pi - [v] G1 the point at infinity under a finite LL = pi: e(pi, [tau^64] G2) alone
+    is not 1.  The converse (LL at infinity, RL not) is the constant cell with the wrong commitment of
+    test_all_groups_accepted."""
+    h = host.engine.h
+    v, s, idx = 10, 0x5EED, 5
+    h64 = pow(K.coset_shift(idx), 64, R)
+    pi = o.g1_compress(o.g1_mul(o.G1, s))
+    comm = o.g1_compress(o.g1_mul(o.G1, (v - h64 * s) % R))
+    cell = S.values_to_blob([v] * 64)
+    assert c_verify(h, [comm], [idx], [cell], [pi], [0, 1]) == (N.LB_OK, [0])
+    # the same cell under its own commitment and proof accepts: both points at infinity
+    assert c_verify(h, [o.g1_compress(o.g1_mul(o.G1, v))], [idx], [cell], [INF], [0, 1]) == (N.LB_OK, [1])
+
+
 def test_rejections_stay_local(host, fx):
     h = host.engine.h
     c, i, cells, p = fx["c"], fx["i"], fx["cells"], fx["p"]
