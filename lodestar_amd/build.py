@@ -201,7 +201,9 @@ def build_cpu_pool(force=False, verbose=True):
     return _build_so(src, CPU_POOL, flags=("-O3", "-pthread"), force=force, verbose=verbose)
 
 
-UBENCH = ["fpmul_asm"]  # tools/ubench programs the GPU tests run (correctness of the asm Fp multiply)
+# tools/ubench programs the GPU tests run (correctness of the asm Fp multiply; the row, wave and
+# group engines' arithmetic at operand level)
+UBENCH = ["fpmul_asm", "lanes_check"]
 
 
 def build_ubench(force=False, verbose=True):

@@ -12,6 +12,9 @@
 // Representation (tools/gen_row_programs.py mirrors it exactly): a slot holds an integer v in
 // (-2p, 2p) congruent to x R' (mod p), R' = 2^392, as v = sum_k l_k 2^(28 k) with l_0..l_12 in
 // [-1, 2^28 + 2) and l_13 a small signed top limb.  Slot s, limb k at LDS word 16 s + k.
+// (Limb sums leave the two carry rounds of r_norm within [-1, 2^28]; a product's columns, whose
+// carry has a third 28-bit piece, can add one more.  tests/test_lane_engines_gpu.py holds rp_mul,
+// r_reduce, r_operand and the import / export pairs below to the model limb for limb.)
 //
 // Product (rp_mul): x replicated in every lane of the row (14 registers), y distributed.
 //   columns of x y: lane k accumulates column k (lo) and column k + 16 (hi), 64-bit, while y

@@ -26,7 +26,7 @@ def test_row_product_model_against_big_integers():
         r = R.rp_mul(R.limbs(a), R.limbs(b))
         v = R.val(r)
         assert (v - a * b * pow(R.RP, -1, R.P)) % R.P == 0
-        assert all(-2 <= x < (1 << 28) + 3 for x in r[:13])
+        assert all(-1 <= x < (1 << 28) + 2 for x in r[:13])
         if bits <= 386:
             assert abs(v) < 2 * R.P   # the slot invariant
     # reduced limb sums: any signed combination of slot values lands in [0, p) up to far below p
@@ -79,7 +79,7 @@ def test_written_out_pdbl_and_csqr_on_the_row_model():
     for _ in range(70):  # a ladder's run of doublings on the carried slots
         s = pdbl(s)
         want = o.g2_add(want, want)
-        assert all(-2 <= x < (1 << 28) + 3 for l in s for x in l[:13])
+        assert all(-1 <= x < (1 << 28) + 2 for l in s for x in l[:13])
     X, Y, Z = [(R.from_row(s[2 * c]), R.from_row(s[2 * c + 1])) for c in range(3)]
     zi = o.f2_inv(Z)
     assert (o.f2_mul(X, zi), o.f2_mul(Y, zi)) == want
@@ -146,7 +146,7 @@ def test_written_out_mul12_on_the_row_model():
         b = [rnd.randrange(o.P) for _ in range(12)]
         acc = mul(acc, [R.to_row(v) for v in b])
         want = o.f12_mul(want, tw(b))
-        assert all(-2 <= x < (1 << 28) + 3 for l in acc for x in l[:13])
+        assert all(-1 <= x < (1 << 28) + 2 for l in acc for x in l[:13])
     assert [R.from_row(l) for l in acc] == flatf(want)
 
 
