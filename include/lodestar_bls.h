@@ -446,6 +446,16 @@ uint32_t lb_pubkey_comb_size(const lb_engine* e);
 uint64_t lb_pubkey_comb_sets(const lb_engine* e);
 
 /*
+ * The signatures' subgroup check once per batch.  A batch on the bucket MSM whose blinding scalars
+ * the engine draws itself skips the per-signature test: 64 random 0/1 combinations of the MSM's
+ * bucket sums take it instead.  If one of them fails, the same batch runs again with the
+ * per-signature test, so every code is what that test gives.  Returns the pipeline runs that took
+ * the per-batch test so far; *fallbacks (may be NULL) gets how many of them ran again.
+ * Environment, read at engine creation: LB_SUBGROUP_BATCH=0 = the per-signature test always.
+ */
+uint64_t lb_subgroup_batch_runs(const lb_engine* e, uint64_t* fallbacks);
+
+/*
  * Like lb_batch_create, but set i aggregates table entries pk_indices[set_pk_offsets[i] ..
  * set_pk_offsets[i+1]) instead of carrying pubkey bytes (4 bytes per key on the bus instead of 96).
  * An index beyond the table makes that set's job reject with LB_ERR_ARGUMENT.  pk_indices may be

@@ -92,6 +92,7 @@ SIGNATURES = {
     "lb_pubkey_table_size": (ctypes.c_uint32, [_vp]),
     "lb_pubkey_comb_size": (ctypes.c_uint32, [_vp]),
     "lb_pubkey_comb_sets": (ctypes.c_uint64, [_vp]),
+    "lb_subgroup_batch_runs": (ctypes.c_uint64, [_vp, _u64p]),
     "lb_batch_create_indexed": (ctypes.c_int32, [_vp, ctypes.c_uint32, _u32p, _u32p, _u32p, _u8p, _u8p, _u32p,
                                                  ctypes.POINTER(_vp)]),
     "lb_engine_set_profiling": (ctypes.c_int32, [_vp, ctypes.c_int32]),

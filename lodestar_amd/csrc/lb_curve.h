@@ -632,6 +632,17 @@ LB_HD bool g2_aff_in_subgroup_i(const g2a& a) {
   return fp2_eq(fp2_mul(fp2_mul(py, z2), acc.z), fp2_neg(acc.y));
 }
 
+// One share of a test point of the per-batch subgroup check (lb_kernels.h k_subgroup_mix, a lane's;
+// DESIGN §5.10): the sum of the bucket sums ld(b), b = first, first + stride, ... < nb, whose bit of
+// `bits` (bit b in word b / 32) is set.  The buckets may hold anything on the curve: jac_add_i is complete.
+template <class Ld>
+LB_HD g2j g2_mix_share(Ld&& ld, const uint32_t* bits, uint32_t first, uint32_t stride, uint32_t nb) {
+  g2j v = jac_infinity<fp2>();
+  for (uint32_t b = first; b < nb; b += stride)
+    if ((bits[b >> 5] >> (b & 31)) & 1u) v = jac_add_i(v, ld(b));
+  return v;
+}
+
 // h_eff * P via psi (RFC 9380 App. G.3 / Budroni-Pintore)
 LB_NI g2j g2_clear_cofactor(g2j p) {
   g2j t1 = jac_neg(jac_mul_xabs(p));  // [x]P

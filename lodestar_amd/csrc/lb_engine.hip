@@ -265,6 +265,7 @@ int32_t lb_engine_create_ex(int32_t device, uint32_t flags, lb_engine** out) {
   }
   if (const char* sm = getenv("LB_SEARCH_BLOCKS")) e->search_blk = std::atoi(sm) != 0;
   if (const char* sm = getenv("LB_ROOT_SHUFFLE")) e->root_shuffle = std::atoi(sm) != 0;
+  if (const char* sb = getenv("LB_SUBGROUP_BATCH")) e->subgroup_batch = std::atoi(sb) != 0;
   {
     const char* on = getenv("LB_PK_COMB");
     const char* mb = getenv("LB_PK_COMB_MB");
@@ -325,6 +326,8 @@ int32_t lb_engine_create_ex(int32_t device, uint32_t flags, lb_engine** out) {
   hipEventCreateWithFlags(&e->ev_pkst, hipEventDisableTiming);
   hipEventCreateWithFlags(&e->ev_sdec, hipEventDisableTiming);
   hipEventCreateWithFlags(&e->ev_sblind, hipEventDisableTiming);
+  hipEventCreateWithFlags(&e->ev_bsum, hipEventDisableTiming);
+  hipEventCreateWithFlags(&e->ev_sgb, hipEventDisableTiming);
   for (int i = 0; i < kStages; i++) {
     hipEventCreate(&e->ev0[i]);
     hipEventCreate(&e->ev1[i]);
@@ -364,6 +367,14 @@ int32_t lb_engine_create_ex(int32_t device, uint32_t flags, lb_engine** out) {
                            nullptr, nullptr);
         hipLaunchKernelGGL(k_sig_blind_g8, g8_waves(k.small_s_g8_max), dim3(64), 0, e->stream2, 0u, nullptr, nullptr,
                            nullptr, nullptr, nullptr);
+        // s3 also carries the per-batch subgroup test of a bucket-MSM batch (its pubkey work is on
+        // s2 then): k_subgroup_mix's out-of-line additions over LB_SGB_TESTS waves, SUBGROUP_G8 over
+        // the LB_SGB_TESTS mixed points
+        hipLaunchKernelGGL(k_subgroup_mix, dim3(LB_SGB_TESTS), dim3(64), 0, e->stream3, nullptr, 0u, nullptr, nullptr);
+        hipLaunchKernelGGL(k_subgroup_affine, dim3(1), dim3(LB_INV_TPB), 0, e->stream3, 0u, nullptr, nullptr, nullptr,
+                           nullptr);
+        hipLaunchKernelGGL(k_sig_subgroup_g8, dim3(LB_SGB_TESTS / 8), dim3(64), 0, e->stream3, 0u, nullptr, nullptr,
+                           nullptr);
         ok = hipGetLastError() == hipSuccess && hipStreamSynchronize(e->stream) == hipSuccess &&
              hipStreamSynchronize(e->stream2) == hipSuccess && hipStreamSynchronize(e->stream3) == hipSuccess;
       }
@@ -389,7 +400,8 @@ void lb_engine_destroy(lb_engine* e) {
                   &e->gch, &e->chunk_beg, &e->chunk_end, &e->members, &e->set_live, &e->gacc, &e->gp_aff,
                   &e->gp_inf, &e->chunk_root, &e->sig_aos, &e->bcnt, &e->bcursor, &e->boff, &e->bch, &e->bchunk_beg,
                   &e->bchunk_end, &e->bmembers, &e->bacc, &e->bsum, &e->wsum, &e->park, &e->pk_aff, &e->y_root,
-                  &e->s_terms, &e->s_part, &e->s_root, &e->rs_idx, &e->s_set};
+                  &e->s_terms, &e->s_part, &e->s_root, &e->rs_idx, &e->s_set, &e->sgb_bits, &e->sgb_w, &e->sgb_aff,
+                  &e->sgb_inf, &e->sgb_status, &e->sgb_flag};
   for (dbuf* b : bufs) b->release();
   e->kzg.release();
   for (dbuf& b : e->sx) b.release();
@@ -404,6 +416,8 @@ void lb_engine_destroy(lb_engine* e) {
   if (e->ev_pkst) hipEventDestroy(e->ev_pkst);
   if (e->ev_sdec) hipEventDestroy(e->ev_sdec);
   if (e->ev_sblind) hipEventDestroy(e->ev_sblind);
+  if (e->ev_bsum) hipEventDestroy(e->ev_bsum);
+  if (e->ev_sgb) hipEventDestroy(e->ev_sgb);
   hipStreamSynchronize(e->stream2);
   hipStreamSynchronize(e->stream3);
   if (e->scratch) delete e->scratch;
@@ -628,6 +642,10 @@ void lb_host_free(void* p) {
 uint32_t lb_pubkey_table_size(const lb_engine* e) { return e ? e->table_n : 0; }
 uint32_t lb_pubkey_comb_size(const lb_engine* e) { return e ? e->comb_n : 0; }
 uint64_t lb_pubkey_comb_sets(const lb_engine* e) { return e ? e->comb_sets : 0; }
+uint64_t lb_subgroup_batch_runs(const lb_engine* e, uint64_t* fallbacks) {
+  if (fallbacks) *fallbacks = e ? e->sgb_fallbacks : 0;
+  return e ? e->sgb_runs : 0;
+}
 
 int32_t lb_pubkey_table_append(lb_engine* e, uint32_t n, const uint8_t* keys, uint32_t key_size, int32_t validate,
                                int32_t* out_status, uint32_t* out_first_index) {
@@ -733,8 +751,10 @@ struct stage_scope {
 // Bucket sums -> S_j = sum_d d B_d per instance j (n_inst instances of W windows, buckets
 // [j W 256, (j+1) W 256) of bsum) -> element out0 + j of `out` (SoA, stride n_out).
 // entries: bucket entries (point, window) of the launch, an upper bound; the forms: pipe_plan_msm.
+// ev_bsum (optional): recorded on st after the bucket sums, before their reduction.
 static hipError_t msm_reduce(lb_engine* e, hipStream_t st, uint32_t bcap, uint32_t nb, uint32_t n_inst, int W,
-                             uint32_t* out, uint32_t n_out, uint32_t out0, uint64_t entries, uint32_t chunk) {
+                             uint32_t* out, uint32_t n_out, uint32_t out0, uint64_t entries, uint32_t chunk,
+                             hipEvent_t ev_bsum = nullptr) {
   const pipe_msm_plan p = pipe_plan_msm(e->knobs, entries, chunk, nb, device_alone(e));
   const bool w4 = W == LB_MSM_W;  // else LB_SMSM_W windows
   if (p.reduce == MSMR_WINDOW_HORNER) {
@@ -744,6 +764,10 @@ static hipError_t msm_reduce(lb_engine* e, hipStream_t st, uint32_t bcap, uint32
   const bool bg8 = p.buckets == MSMB_G8;  // one wave per bucket, else one lane
   hipLaunchKernelGGL(bg8 ? k_msm_buckets_g8 : k_msm_buckets, dim3(bg8 ? nb : nblk(nb)), dim3(bg8 ? 64 : LB_TPB), 0, st,
                      e->bch.as<uint32_t>(), e->bacc.as<uint32_t>(), bcap, e->bsum.as<uint32_t>(), nb);
+  if (ev_bsum) {
+    const hipError_t r = hipEventRecord(ev_bsum, st);
+    if (r != hipSuccess) return r;
+  }
   switch (p.reduce) {
     case MSMR_WINDOW_HORNER:
       hipLaunchKernelGGL(k_msm_window_g8, dim3(n_inst * W), dim3(256), 0, st, e->bsum.as<uint32_t>(), nb,
@@ -831,17 +855,38 @@ static hipError_t per_root_chain(lb_engine* e, uint32_t n, uint32_t nuh, uint32_
 // Runs the batch pipeline on two streams: the job S tree (leaf count mj = pow2 >= jobs) with
 // fS = ML(-G1, S_root) on s2, the message product tree (leaf count mu = pow2 >= sets, leaves
 // [0, n_u) live) on s1, joined on s1 ready for the root check.
+// force_per_set: the signatures' subgroup check by the per-set kernel whatever the plan says (the
+// rerun after a failing per-batch test; e->sgb_active tells the caller which one ran).
 static int32_t run_pipeline(lb_engine* e, lb_batch* b, const uint64_t* scalars, uint32_t& mj, uint32_t& mu,
-                            bool unblinded) {
+                            bool unblinded, bool force_per_set = false) {
   const uint32_t n = b->n_sets, nj = b->n_jobs;
   e->partial_serial = 0;
   const pipe_shape shape{n, b->n_chunks, b->n_comb, b->indexed, b->route_eng == e, scalars != nullptr, unblinded,
                          e->root_shuffle};
   e->plan = pipe_plan_batch(e->knobs, shape, device_alone(e));
   const pipe_batch_plan& bp = e->plan;
+  const bool sgb = n && !force_per_set && pipe_plan_subgroup_batch(bp, shape, e->subgroup_batch);
+  e->sgb_active = sgb;
   const uint32_t gchunk = gsum_chunk(bp.gsum);
   int st = fill_scalars(e, n, scalars, unblinded);
   if (st != LB_OK) return st;
+  if (sgb) {
+    // the tests' bit vectors: fresh per run, from the source of the blinding scalars
+    e->h_sgb_bits.resize((size_t)LB_SGB_TESTS * LB_SGB_WORDS);
+    size_t need = e->h_sgb_bits.size() * 4, got = 0;
+    uint8_t* dst = reinterpret_cast<uint8_t*>(e->h_sgb_bits.data());
+    while (got < need) {
+      ssize_t r = getrandom(dst + got, need - got, 0);
+      if (r < 0) return LB_ERR_DEVICE;
+      got += (size_t)r;
+    }
+    LB_HIP(e->sgb_bits.ensure(need));
+    LB_HIP(e->sgb_w.ensure((size_t)LB_SGB_TESTS * sizeof(g2j)));
+    LB_HIP(e->sgb_aff.ensure((size_t)LB_SGB_TESTS * sizeof(g2a)));
+    LB_HIP(e->sgb_inf.ensure((size_t)LB_SGB_TESTS * 4));
+    LB_HIP(e->sgb_status.ensure((size_t)LB_SGB_TESTS * 4));
+    LB_HIP(e->sgb_flag.ensure(8));
+  }
   mj = 1;
   while (mj < nj) mj <<= 1;
   mu = 1;
@@ -896,6 +941,7 @@ static int32_t run_pipeline(lb_engine* e, lb_batch* b, const uint64_t* scalars, 
     e->used[ST_TOTAL] = true;
   }
   if (n) LB_HIP(hipMemcpyAsync(e->scalars.p, e->h_scalars.data(), (size_t)n * 8, hipMemcpyHostToDevice, s1));
+  if (sgb) LB_HIP(hipMemcpyAsync(e->sgb_bits.p, e->h_sgb_bits.data(), e->h_sgb_bits.size() * 4, hipMemcpyHostToDevice, s1));
   // fork: s2 starts after s1's scalar upload
   LB_HIP(hipEventRecord(e->ev_fork, s1));
   LB_HIP(hipStreamWaitEvent(s2, e->ev_fork, 0));
@@ -971,7 +1017,8 @@ static int32_t run_pipeline(lb_engine* e, lb_batch* b, const uint64_t* scalars, 
                          b->has_sizes ? b->d_sig_sizes.as<uint32_t>() : nullptr, e->sig_aff.as<uint32_t>(),
                          e->sig_aos.as<uint4>(), e->sig_inf.as<uint32_t>(), e->sig_status.as<int32_t>());
       if (sb_par) LB_HIP(hipEventRecord(e->ev_sdec, s2));
-      switch (bp.subgroup) {
+      // (the per-batch test: no per-set kernel; sig_status stays as the decode left it)
+      if (!sgb) switch (bp.subgroup) {
         case SUBGROUP_W4:
           hipLaunchKernelGGL(k_sig_subgroup_w4, dim3(n), dim3(64), 0, s2, n, e->sig_aff.as<uint32_t>(),
                              e->sig_inf.as<uint32_t>(), e->sig_status.as<int32_t>());
@@ -1163,7 +1210,25 @@ static int32_t run_pipeline(lb_engine* e, lb_batch* b, const uint64_t* scalars, 
                            e->bchunk_beg.as<uint32_t>(), e->bchunk_end.as<uint32_t>(), e->bmembers.as<uint32_t>(),
                            e->sig_aos.as<uint4>(), bcap, e->bacc.as<uint32_t>(), (uint32_t)LB_MSM_NB);
         LB_HIP(msm_reduce(e, s2, bcap, LB_MSM_NB, 1u, LB_MSM_W, e->treeS.as<uint32_t>(), 2 * mj, 1u,
-                          (uint64_t)2 * LB_MSM_W * n, LB_MSM_CHUNK));
+                          (uint64_t)2 * LB_MSM_W * n, LB_MSM_CHUNK, sgb ? e->ev_bsum : nullptr));
+        if (sgb) {
+          // the per-batch subgroup test on s3 (idle: a bucket-MSM batch has its pubkey work on s2),
+          // beside the bucket reduction and ML(-G1, S), which do not need its result
+          LB_HIP(hipStreamWaitEvent(s3_, e->ev_bsum, 0));
+          LB_HIP(hipMemsetAsync(e->sgb_flag.p, 0, 8, s3_));
+          hipLaunchKernelGGL(k_subgroup_mix, dim3(LB_SGB_TESTS), dim3(64), 0, s3_, e->bsum.as<uint32_t>(),
+                             (uint32_t)LB_MSM_NB, e->sgb_bits.as<uint32_t>(), e->sgb_w.as<uint32_t>());
+          hipLaunchKernelGGL(k_subgroup_affine, dim3(1), dim3(LB_INV_TPB), 0, s3_, (uint32_t)LB_SGB_TESTS,
+                             e->sgb_w.as<uint32_t>(), e->sgb_aff.as<uint32_t>(), e->sgb_inf.as<uint32_t>(),
+                             e->sgb_status.as<int32_t>());
+          hipLaunchKernelGGL(k_sig_subgroup_g8, dim3(LB_SGB_TESTS / 8), dim3(64), 0, s3_, (uint32_t)LB_SGB_TESTS,
+                             e->sgb_aff.as<uint32_t>(), e->sgb_inf.as<uint32_t>(), e->sgb_status.as<int32_t>());
+          hipLaunchKernelGGL(k_subgroup_flag, dim3(nblk(std::max<uint32_t>(nj, LB_SGB_TESTS))), dim3(LB_TPB), 0, s3_, nj,
+                             b->d_job_off.as<uint32_t>(), e->sig_status.as<int32_t>(), e->sig_inf.as<uint32_t>(),
+                             e->pk_status.as<int32_t>(), e->job_status.as<int32_t>(), e->sgb_status.as<int32_t>(),
+                             e->sgb_flag.as<uint32_t>());
+          LB_HIP(hipEventRecord(e->ev_sgb, s3_));  // (s1 joins it below, after its own chain)
+        }
         break;
       }
     }
@@ -1191,8 +1256,19 @@ static int32_t run_pipeline(lb_engine* e, lb_batch* b, const uint64_t* scalars, 
   }
   LB_HIP(hipEventRecord(e->ev_s, s2));
   LB_HIP(hipStreamWaitEvent(s1, e->ev_s, 0));  // join
+  if (sgb) LB_HIP(hipStreamWaitEvent(s1, e->ev_sgb, 0));  // the flag words come back with the verdict
   LB_HIP(hipGetLastError());
   return LB_OK;
+}
+
+// After the readback that ends a run: counts a run of the per-batch subgroup test and tells whether
+// it failed (flag: k_subgroup_flag's two words), i.e. whether the batch runs again by the per-set test.
+static bool sgb_failed(lb_engine* e, const uint32_t flag[2]) {
+  if (!e->sgb_active) return false;
+  e->sgb_runs++;
+  if (!(flag[0] | flag[1])) return false;
+  e->sgb_fallbacks++;
+  return true;
 }
 
 // ---------------------------------------------------------------- invalid-set search
@@ -1466,22 +1542,30 @@ static int32_t verify_locked(lb_engine* e, lb_batch* b, const uint64_t* scalars,
   if (nj == 0) return LB_OK;
   uint32_t m = 1, mu = 1;
   busy_scope busy(e->device, e, e->latency);
-  int32_t st = run_pipeline(e, b, scalars, m, mu, true);
-  if (st != LB_OK) return st;
-  // root verdict on s1 (after the join)
-  LB_HIP(e->verdict.ensure(4));
-  {
-    stage_scope sc(e, ST_ROOT, e->stream);
-    LB_HIP(e->y_root.ensure(576));
-    hipLaunchKernelGGL(e->plan.fe == FE_ROW ? k_root_check_row : k_root_check, dim3(1), dim3(e->plan.fe == FE_ROW ? LBR_NT : 64), 0, e->stream, mu, e->treeP.as<uint32_t>(),
-                       e->fS.as<uint32_t>(), e->verdict.as<int32_t>(), e->y_root.as<uint32_t>());
-  }
-  LB_HIP(hipGetLastError());
+  int32_t st;
   std::vector<int32_t> jst(nj);
   int32_t root_ok = 0;
-  LB_HIP(hipMemcpyAsync(jst.data(), e->job_status.p, (size_t)nj * 4, hipMemcpyDeviceToHost, e->stream));
-  LB_HIP(hipMemcpyAsync(&root_ok, e->verdict.p, 4, hipMemcpyDeviceToHost, e->stream));
-  LB_HIP(hipStreamSynchronize(e->stream));
+  // a failing per-batch subgroup test discards its run, before any search round: the batch runs
+  // again by the per-set test, which is what gives the codes
+  for (bool per_set = false;; per_set = true) {
+    st = run_pipeline(e, b, scalars, m, mu, true, per_set);
+    if (st != LB_OK) return st;
+    // root verdict on s1 (after the join)
+    LB_HIP(e->verdict.ensure(4));
+    {
+      stage_scope sc(e, ST_ROOT, e->stream);
+      LB_HIP(e->y_root.ensure(576));
+      hipLaunchKernelGGL(e->plan.fe == FE_ROW ? k_root_check_row : k_root_check, dim3(1), dim3(e->plan.fe == FE_ROW ? LBR_NT : 64), 0, e->stream, mu, e->treeP.as<uint32_t>(),
+                         e->fS.as<uint32_t>(), e->verdict.as<int32_t>(), e->y_root.as<uint32_t>());
+    }
+    LB_HIP(hipGetLastError());
+    uint32_t sgb_flag[2] = {0u, 0u};
+    LB_HIP(hipMemcpyAsync(jst.data(), e->job_status.p, (size_t)nj * 4, hipMemcpyDeviceToHost, e->stream));
+    LB_HIP(hipMemcpyAsync(&root_ok, e->verdict.p, 4, hipMemcpyDeviceToHost, e->stream));
+    if (e->sgb_active) LB_HIP(hipMemcpyAsync(sgb_flag, e->sgb_flag.p, 8, hipMemcpyDeviceToHost, e->stream));
+    LB_HIP(hipStreamSynchronize(e->stream));
+    if (!sgb_failed(e, sgb_flag)) break;
+  }
   bool any_live = false;
   for (uint32_t j = 0; j < nj; j++) {
     out_job[j] = jst[j] == LB_OK ? 1 : -jst[j];
@@ -1513,20 +1597,25 @@ extern "C" int32_t lb_batch_partial(lb_engine* e, lb_batch* b, const uint64_t* s
     return LB_OK;
   }
   busy_scope busy(e->device, e, e->latency);
-  int32_t st = run_pipeline(e, b, scalars, m, mu, false);  // always blinded: multiplied with other partials
-  if (st != LB_OK) return st;
-  LB_HIP(e->parts.ensure(576));
-  {
-    stage_scope sc(e, ST_ROOT, e->stream);
-    hipLaunchKernelGGL(e->plan.fe == FE_ROW ? k_root_partial_row : k_root_partial, dim3(1), dim3(e->plan.fe == FE_ROW ? LBR_NT : 64), 0, e->stream, mu, e->treeP.as<uint32_t>(),
-                       e->fS.as<uint32_t>(), e->parts.as<uint8_t>());
-  }
-  LB_HIP(hipGetLastError());
   std::vector<int32_t> jst(b->n_jobs);
-  LB_HIP(hipMemcpyAsync(out576, e->parts.p, 576, hipMemcpyDeviceToHost, e->stream));
-  LB_HIP(hipMemcpyAsync(jst.data(), e->job_status.p, (size_t)b->n_jobs * 4, hipMemcpyDeviceToHost, e->stream));
-  if (e->profiling) hipEventRecord(e->ev1[ST_TOTAL], e->stream);
-  LB_HIP(hipStreamSynchronize(e->stream));
+  for (bool per_set = false;; per_set = true) {  // (as verify_locked)
+    int32_t st = run_pipeline(e, b, scalars, m, mu, false, per_set);  // always blinded: multiplied with other partials
+    if (st != LB_OK) return st;
+    LB_HIP(e->parts.ensure(576));
+    {
+      stage_scope sc(e, ST_ROOT, e->stream);
+      hipLaunchKernelGGL(e->plan.fe == FE_ROW ? k_root_partial_row : k_root_partial, dim3(1), dim3(e->plan.fe == FE_ROW ? LBR_NT : 64), 0, e->stream, mu, e->treeP.as<uint32_t>(),
+                         e->fS.as<uint32_t>(), e->parts.as<uint8_t>());
+    }
+    LB_HIP(hipGetLastError());
+    uint32_t sgb_flag[2] = {0u, 0u};
+    LB_HIP(hipMemcpyAsync(out576, e->parts.p, 576, hipMemcpyDeviceToHost, e->stream));
+    LB_HIP(hipMemcpyAsync(jst.data(), e->job_status.p, (size_t)b->n_jobs * 4, hipMemcpyDeviceToHost, e->stream));
+    if (e->sgb_active) LB_HIP(hipMemcpyAsync(sgb_flag, e->sgb_flag.p, 8, hipMemcpyDeviceToHost, e->stream));
+    if (e->profiling) hipEventRecord(e->ev1[ST_TOTAL], e->stream);
+    LB_HIP(hipStreamSynchronize(e->stream));
+    if (!sgb_failed(e, sgb_flag)) break;
+  }
   for (uint32_t j = 0; j < b->n_jobs; j++) out_job[j] = jst[j] == LB_OK ? 1 : -jst[j];
   finish_profile(e);
   e->partial_serial = b->serial;

@@ -129,6 +129,16 @@ struct lb_engine {
   pipe_batch_plan plan;
   // bucket MSM for sum r_i sig_i (k_msm_*)
   dbuf sig_aos, bcnt, bcursor, boff, bch, bchunk_beg, bchunk_end, bmembers, bacc, bsum, wsum;
+  // The signatures' subgroup check once per batch (lb_pipeline_plan.h pipe_plan_subgroup_batch,
+  // k_subgroup_*): LB_SUBGROUP_BATCH=0 turns it off.  sgb_active: the last run_pipeline took it, and
+  // its two flag words (sgb_flag) come back with the verdict; a set word reruns the batch with the
+  // per-set kernel.  The bits (LB_SGB_TESTS x LB_MSM_NB, from the CSPRNG per run) go up with the
+  // scalars; the side chain runs on s3 after the bucket sums (ev_bsum) and joins s1 (ev_sgb).
+  bool subgroup_batch = true, sgb_active = false;
+  std::vector<uint32_t> h_sgb_bits;
+  dbuf sgb_bits, sgb_w, sgb_aff, sgb_inf, sgb_status, sgb_flag;
+  hipEvent_t ev_bsum = nullptr, ev_sgb = nullptr;
+  uint64_t sgb_runs = 0, sgb_fallbacks = 0;  // lb_subgroup_batch_runs
   // parked lone-lane state: k_hash_finish's points (4 x 72 words per launched lane), k_miller_lane's T
   dbuf park;
   // serial of the batch upload whose lb_batch_partial left its state (trees, statuses, scalars) in

@@ -1840,6 +1840,77 @@ __global__ void __launch_bounds__(64) k_msm_horner_g8(const uint32_t* __restrict
 }
 #endif  // LB_KG
 
+// ---- The signatures' subgroup check once per batch.  The batch MSM's LB_MSM_NB
+// bucket sums B_b hold every live signature (and its [lambda] image) under non-zero digits of the
+// engine's own secret scalars.  LB_SGB_TESTS fresh random bit vectors gamma_j pick W_j = sum_b
+// gamma_j,b B_b, and Scott's test runs on the W_j instead of on every signature: a bucket whose sum
+// has a component outside G2 lets each W_j pass with probability <= 1/2.  Every addition on the way
+// (k_msm_chunks, k_msm_buckets[_g8], here) is the complete jac_add[_aff]_i / g8_add, so a point of
+// small order, a repeated point or a point and its negative meet no untested case.
+#define LB_SGB_TESTS 64
+#define LB_SGB_WORDS (LB_MSM_NB / 32)  // words of gamma_j: bit b at word b / 32, bit b % 32
+// W_j: one wave per test, lane l adds the picked buckets b = l (mod 64) in series (~8 of 16), then
+// the 64:1 shuffle sum -> element j of wmix (SoA, stride LB_SGB_TESTS).  nb != LB_MSM_NB: nothing
+// (the scratch reservation's empty launch).
+#if LB_KG(1)
+__global__ void __launch_bounds__(64) k_subgroup_mix(const uint32_t* __restrict__ bsum, uint32_t nb,
+                                                     const uint32_t* __restrict__ bits, uint32_t* __restrict__ wmix) {
+  static_assert(LB_MSM_NB % 64 == 0, "a lane's buckets: l, l + 64, ...");
+  const uint32_t j = blockIdx.x, l = threadIdx.x;
+  if (nb != LB_MSM_NB || j >= LB_SGB_TESTS) return;
+  g2j v = g2_mix_share([&](uint32_t b) { return soa_ld<g2j>(bsum, nb, b); }, bits + j * LB_SGB_WORDS, l, 64u, nb);
+  for (int lv = 5; lv >= 0; lv--) {  // (wave_sum64 with the out-of-line addition)
+    const unsigned d = 1u << lv;
+    const g2j o = jac_shfl_down(v, d);
+    if (l < d) v = jac_add_i(v, o);
+  }
+  if (l == 0) soa_st(wmix, LB_SGB_TESTS, j, v);
+}
+#endif  // LB_KG
+// The W_j to affine with one inversion (one workgroup), as k_sig_subgroup_g8 reads its points:
+// w_aff (SoA, stride n), w_inf (infinity counts as in the group), w_status = LB_OK.
+#if LB_KG(1)
+__global__ void __launch_bounds__(LB_INV_TPB) k_subgroup_affine(uint32_t n, const uint32_t* __restrict__ wmix,
+                                                                uint32_t* __restrict__ w_aff, uint32_t* __restrict__ w_inf,
+                                                                int32_t* __restrict__ w_status) {
+  static_assert(LB_SGB_TESTS == LB_INV_TPB, "one lane per test, one block inversion");
+  if (n != LB_SGB_TESTS) return;  // uniform
+  const uint32_t j = threadIdx.x;
+  bool inf;
+  const g2a a = g2_to_aff_block(soa_ld<g2j>(wmix, n, j), true, inf);
+  soa_st(w_aff, n, j, a);
+  w_inf[j] = inf ? 1u : 0u;
+  w_status[j] = LB_OK;
+}
+#endif  // LB_KG
+// The batch's flag words after k_sig_subgroup_g8 over the W_j.  flag[0]: a test failed.  flag[1]: a
+// dead job holds a signature that no test saw (only live sets enter the MSM) at a place where the
+// per-set test's verdict would have come before the job's status (job_status_of: after the pubkey
+// decode errors, in set order among the signatures, before an infinite pubkey).  Either sends the
+// batch through the per-set test.  The caller zeroes flag first.
+#if LB_KG(1)
+__global__ void __launch_bounds__(LB_TPB) k_subgroup_flag(uint32_t n_jobs, const uint32_t* __restrict__ job_off,
+                                                          const int32_t* __restrict__ sig_status,
+                                                          const uint32_t* __restrict__ sig_inf,
+                                                          const int32_t* __restrict__ pk_status,
+                                                          const int32_t* __restrict__ job_status,
+                                                          const int32_t* __restrict__ w_status,
+                                                          uint32_t* __restrict__ flag) {
+  static_assert(LB_SGB_TESTS == LB_TPB, "block 0 reads one test's verdict per lane");
+  const uint32_t j = lb_tid();
+  if (blockIdx.x == 0 && w_status[threadIdx.x] != LB_OK) flag[0] = 1u;
+  if (j >= n_jobs || job_status[j] == LB_OK) return;
+  const uint32_t a = job_off[j], e = job_off[j + 1];
+  for (uint32_t i = a; i < e; i++)
+    if (pk_status[i] != LB_OK && pk_status[i] != LB_PK_IS_INFINITY) return;
+  for (uint32_t i = a; i < e && sig_status[i] == LB_OK; i++)
+    if (!sig_inf[i]) {
+      flag[1] = 1u;
+      return;
+    }
+}
+#endif  // LB_KG
+
 // Small batches: S = sum r_i sig_i without the bucket MSM, whose chunk / bucket / reduction
 // chain is a fixed ~5 ms of serial G2 additions however few the sets.  Each live set's r_i sig_i
 // by 8 lanes (k_sig_blind_g8: GLV double-and-add, [lambda] sig = -psi^2(sig)), then 64:1 shuffle

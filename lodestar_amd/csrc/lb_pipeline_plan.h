@@ -186,6 +186,16 @@ inline pipe_batch_plan pipe_plan_batch(const pipe_knobs& k, const pipe_shape& s,
   return p;
 }
 
+// The signatures' subgroup check once per batch instead of once per set: the per-set
+// kernel of p.subgroup is skipped and LB_SGB_TESTS random 0/1 combinations of the bucket sums take
+// Scott's test.  Only on the bucket MSM, whose buckets hold every live signature, and only while
+// the engine draws the blinding scalars itself: the digits that place a signature in its buckets
+// must be secret from whoever chose the batch.  enabled: LB_SUBGROUP_BATCH (lb_engine::subgroup_batch).
+// p.subgroup keeps naming the per-set kernel, which a failing batch test falls back to.
+inline bool pipe_plan_subgroup_batch(const pipe_batch_plan& p, const pipe_shape& s, bool enabled) {
+  return p.ssum == SSUM_BUCKET_MSM && !s.scalars_given && enabled;
+}
+
 // pubkey chunks of <= LB_PK_CHUNK_SMALL keys (a small batch's aggregation is latency) or <= LB_PK_CHUNK
 inline bool pipe_pk_chunks_small(const pipe_knobs& k, uint32_t n_sets) { return n_sets <= k.row_max; }
 

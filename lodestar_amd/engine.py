@@ -279,6 +279,13 @@ class Engine:
         """Sets whose r PK came from those entries so far (lb_pubkey_comb_sets)."""
         return int(self.lib.lb_pubkey_comb_sets(self.h))
 
+    def subgroup_batch_runs(self) -> Tuple[int, int]:
+        """(pipeline runs that took the per-batch signature subgroup test, how many of them ran again
+        with the per-signature test) so far (lb_subgroup_batch_runs)."""
+        fb = ctypes.c_uint64(0)
+        runs = int(self.lib.lb_subgroup_batch_runs(self.h, ctypes.byref(fb)))
+        return runs, int(fb.value)
+
     def aggregate_pubkeys(self, sets_pubkeys: Sequence[Sequence[bytes]]) -> Tuple[List[bytes], List[int]]:
         off = [0]
         flat = []

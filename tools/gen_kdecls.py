@@ -28,7 +28,8 @@ GROUPS = {
     0: ["k_decompress_sigs", "k_table_fill", "k_g1_decompress", "k_msg_insert", "k_dedup_one", "k_msg_uid_input",
         "k_msg_uid", "k_msg_count", "k_msg_scan", "k_chunk_fill", "k_msg_scatter", "k_job_status",
         "k_set_one", "k_g2_set_inf"],
-    1: ["k_sig_subgroup", "k_sig_subgroup_g8", "k_sig_agg_chunks", "k_sig_agg_groups"],
+    1: ["k_sig_subgroup", "k_sig_subgroup_g8", "k_sig_agg_chunks", "k_sig_agg_groups", "k_subgroup_mix",
+        "k_subgroup_affine", "k_subgroup_flag"],
     2: ["k_hash_map", "k_sk_to_pk", "k_sign", "k_ssz_zero_hashes", "k_merkleize"],
     3: ["k_hash_finish"],
     4: ["k_miller_lane", "k_pk_chunks", "k_pk_chunks_idx", "k_pk_blind", "k_gsum_chunks", "k_gsum_final"],
