@@ -208,6 +208,49 @@ int32_t lb_merkleize(lb_engine* e, uint32_t n_trees, const uint32_t* chunk_offse
                      const uint32_t* depths, const uint64_t* mix_lengths, uint8_t* out_roots32);
 
 /*
+ * A segment's block signature sets from the SignedBeaconBlocks' SSZ bytes, as range sync and gossip
+ * deliver them (getBlockSignatureSets, state-transition/src/signatureSets/index.ts:26-72): every
+ * set's signing root and signature, and a reference that says which keys the host supplies from
+ * the state.  The device finds everything at offsets the bytes give (csrc/lb_ssz_walk.h) and hashes
+ * it (csrc/lb_ssz_sets.h); the host never walks a block.  One upload, a launch sequence that depends
+ * on nothing read back, one download, one stream synchronisation.
+ *
+ * Block b = ssz[byte_offsets[b], byte_offsets[b+1]) of ForkSeq forks[b] (0 phase0 .. 3 capella; a
+ * later fork is LB_ERR_ARGUMENT).  domains32[b] = 2 x 6 domains of 32 B: [the state's previous = 0 /
+ * current = 1 fork version][proposer, attester, randao, voluntary_exit, sync_committee,
+ * bls_to_execution_change]; a set takes version 0 when its message's epoch is below fork_epochs[b],
+ * as config.getDomain does.  The epoch is the block's (randao, proposer), the header's slot / 32
+ * (proposer slashing), target.epoch (attestation, attester slashing), the exit's, (max(slot, 1) - 1)
+ * / 32 (sync aggregate), state_slots[b] / 32 (BLS change).  flags & 1 leaves the proposer set out.
+ *
+ * out_status[b] = LB_OK; LB_BAD_ENCODING for bytes that are not a well-formed block of that fork
+ * (every offset is checked before use and nothing outside the block is read; the other blocks are
+ * unaffected); LB_VERIFY_FAIL for a sync aggregate without participants whose signature is not the
+ * point at infinity.  out_n_sets[b] = its sets (0 unless LB_OK), rows [b * LB_BLOCK_MAX_SETS, +n) of
+ * out_kind (LB_SET_*), out_roots32, out_sigs96 and out_ref (4 words a row), in the reference's order:
+ * randao, proposer slashings (two sets each), attester slashings (two each), attestations, exits,
+ * proposer, sync aggregate (none when no participant and the signature is infinity), BLS changes.
+ * out_ref: {validator index, 0, 0, 0} (randao, proposer, exit; proposer slashing: header 1's
+ * proposer for both sets); {data.slot, data.index, byte position of aggregation_bits in ssz, its
+ * byte length} (attestation); {0, count, position of attesting_indices, byte length} (attester
+ * slashing); {0, 0, position of the 64-byte bit vector, 64} (sync aggregate); {0, 0, position of
+ * from_bls_pubkey, 48} (BLS change).
+ *
+ * LB_ERR_ARGUMENT, with nothing launched: a needed pointer that is NULL, byte_offsets[0] != 0,
+ * decreasing offsets, a fork above 3, n_blocks > 64, more than 64 MiB in all.  n_blocks == 0 returns
+ * LB_OK at once.  lb_block_sets_syncs: the stream synchronisations these calls made on the engine.
+ */
+#define LB_BLOCK_MAX_SETS 199 /* 1 + 32 + 4 + 128 + 16 + 1 + 1 + 16 */
+enum { LB_SET_RANDAO, LB_SET_PROPOSER_SLASHING, LB_SET_ATTESTER_SLASHING, LB_SET_ATTESTATION,
+       LB_SET_VOLUNTARY_EXIT, LB_SET_PROPOSER, LB_SET_SYNC_AGGREGATE, LB_SET_BLS_TO_EXECUTION_CHANGE };
+int32_t lb_block_sets_from_ssz(lb_engine* e, uint32_t n_blocks, const uint32_t* byte_offsets, const uint8_t* ssz,
+                               const uint32_t* forks, const uint8_t* domains32, const uint64_t* fork_epochs,
+                               const uint64_t* state_slots, uint32_t flags, int32_t* out_status,
+                               uint32_t* out_n_sets, uint32_t* out_kind, uint8_t* out_roots32, uint8_t* out_sigs96,
+                               uint64_t* out_ref);
+uint64_t lb_block_sets_syncs(const lb_engine* e);
+
+/*
  * KZG (EIP-4844 blobs; the c-kzg calls behind packages/beacon-node/src/util/kzg.ts:15-65, SURVEY.md
  * §8(f) row 4).  Two levels: the group calls (lb_g1_lincomb, lb_kzg_verify_proof), for a host that
  * does the scalar-field work itself (lodestar_amd/kzg.py with field="host"), and the blob-level

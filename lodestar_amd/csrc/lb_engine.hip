@@ -401,7 +401,7 @@ void lb_engine_destroy(lb_engine* e) {
                   &e->gp_inf, &e->chunk_root, &e->sig_aos, &e->bcnt, &e->bcursor, &e->boff, &e->bch, &e->bchunk_beg,
                   &e->bchunk_end, &e->bmembers, &e->bacc, &e->bsum, &e->wsum, &e->park, &e->pk_aff, &e->y_root,
                   &e->s_terms, &e->s_part, &e->s_root, &e->rs_idx, &e->s_set, &e->sgb_bits, &e->sgb_w, &e->sgb_aff,
-                  &e->sgb_inf, &e->sgb_status, &e->sgb_flag};
+                  &e->sgb_inf, &e->sgb_status, &e->sgb_flag, &e->ssz_in, &e->ssz_work, &e->ssz_out};
   for (dbuf* b : bufs) b->release();
   e->kzg.release();
   for (dbuf& b : e->sx) b.release();
@@ -1853,6 +1853,89 @@ extern "C" int32_t lb_merkleize(lb_engine* e, uint32_t n_trees, const uint32_t* 
                                          (uint8_t*)p[3], (const uint8_t*)p[4], (uint8_t*)p[5]);
                     });
 }
+
+// A segment's signature sets from the blocks' SSZ bytes (lb_ssz_walk.h, lb_ssz_sets.h): one upload
+// (the per-block arguments, the domains and the bytes in one buffer), a launch sequence that
+// depends on nothing read back, one download, one synchronisation.
+extern "C" int32_t lb_block_sets_from_ssz(lb_engine* e, uint32_t n_blocks, const uint32_t* byte_offsets,
+                                          const uint8_t* ssz, const uint32_t* forks, const uint8_t* domains32,
+                                          const uint64_t* fork_epochs, const uint64_t* state_slots, uint32_t flags,
+                                          int32_t* out_status, uint32_t* out_n_sets, uint32_t* out_kind,
+                                          uint8_t* out_roots32, uint8_t* out_sigs96, uint64_t* out_ref) {
+  if (!e) return LB_ERR_ARGUMENT;
+  if (!n_blocks) return LB_OK;
+  if (n_blocks > 64 || !byte_offsets || !forks || !domains32 || !fork_epochs || !state_slots || !out_status ||
+      !out_n_sets || !out_kind || !out_roots32 || !out_sigs96 || !out_ref)
+    return LB_ERR_ARGUMENT;
+  if (byte_offsets[0] != 0) return LB_ERR_ARGUMENT;
+  for (uint32_t b = 0; b < n_blocks; b++)
+    if (byte_offsets[b + 1] < byte_offsets[b] || forks[b] > SSZ_CAPELLA) return LB_ERR_ARGUMENT;
+  const uint32_t total = byte_offsets[n_blocks];
+  if (total > (64u << 20) || (total && !ssz)) return LB_ERR_ARGUMENT;
+  const bool skip = (flags & 1u) != 0;
+  const size_t rows = (size_t)n_blocks * LB_SSZ_MAX_SETS;
+  // upload: arguments | domains | bytes
+  const size_t up_dom = (size_t)n_blocks * sizeof(ssz_blk_arg), up_ssz = up_dom + (size_t)n_blocks * 384;
+  const size_t up_bytes = up_ssz + total;
+  // work area: zero-subtree roots | indices | nodes | fold buffers (A and B per block)
+  const size_t w_blk = 64 * 32, w_nodes = w_blk + (((size_t)n_blocks * sizeof(ssz_blk) + 31) & ~(size_t)31);
+  const size_t w_fold = w_nodes + (size_t)n_blocks * LB_SSZ_N_NODES * 32;
+  // download: ref | roots | signatures | kind | status | set counts
+  const size_t d_roots = rows * 32, d_sigs = d_roots + rows * 32, d_kind = d_sigs + rows * 96;
+  const size_t d_status = d_kind + rows * 4, d_nsets = d_status + (size_t)n_blocks * 4;
+  const size_t down_bytes = d_nsets + (size_t)n_blocks * 4;
+  std::lock_guard<std::mutex> lk(e->mu);
+  LB_HIP(hipSetDevice(e->device));
+  e->ssz_up.resize(up_bytes);
+  ssz_blk_arg* args = reinterpret_cast<ssz_blk_arg*>(e->ssz_up.data());
+  uint64_t fold_nodes = 0;
+  for (uint32_t b = 0; b < n_blocks; b++) {
+    args[b] = ssz_blk_arg{byte_offsets[b], byte_offsets[b + 1], forks[b], 0, fork_epochs[b], state_slots[b], fold_nodes};
+    fold_nodes += 2 * (uint64_t)ssz_fold_cap(byte_offsets[b + 1] - byte_offsets[b]);
+  }
+  memcpy(e->ssz_up.data() + up_dom, domains32, (size_t)n_blocks * 384);
+  if (total) memcpy(e->ssz_up.data() + up_ssz, ssz, total);
+  e->ssz_down.resize(down_bytes);
+  const size_t work_cap = e->ssz_work.cap;
+  LB_HIP(e->ssz_in.ensure(up_bytes + 64));  // the walk never reads past a block's end; slack all the same
+  LB_HIP(e->ssz_work.ensure(w_fold + fold_nodes * 32));
+  LB_HIP(e->ssz_out.ensure(down_bytes));
+  if (e->ssz_work.cap != work_cap) e->ssz_zh_ready = false;  // a new allocation (maybe at the old address)
+  hipStream_t s1 = e->stream;
+  uint8_t* in = e->ssz_in.as<uint8_t>();
+  uint8_t* work = e->ssz_work.as<uint8_t>();
+  uint8_t* out = e->ssz_out.as<uint8_t>();
+  const ssz_blk_arg* d_args = reinterpret_cast<const ssz_blk_arg*>(in);
+  ssz_blk* d_blks = reinterpret_cast<ssz_blk*>(work + w_blk);
+  uint32_t* d_nodes = reinterpret_cast<uint32_t*>(work + w_nodes);
+  LB_HIP(hipMemcpyAsync(in, e->ssz_up.data(), up_bytes, hipMemcpyHostToDevice, s1));
+  LB_HIP(hipMemsetAsync(out, 0, down_bytes, s1));
+  if (!e->ssz_zh_ready) hipLaunchKernelGGL(k_ssz_zero_hashes, dim3(1), dim3(64), 0, s1, work);
+  hipLaunchKernelGGL(k_ssz_index, dim3(n_blocks), dim3(LB_SSZ_WG), 0, s1, n_blocks, d_args, in + up_ssz, skip ? 1u : 0u,
+                     d_blks, reinterpret_cast<int32_t*>(out + d_status), reinterpret_cast<uint32_t*>(out + d_nsets));
+  if (!skip)
+    hipLaunchKernelGGL(k_ssz_block_root, dim3(n_blocks), dim3(LB_SSZ_WG), 0, s1, n_blocks, d_args, in + up_ssz, d_blks,
+                       d_nodes, reinterpret_cast<uint32_t*>(work + w_fold), work);
+  hipLaunchKernelGGL(k_ssz_sets, dim3(nblk((uint32_t)rows)), dim3(LB_TPB), 0, s1, n_blocks, d_args, in + up_ssz,
+                     in + up_dom, skip ? 1u : 0u, d_blks, reinterpret_cast<const uint32_t*>(out + d_nsets), d_nodes, work,
+                     reinterpret_cast<uint32_t*>(out + d_kind), out + d_roots, out + d_sigs,
+                     reinterpret_cast<uint64_t*>(out));
+  LB_HIP(hipGetLastError());
+  LB_HIP(hipMemcpyAsync(e->ssz_down.data(), out, down_bytes, hipMemcpyDeviceToHost, s1));
+  e->ssz_syncs++;
+  LB_HIP(hipStreamSynchronize(s1));
+  e->ssz_zh_ready = true;
+  const uint8_t* dn = e->ssz_down.data();
+  memcpy(out_ref, dn, rows * 32);
+  memcpy(out_roots32, dn + d_roots, rows * 32);
+  memcpy(out_sigs96, dn + d_sigs, rows * 96);
+  memcpy(out_kind, dn + d_kind, rows * 4);
+  memcpy(out_status, dn + d_status, (size_t)n_blocks * 4);
+  memcpy(out_n_sets, dn + d_nsets, (size_t)n_blocks * 4);
+  return LB_OK;
+}
+
+extern "C" uint64_t lb_block_sets_syncs(const lb_engine* e) { return e ? e->ssz_syncs : 0; }
 
 extern "C" int32_t lb_g1_decompress(lb_engine* e, uint32_t n, const uint8_t* in48, uint8_t* out96,
                                     int32_t* out_status, int32_t validate) {

@@ -181,6 +181,13 @@ struct lb_engine {
   uint32_t comb_n = 0, comb_cap = 0, comb_max = 0;
   uint64_t comb_sets = 0;  // sets k_pk_blind_comb was launched over, all batches (lb_pubkey_comb_sets)
   kzg_state kzg;
+  // lb_block_sets_from_ssz (lb_ssz_sets.h): the upload, the work area (zero-subtree roots, block
+  // indices, node and fold scratch) and the packed results, kept between calls; the zero-subtree
+  // roots are computed once per work area.  ssz_syncs counts the call's stream synchronisations.
+  dbuf ssz_in, ssz_work, ssz_out;
+  bool ssz_zh_ready = false;
+  std::vector<uint8_t> ssz_up, ssz_down;
+  uint64_t ssz_syncs = 0;
   // profiling
   bool profiling = false;
   hipEvent_t ev0[kStages] = {}, ev1[kStages] = {};

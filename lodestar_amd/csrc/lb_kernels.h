@@ -118,6 +118,7 @@ __device__ __forceinline__ uint32_t lb_tid() { return blockIdx.x * blockDim.x + 
 #include "lb_group_exec.h"
 #include "lb_group.h"
 #include "lb_ssz.h"
+#include "lb_ssz_sets.h"
 
 // ---------------------------------------------------------------- block-wide batch inversion
 // Montgomery's trick across the LB_INV_TPB threads of a block: prefix and suffix products by

@@ -163,3 +163,28 @@ export type KzgRecoverGroup = {cellIndices: number[]; cells: Uint8Array[]};
 export type KzgSidecar = {blobs: Uint8Array[]; commitments: Uint8Array[]; proof: Uint8Array};
 /** One verifyBlobKzgProofBatch call: one proof per blob. */
 export type KzgBlobGroup = {blobs: Uint8Array[]; commitments: Uint8Array[]; proofs: Uint8Array[]};
+
+// ---- block signature sets from SSZ bytes (js/signing_roots.js; addon.blockSetsFromSsz = lb_block_sets_from_ssz)
+/** What getBlockSignatureSets reads from the cached state; only the keys are needed from it here. */
+export type StateView = {
+  genesisValidatorsRoot: Uint8Array; forkPreviousVersion: Uint8Array; forkCurrentVersion: Uint8Array;
+  forkEpoch: number; slot?: number; pubkey: (index: number) => unknown;
+  beaconCommittee: (slot: number, index: number) => number[]; syncCommittee: () => unknown[];
+  keyFromBytes?: (bytes48: Uint8Array) => unknown; forkSeq?: (slot: number) => number;
+};
+export type BlockSignatureSet = {
+  name: "randao" | "proposer_slashing" | "attester_slashing" | "attestation" | "voluntary_exit" | "proposer" |
+    "sync_aggregate" | "bls_to_execution_change";
+  type: "single" | "aggregate"; pubkey?: unknown; pubkeys?: unknown[]; signingRoot: Uint8Array; signature: Uint8Array;
+};
+/** rows [b * 199, b * 199 + nSets[b]) of kind / roots (32 B) / sigs (96 B) / ref (4 words) belong to block b */
+export type BlockSetRows = {status: Int32Array; nSets: Uint32Array; kind: Uint32Array; roots: Uint8Array;
+  sigs: Uint8Array; ref: BigUint64Array};
+export interface SigningRootsAddon {
+  blockSetsFromSsz(engine: unknown, byteOffsets: Uint32Array, ssz: Uint8Array, forks: Uint32Array, domains: Uint8Array,
+    forkEpochs: BigUint64Array, stateSlots: BigUint64Array, flags: number): BlockSetRows;
+}
+/** require("lodestar_amd/js/signing_roots").getBlockSignatureSetsFromSsz: the sets of SignedBeaconBlocks handed
+ * over as SSZ bytes (phase0 .. capella; at most 64 blocks and 64 MiB), or an Error per rejected block */
+export declare function getBlockSignatureSetsFromSsz(blocks: Uint8Array[], states: StateView | StateView[],
+  opts: {engine: unknown; skipProposerSignature?: boolean}): (BlockSignatureSet[] | Error)[];

@@ -396,6 +396,96 @@ function resolve(sets, merkleize) {
   return sets;
 }
 
+const LB_BLOCK_MAX_SETS = 199;
+const SET_KINDS = ["randao", "proposer_slashing", "attester_slashing", "attestation", "voluntary_exit", "proposer",
+  "sync_aggregate", "bls_to_execution_change"];
+const DOMAIN_ORDER = [DOMAIN_BEACON_PROPOSER, DOMAIN_BEACON_ATTESTER, DOMAIN_RANDAO, DOMAIN_VOLUNTARY_EXIT,
+  DOMAIN_SYNC_COMMITTEE, DOMAIN_BLS_TO_EXECUTION_CHANGE];
+
+/**
+ * getBlockSignatureSets for SignedBeaconBlocks as SSZ bytes, as range sync and gossip deliver them
+ * (at most 64 blocks and 64 MiB a call): the device finds and hashes everything
+ * (addon.blockSetsFromSsz = lb_block_sets_from_ssz: one upload, one download, one stream
+ * synchronisation); the host supplies the keys from `states` (one StateView per block, or one for
+ * all) and never walks a block.  Entry b is the sets getBlockSignatureSets gives for block b with
+ * signingRoot already bytes, or the Error of a block that is not a well-formed encoding of its fork
+ * or that fails "Empty sync committee signature is not infinity"; other blocks are unaffected.
+ * @param {Uint8Array[]} blocks @param {StateView|StateView[]} states
+ * @param {{engine: any, skipProposerSignature?: boolean}} opts
+ */
+function getBlockSignatureSetsFromSsz(blocks, states, opts) {
+  const n = blocks.length;
+  if (n === 0) return [];
+  const stateOf = (k) => (Array.isArray(states) ? states[k] : states);
+  const off = new Uint32Array(n + 1);
+  for (let k = 0; k < n; k++) off[k + 1] = off[k] + blocks[k].length;
+  const ssz = new Uint8Array(off[n]);
+  const forks = new Uint32Array(n);
+  const doms = new Uint8Array(n * 384);
+  const forkEpochs = new BigUint64Array(n);
+  const stateSlots = new BigUint64Array(n);
+  const FAR = 0xffffffffffffffffn;
+  for (let k = 0; k < n; k++) {
+    const st = stateOf(k);
+    const blk = blocks[k];
+    ssz.set(blk, off[k]);
+    // the slot sits at a fixed position (offset 4, signature 96, then the message): it picks the fork
+    const slot = blk.length >= 108 ? Number(new DataView(blk.buffer, blk.byteOffset + 100, 8).getBigUint64(0, true)) : 0;
+    forks[k] = st.forkSeq ? st.forkSeq(slot) : ForkSeq.capella;
+    forkEpochs[k] = Number.isFinite(st.forkEpoch) ? BigInt(st.forkEpoch) : FAR;
+    stateSlots[k] = BigInt(st.slot === undefined ? slot : Number(st.slot));
+    if (!st._domains32) {
+      st._domains32 = new Uint8Array(384);
+      [st.forkPreviousVersion, st.forkCurrentVersion].forEach((v, i) => DOMAIN_ORDER.forEach((t, j) =>
+        st._domains32.set(computeDomain(t, v, st.genesisValidatorsRoot), 32 * (6 * i + j))));
+    }
+    doms.set(st._domains32, 384 * k);
+  }
+  const r = addon.blockSetsFromSsz(opts.engine, off, ssz, forks, doms, forkEpochs, stateSlots,
+    opts.skipProposerSignature ? 1 : 0);
+  const out = [];
+  for (let k = 0; k < n; k++) {
+    if (r.status[k] === 5) {
+      out.push(Error("Empty sync committee signature is not infinity"));
+      continue;
+    }
+    if (r.status[k] !== 0) {
+      out.push(Error(`block ${k}: not a well-formed SignedBeaconBlock of fork ${forks[k]} (status ${r.status[k]})`));
+      continue;
+    }
+    const st = stateOf(k);
+    const keyFromBytes = st.keyFromBytes || ((x) => x);
+    const sets = [];
+    for (let i = k * LB_BLOCK_MAX_SETS; i < k * LB_BLOCK_MAX_SETS + r.nSets[k]; i++) {
+      const name = SET_KINDS[r.kind[i]];
+      const r0 = Number(r.ref[4 * i]), r1 = Number(r.ref[4 * i + 1]), pos = Number(r.ref[4 * i + 2]), nb = Number(r.ref[4 * i + 3]);
+      const raw = ssz.subarray(pos, pos + nb);
+      const set = {name, signingRoot: r.roots.slice(32 * i, 32 * i + 32), signature: r.sigs.slice(96 * i, 96 * i + 96)};
+      if (name === "attestation") {
+        const committee = st.beaconCommittee(r0, r1);
+        let nbits = 8 * (nb - 1) + 31 - Math.clz32(raw[nb - 1]);
+        const idx = [];
+        for (let j = 0; j < nbits && j < committee.length; j++) if ((raw[j >> 3] >> (j & 7)) & 1) idx.push(committee[j]);
+        idx.sort((a, b) => a - b);
+        Object.assign(set, {type: "aggregate", pubkeys: idx.map((v) => st.pubkey(v))});
+      } else if (name === "attester_slashing") {
+        const dv = new DataView(raw.buffer, raw.byteOffset, nb);
+        Object.assign(set, {type: "aggregate",
+          pubkeys: Array.from({length: r1}, (_, j) => st.pubkey(Number(dv.getBigUint64(8 * j, true))))});
+      } else if (name === "sync_aggregate") {
+        Object.assign(set, {type: "aggregate", pubkeys: st.syncCommittee().filter((_, j) => (raw[j >> 3] >> (j & 7)) & 1)});
+      } else if (name === "bls_to_execution_change") {
+        Object.assign(set, {type: "single", pubkey: keyFromBytes(raw.slice())});
+      } else {
+        Object.assign(set, {type: "single", pubkey: st.pubkey(r0)});
+      }
+      sets.push(set);
+    }
+    out.push(sets);
+  }
+  return out;
+}
+
 module.exports = {
   Tree,
   ForkSeq,
@@ -403,6 +493,8 @@ module.exports = {
   G2_POINT_AT_INFINITY,
   forkSchedule,
   getBlockSignatureSets,
+  getBlockSignatureSetsFromSsz,
+  SET_KINDS,
   getSyncCommitteeSignatureSet,
   beaconBlock,
   beaconBlockBody,

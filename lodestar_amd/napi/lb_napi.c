@@ -687,6 +687,61 @@ static napi_value merkleize(napi_env env, napi_callback_info info) {
   return out;
 }
 
+/* blockSetsFromSsz(engine, byteOffsets: Uint32Array (nBlocks + 1), ssz: Uint8Array, forks: Uint32Array,
+ *   domains: Uint8Array (nBlocks x 384), forkEpochs: BigUint64Array, stateSlots: BigUint64Array, flags: number)
+ *   -> {status: Int32Array, nSets: Uint32Array, kind: Uint32Array, roots: Uint8Array, sigs: Uint8Array,
+ *       ref: BigUint64Array}: lb_block_sets_from_ssz, a segment's signature sets from the blocks' SSZ bytes;
+ *   rows [b * 199, + nSets[b]) belong to block b.  Synchronous: one upload, one download. */
+static napi_value block_sets_from_ssz(napi_env env, napi_callback_info info) {
+  size_t argc = 8;
+  napi_value argv[8];
+  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  engine_box* b = NULL;
+  tview off, ssz, forks, dom, fe, ss;
+  uint32_t flags = 0;
+  if (argc < 8 || napi_get_value_external(env, argv[0], (void**)&b) != napi_ok || !b || !b->e ||
+      !get_view(env, argv[1], &off) || !off.present || off.type != napi_uint32_array || off.n < 1 ||
+      !get_view(env, argv[2], &ssz) || (ssz.present && ssz.type != napi_uint8_array) ||
+      !get_view(env, argv[3], &forks) || !forks.present || forks.type != napi_uint32_array || forks.n != off.n - 1 ||
+      !get_view(env, argv[4], &dom) || !dom.present || dom.type != napi_uint8_array || dom.n != (off.n - 1) * 384 ||
+      !get_view(env, argv[5], &fe) || !fe.present || fe.type != napi_biguint64_array || fe.n != off.n - 1 ||
+      !get_view(env, argv[6], &ss) || !ss.present || ss.type != napi_biguint64_array || ss.n != off.n - 1 ||
+      napi_get_value_uint32(env, argv[7], &flags) != napi_ok) {
+    napi_throw_type_error(env, NULL,
+                          "blockSetsFromSsz(engine, byteOffsets: Uint32Array, ssz: Uint8Array, forks: Uint32Array, "
+                          "domains: Uint8Array, forkEpochs: BigUint64Array, stateSlots: BigUint64Array, flags: number)");
+    return NULL;
+  }
+  const uint32_t n = (uint32_t)(off.n - 1);
+  const uint32_t* o = (const uint32_t*)off.data;
+  if (n && (size_t)o[n] > (ssz.present ? ssz.n : 0)) {
+    napi_throw_type_error(env, NULL, "blockSetsFromSsz: ssz shorter than byteOffsets[nBlocks]");
+    return NULL;
+  }
+  const size_t rows = (size_t)n * LB_BLOCK_MAX_SETS;
+  napi_value ab[6], out[6], obj;
+  void* p[6];
+  const size_t bytes[6] = {(size_t)n * 4, (size_t)n * 4, rows * 4, rows * 32, rows * 96, rows * 32};
+  for (int i = 0; i < 6; i++) NAPI_CALL(env, napi_create_arraybuffer(env, bytes[i], &p[i], &ab[i]));
+  if (n) {
+    const int32_t st = lb_block_sets_from_ssz(b->e, n, o, (const uint8_t*)ssz.data, (const uint32_t*)forks.data,
+                                              (const uint8_t*)dom.data, (const uint64_t*)fe.data,
+                                              (const uint64_t*)ss.data, flags, (int32_t*)p[0], (uint32_t*)p[1],
+                                              (uint32_t*)p[2], (uint8_t*)p[3], (uint8_t*)p[4], (uint64_t*)p[5]);
+    if (st != LB_OK) return throw_code(env, st);
+  }
+  NAPI_CALL(env, napi_create_typedarray(env, napi_int32_array, n, ab[0], 0, &out[0]));
+  NAPI_CALL(env, napi_create_typedarray(env, napi_uint32_array, n, ab[1], 0, &out[1]));
+  NAPI_CALL(env, napi_create_typedarray(env, napi_uint32_array, rows, ab[2], 0, &out[2]));
+  NAPI_CALL(env, napi_create_typedarray(env, napi_uint8_array, rows * 32, ab[3], 0, &out[3]));
+  NAPI_CALL(env, napi_create_typedarray(env, napi_uint8_array, rows * 96, ab[4], 0, &out[4]));
+  NAPI_CALL(env, napi_create_typedarray(env, napi_biguint64_array, rows * 4, ab[5], 0, &out[5]));
+  static const char* names[6] = {"status", "nSets", "kind", "roots", "sigs", "ref"};
+  NAPI_CALL(env, napi_create_object(env, &obj));
+  for (int i = 0; i < 6; i++) NAPI_CALL(env, napi_set_named_property(env, obj, names[i], out[i]));
+  return obj;
+}
+
 /* KZG group work (util/kzg.ts ckzg calls; synchronous, like c-kzg's) */
 static napi_value kzg_load_setup(napi_env env, napi_callback_info info) {
   size_t argc = 3;
@@ -1101,6 +1156,7 @@ static napi_value init(napi_env env, napi_value exports) {
       {"errorName", NULL, error_name, NULL, NULL, NULL, napi_default, NULL},
       {"hwQueues", NULL, hw_queues, NULL, NULL, NULL, napi_default, NULL},
       {"merkleize", NULL, merkleize, NULL, NULL, NULL, napi_default, NULL},
+      {"blockSetsFromSsz", NULL, block_sets_from_ssz, NULL, NULL, NULL, napi_default, NULL},
       {"kzgLoadSetup", NULL, kzg_load_setup, NULL, NULL, NULL, napi_default, NULL},
       {"g1Lincomb", NULL, g1_lincomb, NULL, NULL, NULL, napi_default, NULL},
       {"kzgVerifyProof", NULL, kzg_verify_proof, NULL, NULL, NULL, napi_default, NULL},

@@ -446,3 +446,113 @@ def resolve(sets: Sequence[BlockSet], merkleize) -> List[BlockSet]:
     for s, r in zip(sets, roots):
         s.signing_root = r
     return list(sets)
+
+
+# ------------------------------------------------------------------ block signature sets from SSZ bytes
+LB_BLOCK_MAX_SETS = 199
+LB_MAX_BLOCKS_PER_CALL = 64
+LB_MAX_BYTES_PER_CALL = 64 << 20
+SET_KINDS = ("randao", "proposer_slashing", "attester_slashing", "attestation", "voluntary_exit", "proposer",
+             "sync_aggregate", "bls_to_execution_change")
+_DOMAIN_ORDER = (DOMAIN_BEACON_PROPOSER, DOMAIN_BEACON_ATTESTER, DOMAIN_RANDAO, DOMAIN_VOLUNTARY_EXIT,
+                 DOMAIN_SYNC_COMMITTEE, DOMAIN_BLS_TO_EXECUTION_CHANGE)
+
+
+def _bits_le(raw: bytes, n: int) -> List[int]:
+    v = int.from_bytes(raw, "little")
+    return [(v >> i) & 1 for i in range(n)]
+
+
+def _sets_from_rows(block: bytes, base: int, state: StateView, kinds, roots, sigs, refs) -> List[BlockSet]:
+    """rows of lb_block_sets_from_ssz -> the BlockSets block_signature_sets gives; only the keys come
+    from the state, through the references (byte positions are relative to the call's buffer)"""
+    out = []
+    for kind, root, sig, ref in zip(kinds, roots, sigs, refs):
+        name = SET_KINDS[kind]
+        r0, r1, pos, nb = (int(x) for x in ref)
+        raw = block[pos - base:pos - base + nb]
+        if name in ("randao", "proposer", "voluntary_exit", "proposer_slashing"):
+            typ, keys = "single", [state.pubkey(r0)]
+        elif name == "attestation":
+            v = int.from_bytes(raw, "little")
+            bits = _bits_le(raw, v.bit_length() - 1)
+            idx = sorted(i for i, bit in zip(state.beacon_committee(r0, r1), bits) if bit)
+            typ, keys = "aggregate", [state.pubkey(i) for i in idx]
+        elif name == "attester_slashing":
+            typ, keys = "aggregate", [state.pubkey(int.from_bytes(raw[8 * i:8 * i + 8], "little")) for i in range(r1)]
+        elif name == "sync_aggregate":
+            typ = "aggregate"
+            keys = [k for k, bit in zip(state.sync_committee(), _bits_le(raw, SYNC_COMMITTEE_SIZE)) if bit]
+        else:
+            typ, keys = "single", [state.key_from_bytes(raw)]
+        out.append(BlockSet(name, typ, keys, bytes(root), bytes(sig)))
+    return out
+
+
+def block_signature_sets_ssz(engine, blocks: Sequence[bytes], states: Sequence[StateView],
+                             skip_proposer_signature: bool = False) -> List[Union[List[BlockSet], Exception]]:
+    """getBlockSignatureSets for SignedBeaconBlocks as SSZ bytes (what range sync and gossip deliver): the
+    device finds and hashes everything (lb_block_sets_from_ssz, one upload, one download and one stream
+    synchronisation per 64 blocks), the host supplies the keys from `states` and never walks a block.
+    Entry b is the BlockSets block_signature_sets gives for block b with signing_root already bytes, or
+    the ValueError of a block that is not a well-formed encoding of its fork or that fails the
+    reference's "Empty sync committee signature is not infinity"; other blocks are unaffected."""
+    from . import _native as N
+    from .engine import _check
+    assert len(blocks) == len(states)
+    out: List[Union[List[BlockSet], Exception]] = []
+    P = lambda a, t: a.ctypes.data_as(ctypes.POINTER(t))  # noqa: E731
+    domain_cache: Dict[tuple, bytes] = {}
+    lo = 0
+    while lo < len(blocks):
+        hi, total = lo, 0
+        while hi < len(blocks) and hi - lo < LB_MAX_BLOCKS_PER_CALL and (hi == lo or total + len(blocks[hi]) <= LB_MAX_BYTES_PER_CALL):
+            total += len(blocks[hi])
+            hi += 1
+        n = hi - lo
+        off = np.zeros(n + 1, dtype=np.uint32)
+        forks = np.zeros(n, dtype=np.uint32)
+        fork_epochs = np.zeros(n, dtype=np.uint64)
+        state_slots = np.zeros(n, dtype=np.uint64)
+        doms = []
+        for k in range(n):
+            blk, st = blocks[lo + k], states[lo + k]
+            off[k + 1] = off[k] + len(blk)
+            # the slot sits at a fixed position (offset 4, signature 96, then the message): it picks the fork
+            slot = int.from_bytes(blk[100:108], "little") if len(blk) >= 108 else 0
+            forks[k] = st.fork_seq(slot)
+            fork_epochs[k] = st.fork_epoch
+            state_slots[k] = slot if st.slot is None else int(st.slot)
+            key = (st.genesis_validators_root, st.fork_previous_version, st.fork_current_version)
+            if key not in domain_cache:
+                domain_cache[key] = b"".join(compute_domain(t, v, st.genesis_validators_root)
+                                             for v in (st.fork_previous_version, st.fork_current_version)
+                                             for t in _DOMAIN_ORDER)
+            doms.append(domain_cache[key])
+        ssz = np.frombuffer(b"".join(blocks[lo:hi]) or b"\0", dtype=np.uint8)
+        dom = np.frombuffer(b"".join(doms), dtype=np.uint8)
+        rows = n * LB_BLOCK_MAX_SETS
+        status = np.zeros(n, dtype=np.int32)
+        n_sets = np.zeros(n, dtype=np.uint32)
+        kind = np.zeros(rows, dtype=np.uint32)
+        roots = np.zeros((rows, 32), dtype=np.uint8)
+        sigs = np.zeros((rows, 96), dtype=np.uint8)
+        ref = np.zeros((rows, 4), dtype=np.uint64)
+        _check(engine.lib.lb_block_sets_from_ssz(
+            engine.h, n, P(off, ctypes.c_uint32), P(ssz, ctypes.c_uint8), P(forks, ctypes.c_uint32),
+            P(dom, ctypes.c_uint8), P(fork_epochs, ctypes.c_uint64), P(state_slots, ctypes.c_uint64),
+            1 if skip_proposer_signature else 0, P(status, ctypes.c_int32), P(n_sets, ctypes.c_uint32),
+            P(kind, ctypes.c_uint32), P(roots, ctypes.c_uint8), P(sigs, ctypes.c_uint8), P(ref, ctypes.c_uint64)))
+        for k in range(n):
+            if status[k] == N.LB_VERIFY_FAIL:
+                out.append(ValueError("Empty sync committee signature is not infinity"))
+            elif status[k] != N.LB_OK:
+                out.append(ValueError(f"block {lo + k}: not a well-formed SignedBeaconBlock of fork {int(forks[k])} "
+                                      f"({N.error_name(int(status[k]))})"))
+            else:
+                a, b = k * LB_BLOCK_MAX_SETS, k * LB_BLOCK_MAX_SETS + int(n_sets[k])
+                out.append(_sets_from_rows(blocks[lo + k], int(off[k]), states[lo + k], kind[a:b].tolist(),
+                                           [r.tobytes() for r in roots[a:b]], [s.tobytes() for s in sigs[a:b]],
+                                           ref[a:b].tolist()))
+        lo = hi
+    return out

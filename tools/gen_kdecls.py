@@ -19,7 +19,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "lodestar_amd", "csrc")
-FILES = ["lb_kernels.h", "lb_group_exec.h", "lb_kzg.h", "lb_kzg_field.h", "lb_kzg_fk20.h", "lb_ssz.h", "lb_latency.h"]
+FILES = ["lb_kernels.h", "lb_group_exec.h", "lb_kzg.h", "lb_kzg_field.h", "lb_kzg_fk20.h", "lb_ssz.h", "lb_ssz_sets.h", "lb_latency.h"]
 OUT = os.path.join(CSRC, "lb_kdecl.h")
 
 # kernel -> translation-unit group (balanced by measured compile time; the one-lane per-root and
@@ -30,7 +30,8 @@ GROUPS = {
         "k_set_one", "k_g2_set_inf"],
     1: ["k_sig_subgroup", "k_sig_subgroup_g8", "k_sig_agg_chunks", "k_sig_agg_groups", "k_subgroup_mix",
         "k_subgroup_affine", "k_subgroup_flag"],
-    2: ["k_hash_map", "k_sk_to_pk", "k_sign", "k_ssz_zero_hashes", "k_merkleize"],
+    2: ["k_hash_map", "k_sk_to_pk", "k_sign", "k_ssz_zero_hashes", "k_merkleize", "k_ssz_index",
+        "k_ssz_block_root", "k_ssz_sets"],
     3: ["k_hash_finish"],
     4: ["k_miller_lane", "k_pk_chunks", "k_pk_chunks_idx", "k_pk_blind", "k_gsum_chunks", "k_gsum_final"],
     14: ["k_gsum_wave", "k_pk_out96"],
